@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rectified images/sec of the TPS hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,16 @@ grid_sample HIP kernel on a batch of 512 synthetic 3x32x100 fp32 images, 20 fidu
 points = fiducial lattice + 0.05 * noise.  Inputs are resident in HBM before the timed region; the
 steps rotate over enough distinct input/output buffers (> 256 MB) that the Infinity Cache cannot
 hold the working set.  Weak scaling: every rank rectifies its own 512-image batches, there is no
-data-path collective (images are independent).  Two launch protocols are timed over exactly K steps each: all steps on ONE
+data-path collective (images are independent).
+
+A plain run does only what the headline needs: set-up, W warm-up steps, ONE timed region of exactly K steps round-robin
+on `--streams` HIP streams (default 2 for K <= 200, else 3), then the JSON line (`value`, `ms_per_step` and the roofline
+fraction of that region).  `--dump-outputs DIR` writes what the last timed step computed, the rectified batch a caller
+of the path receives, as DIR/rectified.npy (float32, 19.7 MB); the inputs are the same from run to run.
+
+`--full` adds everything else, as described below: both launch protocols over `--repeats` regions each, the parity
+spot-check against the CPU oracle, the plain-copy ceiling, device clocks, `extra` and `cpu_baseline`.
+With `--full`, two launch protocols are timed over exactly K steps each: all steps on ONE
 stream (every launch waits for the previous one: kernel duration + launch gap, what a kernel trace shows), and the steps
 round-robin on `--streams` HIP streams (default 2 for K <= 200, else 3 -- consecutive batches are independent, so a serving
 loop has no reason to serialise their launches).  Each protocol's region is repeated (`--repeats`, default 5 for K <= 200: a
@@ -23,12 +32,12 @@ and one after its last launch, a region is latest end - earliest start -- max ov
 region is reported as `wall_ms_per_step`.
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself (torch.distributed.run as a
-child process; the parent never touches a GPU) and passes rank 0's JSON line through.  At N > 1 the line
+child process; the parent never touches a GPU) and passes rank 0's JSON line through.  At N > 1 with `--full` the line
 also carries `extra.recognizer_sharded`: the whole recogniser on 256 images per rank with the one collective
 of the inference path, the RCCL all-gather of the decoder scores, inside the timed region
 (tools/test.py:202-207).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 with two extra objects (the second under `--full` only):
   roofline     -- algorithmic HBM bytes per launch / average launch duration (HIP events on the
                   launch stream over the timed region) against the 8 TB/s HBM peak;
   cpu_baseline -- the CPU oracle (a port of the reference's algorithm, OpenMP over images) timed on
@@ -573,21 +582,28 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: both launch protocols over `--repeats` regions each, parity against the CPU "
+                         "oracle, plain-copy ceiling, device clocks, `extra` and `cpu_baseline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rectified batch of the last timed step to DIR/rectified.npy (float32)")
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed regions of `steps` steps per launch protocol, the fastest counts (0 = 5 when steps <= 200, else 1)")
+                    help="--full: timed regions of `steps` steps per launch protocol (0 = 5 when steps <= 200, else 1)")
     ap.add_argument("--streams", type=int, default=0,
                     help="HIP streams the steps are launched on, round-robin (1 = every launch waits for the previous one; "
                          "0 = 2 when steps <= 200, else 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="--full without `extra`")
     ap.add_argument("--precondition-ms", type=float, default=300.0,
                     help="device copies over the bench buffers before the warm-up steps: the chip leaves its idle "
                          "clocks only after some hundred ms of activity (not steps of the workload; 0 disables)")
     ap.add_argument("--dry-run", action="store_true", help="CPU / gloo check of the launch path, no GPU work")
     ap.add_argument("--sharded-extra", action="store_true",
-                    help="run extra.recognizer_sharded at N = 1 as well (a 1-rank RCCL group): exercises the N > 1 code path "
-                         "on a single-GPU box")
+                    help="--full: run extra.recognizer_sharded at N = 1 as well (a 1-rank RCCL group): exercises the N > 1 "
+                         "code path on a single-GPU machine")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(a))
@@ -699,6 +715,47 @@ def main():
 
     for i in range(a.warmup):
         step(i)
+    alg_bytes = BYTES_PER_IMG * BATCH
+    kernel = "tps_warp_pair_kernel<20,3,32,100,32,100,false,false>" if pair_kernel else \
+        "tps_warp_lds_mirror_kernel<20,3,32,100,false>"
+    if not a.full:
+        # ---- plain run: one region of exactly `steps` steps on S streams, nothing else on the device ----
+        barrier()
+        tt = torch.tensor(timed(a.steps, S, a.warmup), device=dev, dtype=torch.float64)    # (ms, wall s)
+        if world > 1:
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        ev_ms, dt = float(tt[0]), float(tt[1])
+        rec = None
+        if rank == 0:
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, outs[(a.warmup + a.steps - 1) % nbuf])
+            launch_us = ev_ms * 1e3 / a.steps
+            achieved = alg_bytes / (launch_us * 1e-6) / 1e9
+            rec = {
+                **headline(world, a.steps, a.warmup, ev_ms, dt),
+                "config": {"workload": "BASELINE.json configs[1]: fused TPS grid-gen + bilinear "
+                                       "grid_sample HIP kernel, batch 512 per GPU, 3x32x100 fp32, "
+                                       "20 fiducials, inputs resident in HBM",
+                           "batch_per_gpu": BATCH, "rotating_buffer_sets": int(nbuf),
+                           "working_set_MB": round(nbuf * per_set / 1e6, 1),
+                           "streams": S, "repeats": 1,
+                           "timing": f"one region of exactly `steps` launches (barrier + synchronize before it), step i on HIP "
+                                     f"stream i % {S}; HIP events per stream, region = latest end - earliest start, max over "
+                                     "ranks; --full for both launch protocols over repeated regions",
+                           "preconditioning": f"{a.precondition_ms:.0f} ms of plain device copies over the bench buffers "
+                                              "before the warm-up steps (clock ramp; not steps)"},
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "kernel": kernel, "algorithmic_bytes_per_launch": alg_bytes,
+                             "launch_us": launch_us,
+                             "launch_us_is": f"region of `steps` launches on {S} stream(s) / steps"
+                                             + ("; launches overlap: a period, not one kernel's duration" if S > 1 else "")},
+            }
+        if world > 1:
+            dist.destroy_process_group()
+        if rank == 0:
+            print_line(rec)
+        return
+
     # `repeats` timed regions of exactly `steps` steps per protocol (barrier + synchronize before each).  A 20-step region is
     # 0.2 ms: one region alone is at the mercy of the queues' wake-up after the synchronize.
     R = a.repeats if a.repeats > 0 else (5 if a.steps <= 200 else 1)
@@ -710,9 +767,11 @@ def main():
     for r in range(R):
         barrier()
         reg_m.append(timed(a.steps, S, a.warmup + 2 * r * a.steps))
+        last = a.warmup + (2 * r + 1) * a.steps - 1
         if S > 1:
             barrier()
             reg_1.append(timed(a.steps, 1, a.warmup + (2 * r + 1) * a.steps))
+            last = a.warmup + (2 * r + 2) * a.steps - 1
     if S == 1:
         reg_1 = reg_m
     # a region's time is the MAX over ranks (every rank times the same R regions behind the same barriers); the
@@ -724,6 +783,8 @@ def main():
         dist.all_reduce(tt_min, op=dist.ReduceOp.MIN)
     tt, tt_min = tt.cpu(), tt_min.cpu()
     clocks = device_clocks() if rank == 0 else None          # (right behind the last region: what the device ran at)
+    if rank == 0 and a.dump_outputs:                         # (before the parity step below rewrites buffer set 0)
+        dump_outputs(a.dump_outputs, outs[last % nbuf])
     regions_m = [float(x) for x in tt[0, :, 0]]              # ms per region, `steps` launches each
     regions_1 = [float(x) for x in tt[1, :, 0]]
 
@@ -785,8 +846,6 @@ def main():
 
     rec = None
     if rank == 0:
-        alg_bytes = BYTES_PER_IMG * BATCH
-
         def frac_of(us):
             return alg_bytes / (us * 1e-6) / 1e9 / HBM_PEAK_GBS
 
@@ -795,22 +854,8 @@ def main():
         launchm_us = to_us(ms_multi)                         # median region, S streams
         achieved = alg_bytes / (launch_us * 1e-6) / 1e9
         traffic, traffic_kernel = load_traffic()
-        kernel = "tps_warp_pair_kernel<20,3,32,100,32,100,false,false>" if pair_kernel else \
-            "tps_warp_lds_mirror_kernel<20,3,32,100,false>"
         rec = {
-            "metric": "rectified images/sec (3x32x100)",
-            "value": world * BATCH * a.steps / (ev_ms * 1e-3),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": ev_ms / a.steps,
-            "wall_ms_per_step": dt * 1e3 / a.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
+            **headline(world, a.steps, a.warmup, ev_ms, dt),
             "config": {"workload": "BASELINE.json configs[1]: fused TPS grid-gen + bilinear "
                                    "grid_sample HIP kernel, batch 512 per GPU, 3x32x100 fp32, "
                                    "20 fiducials, inputs resident in HBM",
@@ -875,15 +920,34 @@ def main():
     if world > 1:
         dist.destroy_process_group()
     if rank == 0:
-        # RCCL prints its version banner through C stdio, which a pipe buffers until exit: flush it first so that the
-        # JSON line is the last line of stdout
-        sys.stdout.flush()
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(json.dumps(rec), flush=True)
+        print_line(rec)
+
+
+def headline(world, steps, warmup, ev_ms, wall_s):
+    """The result line's leading fields: `ev_ms` is the timed region of `steps` launches (HIP events), `wall_s` the host
+    clock around it."""
+    return {"metric": "rectified images/sec (3x32x100)", "value": world * BATCH * steps / (ev_ms * 1e-3),
+            "unit": "images/s", "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": ev_ms / steps,
+            "wall_ms_per_step": wall_s * 1e3 / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic"}
+
+
+def print_line(rec):
+    # RCCL prints its version banner through C stdio, which a pipe buffers until exit: flush it first so that the
+    # JSON line is the last line of stdout
+    sys.stdout.flush()
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    print(json.dumps(rec), flush=True)
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the rectified batch (BATCH, C, H, W) of the last timed step, what a caller of the path receives."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "rectified.npy"), out.float().cpu().numpy())
 
 
 if __name__ == "__main__":

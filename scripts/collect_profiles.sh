@@ -12,17 +12,17 @@ STEPS=${STEPS:-400}
 # 1. kernel trace + stats of the bench command (steps round-robin on 3 streams: launches overlap), and of the same steps on
 #    ONE stream (the kernel's own start-to-end duration)
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- \
-    python3 bench.py --steps $STEPS --warmup 50 --no-cpu-baseline --no-extras > $OUT/bench_trace.log 2>&1
+    python3 bench.py --steps $STEPS --warmup 50 --full --no-cpu-baseline --no-extras > $OUT/bench_trace.log 2>&1
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -o bench -- \
-    python3 bench.py --steps $STEPS --warmup 50 --no-cpu-baseline --no-extras --streams 1 > $OUT/bench_trace1.log 2>&1
-# 1b. the driver's own command, untouched: `python bench.py --gpus 1 --steps 20 --warmup 5` (two streams at this step count,
+    python3 bench.py --steps $STEPS --warmup 50 --full --no-cpu-baseline --no-extras --streams 1 > $OUT/bench_trace1.log 2>&1
+# 1b. the headline command with --full: `python bench.py --gpus 1 --steps 20 --warmup 5 --full` (two streams at this step count,
 #     5 regions per protocol, extras and CPU baseline included); the summary lists period and duration of every region
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_driver -o bench -- \
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_trace_driver.log 2>&1
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_trace_driver.log 2>&1
 # 2. PMC passes (own runs, nothing but --pmc)
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 400 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_$c -o bench -- \
-      python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extras > $OUT/bench_pmc_$c.log 2>&1
+      python3 bench.py --steps 100 --warmup 10 --full --no-cpu-baseline --no-extras > $OUT/bench_pmc_$c.log 2>&1
   timeout 400 rocprofv3 --pmc $c --output-format csv -d $OUT/cal_$c -o copy -- \
       ./scripts/ubench/copy_bench > $OUT/copy_pmc_$c.log 2>&1
 done

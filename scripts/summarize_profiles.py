@@ -202,9 +202,10 @@ def timeline_summary():
     `repeats` regions on one stream (when S > 1), then the parity step / extras.  For every region: the kernels' average
     start-to-end duration and the period (last end - first start) / launches, next to the bench line's own
     regions_us of the same run."""
-    runs = (("the driver's command: `python3 bench.py --gpus 1 --steps 20 --warmup 5`", "trace_driver", "bench_trace_driver.log"),
-            ("`--steps 400 --warmup 50` (long regions)", "trace", "bench_trace.log"),
-            ("`--steps 400 --warmup 50 --streams 1`", "trace1", "bench_trace1.log"))
+    runs = (("the headline command with --full: `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`", "trace_driver",
+             "bench_trace_driver.log"),
+            ("`--steps 400 --warmup 50 --full` (long regions)", "trace", "bench_trace.log"),
+            ("`--steps 400 --warmup 50 --full --streams 1`", "trace1", "bench_trace1.log"))
     blocks = []
     for tag, sub, logname in runs:
         pth = os.path.join(SRC, sub, "bench_kernel_trace.csv")
@@ -287,12 +288,12 @@ def main():
         for streams, n, tot, avg, mn, mx, periods in agg:
             wr.writerow([f"{KERNEL} | timed regions on {streams} stream(s) | {ALG} B / average / 8 TB/s = {ALG / avg / 8000.0:.3f}",
                          n, tot, round(avg, 1), "", mn, mx, " ".join(f"{x:.0f}" for x in periods),
-                         "python3 bench.py --gpus 1 --steps 20 --warmup 5 (trace_driver; dispatches in " + f"{TAG}_bench_dispatches.csv); "
+                         "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full (trace_driver; dispatches in " + f"{TAG}_bench_dispatches.csv); "
                          "20-launch regions: the profiler's per-dispatch work stretches duration and period"])
         # the long regions (400 launches): the kernel's own duration with every launch behind the previous one is the
         # one-stream row of these -- the figure bench.py's roofline.one_stream_frac (un-profiled) is to be compared with
-        for sub, logname, cmd in (("trace", "bench_trace.log", "python3 bench.py --steps 400 --warmup 50"),
-                                  ("trace1", "bench_trace1.log", "python3 bench.py --steps 400 --warmup 50 --streams 1")):
+        for sub, logname, cmd in (("trace", "bench_trace.log", "python3 bench.py --steps 400 --warmup 50 --full"),
+                                  ("trace1", "bench_trace1.log", "python3 bench.py --steps 400 --warmup 50 --full --streams 1")):
             for streams, n, tot, avg, mn, mx, periods in protocol_rows(sub, logname):
                 wr.writerow([f"{KERNEL} | timed regions on {streams} stream(s) | {ALG} B / average / 8 TB/s = {ALG / avg / 8000.0:.3f}",
                              n, tot, round(avg, 1), "", mn, mx, " ".join(f"{x:.0f}" for x in periods), cmd + " (400-launch regions)"])
@@ -301,7 +302,7 @@ def main():
                 continue
             if len(row[0]) > 200:
                 row[0] = row[0][:200] + "..."
-            wr.writerow([row[0]] + [float(x) if "." in x else int(x) for x in row[1:7]] + ["", "python3 bench.py --steps 400 --warmup 50 (3 streams + 1 stream mixed: see the rows above for the split)"])
+            wr.writerow([row[0]] + [float(x) if "." in x else int(x) for x in row[1:7]] + ["", "python3 bench.py --steps 400 --warmup 50 --full (3 streams + 1 stream mixed: see the rows above for the split)"])
     stats = {r["Name"]: r for r in csv.DictReader(open(os.path.join(SRC, "trace", "bench_kernel_stats.csv")))}
     krow = next(v for k, v in stats.items() if KERNEL in k)
     bench_line = [l for l in open(os.path.join(SRC, "bench_trace.log")) if l.startswith("{")][-1]
