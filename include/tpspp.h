@@ -126,8 +126,7 @@ int tpspp_prepare_mirror_table(const float* p_hat, int p_hat_ld, int Ho, int Wo,
 #define TPSPP_BWD_FIXED_POINT 16   /* table_flags bit of tpspp_warp_bwd only: accumulate dL/d input in 64-bit fixed point (bitwise
                                     * reproducible from run to run) instead of the default fp64 LDS atomics; per call, any stream */
 #define TPSPP_BWD_TWO_KERNELS 64   /* table_flags bit of tpspp_warp_bwd only: never the one-launch form of the classic rectifier's call
-                                    * (A/B runs, tests); per call.  The environment variable of the same name, read once when
-                                    * the first backward runs, does the same for a whole process. */
+                                    * (A/B runs, tests); per call. */
 #define TPSPP_IO_BF16 4            /* table_flags bit: in0 / in1 / out0 / out1 hold bfloat16 (the pointers are
                                       reinterpreted; everything else stays fp32).  The bf16 configuration
                                       (BASELINE.json configs[2]): T, grid and interpolation in fp32 exactly as
@@ -199,7 +198,7 @@ void tpspp_warp_plan_destroy(tpspp_warp_plan_t* plan);
  * two agree within 5e-5 of the largest entry.  Which form runs depends on these arguments only: in1 == NULL, score == NULL,
  * p_xy == NULL (p_xy means the TPS_PP table layout, whose p_hat lacks the [1, x, y] columns the one-launch form reads from the
  * transposed classic table), p_hat_t given and 16-byte aligned, C0 <= 3, F <= 21, Ho*Wo in (1024, 4096] and a multiple of 4,
- * the fp64 accumulator, and the TPSPP_BWD_TWO_KERNELS flag bit / environment variable unset.
+ * the fp64 accumulator, and the TPSPP_BWD_TWO_KERNELS flag bit unset.
  * replaces: autograd through backbones/tps_pp/tps_pp.py:467-496,597-615;
  *           preprocessor/tps_preprocessor.py:71-83,270-282
  */

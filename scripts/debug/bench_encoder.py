@@ -1,6 +1,5 @@
 """NRTR encoder alone (batch 512 x 64 tokens x 512 channels), per arithmetic configuration: the token GEMM
-(tpspp_tokgemm.hip) carries the bf16 / bf16x3 projections.  `python scripts/debug/bench_encoder.py [N] [iters]`;
-TPSPP_HEAD_NO_TOKGEMM=1 routes them through the convolution kernel as before round 4."""
+(tpspp_tokgemm.hip) carries the bf16 / bf16x3 projections.  `python scripts/debug/bench_encoder.py [N] [iters]`"""
 import os
 import sys
 

@@ -391,7 +391,7 @@ def test_input_gradients_mixed_magnitudes(cuda, geometry):
 def test_classic_backward_single_launch_against_the_two_kernel_route(cuda, C, hw, n):
     """Round 5: the classic rectifier's backward (one input of <= 3 channels, no score, 1024 < pixels <= 4096, transposed
     table) is ONE launch (warp_bwd_classic_kernel: image staged in LDS, fp64 LDS accumulators, dL/dT finished in the
-    workgroup); TPSPP_BWD_TWO_KERNELS=1 selects the sampling + parameter kernels of rounds 3-5.  Same sampling arithmetic:
+    workgroup); the TPSPP_BWD_TWO_KERNELS flag bit selects the sampling + parameter kernels of rounds 3-5.  Same sampling arithmetic:
     dL/d input within one ulp (fp64 sums of the same fp32 terms -- neighbouring lanes add their shared tap in fp64 before
     the atomic, so only the order of the fp64 additions differs); dL/dC' within 5e-5 of the largest entry of the two-kernel
     route (which keeps fp32 partial sums of ~12 terms per lane: measured 1.8e-5 apart) and within 3e-5 of float64 on the
@@ -414,7 +414,7 @@ def test_classic_backward_single_launch_against_the_two_kernel_route(cuda, C, hw
     def run(two_kernels=False):
         return ops.warp_backward(go, img, grid, ctrl, gg.inv_delta_C, gg.P_hat, hw, P_hat_t=P_hat_t, two_kernels=two_kernels)
 
-    want = run(two_kernels=True)                 # (the per-call TPSPP_BWD_TWO_KERNELS bit; the environment variable is read once)
+    want = run(two_kernels=True)                 # (the per-call TPSPP_BWD_TWO_KERNELS bit)
     for rep in range(3):
         got = run()
         gi, wi = got[0], want[0]

@@ -325,40 +325,6 @@ def test_head_argument_errors(cuda):
             dec._w_cache = None                          # rebuild the table for whoever uses the module next
 
 
-def test_decoder_fused_q_cross_launch_is_bit_identical(cuda, tmp_path):
-    """TPSPP_HEAD_QCROSS=1 (q projection + cross-attention of a layer-step in one launch; opt-in, measured slower) must
-    give exactly the scores of the two-launch path: the switch is read when the library loads, so two processes."""
-    import subprocess
-    import sys
-    code = (
-        "import sys, torch\n"
-        "from tps_pp_amd.nrtr_head import NRTRDecoder\n"
-        "torch.manual_seed(3)\n"
-        "dec = NRTRDecoder(num_classes=93, max_seq_len=6, start_idx=91, padding_idx=92).eval().cuda()\n"
-        "enc = torch.randn(37, 64, 512, device='cuda'); feat = torch.empty(37, 512, 8, 8, device='cuda')\n"
-        "res = {}\n"
-        "for tag, cd in (('bf16x3', 'bf16x3'), ('bf16', torch.bfloat16)):\n"
-        "    dec.compute_dtype = cd\n"
-        "    with torch.no_grad():\n"
-        "        res[tag] = dec(feat, enc, None, None, train_mode=False).cpu()\n"
-        "torch.save(res, sys.argv[1])\n")
-    import os
-    outs = []
-    for val in (None, "1"):
-        env = dict(os.environ)
-        env["TPSPP_HEAD_NO_PERSIST"] = "1"               # both on the launch-per-phase pipeline (the fused launch is one of its phases)
-        env.pop("TPSPP_HEAD_QCROSS", None)
-        if val:
-            env["TPSPP_HEAD_QCROSS"] = val
-        path = str(tmp_path / f"dec_{val}.pt")
-        subprocess.run([sys.executable, "-c", code, path], env=env, check=True, timeout=300,
-                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-        outs.append(torch.load(path))
-    for k in outs[0]:
-        assert torch.equal(outs[0][k], outs[1][k]), k
-        assert torch.isfinite(outs[0][k]).all()
-
-
 @pytest.mark.parametrize("n,seq", [(37, 6), (64, 40), (557, 5)])
 def test_decoder_persistent_step_matches_the_launch_pipeline(cuda, n, seq):
     """Round 5: a decoding step is ONE persistent launch (tpspp_head_persist.h: clusters of 16
@@ -402,17 +368,14 @@ def test_decoder_persistent_step_matches_the_launch_pipeline(cuda, n, seq):
                         assert torch.equal(got, want) and torch.equal(got_tf, want_tf), (cd, rep, float((got - want).abs().max()))
                     assert float((got - want).abs().max()) <= (5e-5 if cd == "bf16x3" else 5e-4), (cd, rep, float((got - want).abs().max()))
                     assert float((got_tf - want_tf).abs().max()) <= (1e-3 if cd == torch.bfloat16 else 1e-4) * float(want_tf.abs().max()), (cd, rep)
-                # the step loop is INSIDE the launch (one launch per decode); one launch per step (TPSPP_HEAD_STEP_LAUNCHES=1) and
                 # write-through stores whatever the clusters' placement (TPSPP_HEAD_WRITE_THROUGH=1): the same bits
-                for var in ("TPSPP_HEAD_STEP_LAUNCHES", "TPSPP_HEAD_WRITE_THROUGH"):
-                    os.environ[var] = "1"
-                    one = dec(None, enc, None, metas, train_mode=False)
-                    one_tf = dec(None, enc, dict(padded_targets=forced), metas, train_mode=True)
-                    del os.environ[var]
-                    assert torch.equal(one, got) and torch.equal(one_tf, got_tf), (cd, var, float((one - got).abs().max()))
+                os.environ["TPSPP_HEAD_WRITE_THROUGH"] = "1"
+                one = dec(None, enc, None, metas, train_mode=False)
+                one_tf = dec(None, enc, dict(padded_targets=forced), metas, train_mode=True)
+                del os.environ["TPSPP_HEAD_WRITE_THROUGH"]
+                assert torch.equal(one, got) and torch.equal(one_tf, got_tf), (cd, float((one - got).abs().max()))
     finally:
         os.environ.pop("TPSPP_HEAD_NO_PERSIST", None)
-        os.environ.pop("TPSPP_HEAD_STEP_LAUNCHES", None)
         os.environ.pop("TPSPP_HEAD_WRITE_THROUGH", None)
         if old is not None:
             os.environ["TPSPP_HEAD_NO_PERSIST"] = old
@@ -420,11 +383,11 @@ def test_decoder_persistent_step_matches_the_launch_pipeline(cuda, n, seq):
 
 def test_decoder_persistent_kernel_other_depths_and_widths(cuda):
     """The persistent decoder kernel outside the reference's default shape: an ODD number of layers (the activations' x / y
-    buffers end a step swapped: the step loop inside the launch and the host's per-step launches must both follow) and
+    buffers end a step swapped: the step loop inside the launch must follow) and
     d_inner = 512 (four 16-wide k-steps per wavefront in the w2 projection instead of two), 96 and 40 encoder tokens (wider images:
     the cross-attention then walks a wavefront's two heads one after the other), every head configuration, greedy and
     teacher-forced, against the launch pipeline: exact-fp32 head bit-identical, reduced heads within 5e-5 / 5e-4 with identical
-    tokens; one launch per step and write-through stores bit-equal to the default."""
+    tokens; write-through stores bit-equal to the default."""
     import os
     from tps_pp_amd.nrtr_head import NRTRDecoder
     torch.manual_seed(11)
@@ -455,13 +418,12 @@ def test_decoder_persistent_kernel_other_depths_and_widths(cuda):
                         assert torch.equal(got, want) and torch.equal(got_tf, want_tf), tag
                     assert float((got - want).abs().max()) <= (5e-5 if cd != torch.bfloat16 else 5e-4), (tag, float((got - want).abs().max()))
                     assert float((got_tf - want_tf).abs().max()) <= (1e-3 if cd == torch.bfloat16 else 1e-4) * float(want_tf.abs().max()), tag
-                    for var in ("TPSPP_HEAD_STEP_LAUNCHES", "TPSPP_HEAD_WRITE_THROUGH"):
-                        os.environ[var] = "1"
-                        one = dec(None, enc, None, metas, train_mode=False)
-                        del os.environ[var]
-                        assert torch.equal(one, got), (tag, var)
+                    os.environ["TPSPP_HEAD_WRITE_THROUGH"] = "1"
+                    one = dec(None, enc, None, metas, train_mode=False)
+                    del os.environ["TPSPP_HEAD_WRITE_THROUGH"]
+                    assert torch.equal(one, got), tag
         finally:
-            for var in ("TPSPP_HEAD_NO_PERSIST", "TPSPP_HEAD_STEP_LAUNCHES", "TPSPP_HEAD_WRITE_THROUGH"):
+            for var in ("TPSPP_HEAD_NO_PERSIST", "TPSPP_HEAD_WRITE_THROUGH"):
                 os.environ.pop(var, None)
 
 

@@ -17,7 +17,6 @@
 //   * results leave as 16-byte units of the blocked output (v_permlane32_swap pairs the two half-wavefronts' halves).
 // Bound: HBM.
 #include "tpspp_conv_bf16_impl.h"
-#include <cstdlib>
 
 namespace {
 
@@ -32,7 +31,7 @@ __global__ void __launch_bounds__(NW * 64, 1)
 conv1x1_blk_kernel(const BParams P, int ntiles, int cg_total, int cg0)
 {
     // (round 6: a launch may own a SLICE of the output channels -- groups cg0 .. cg0 + 4 NT - 1 of cg_total -- so that layers whose
-    // whole weight does not fit the LDS (256 -> 512, 512 -> 512) run as 2 / 4 launches of this kernel, each streaming the
+    // whole weight does not fit the LDS (256 -> 512) run as 2 launches of this kernel, each streaming the
     // activations once; P.wt / P.bias then point at the slice; and a tile is 32 NW pixels of the flat (image, pixel) index, so
     // maps smaller than a tile (4x16) are taken as well)
     extern __shared__ u32x4 sAll[];
@@ -166,7 +165,7 @@ bool launch(const BParams& P0, hipStream_t st)
 namespace tpspp {
 
 // true when the kernel took the layer: 1x1, stride 1, one blocked bf16 source at its own resolution, blocked bf16 output,
-// bias / ReLU only, Cin and Cout in {64, 128, 256} (+ 256 -> 512, 512 -> 512 as output-channel slices), whole 32 NW-pixel tiles
+// bias / ReLU only, Cin and Cout in {64, 128, 256} (+ 256 -> 512 as output-channel slices), whole 32 NW-pixel tiles
 // of the flat (image, pixel) index
 bool conv1x1_blk_launch(const BParams& P, hipStream_t st)
 {
@@ -179,10 +178,8 @@ bool conv1x1_blk_launch(const BParams& P, hipStream_t st)
 #undef TPSPP_C1
     // the first layer of the last stage: the weight of an output-channel slice in LDS, one launch per slice (132 -> 82 us at batch
     // 512).  Not 512 -> 512 on the 4x16 maps: four slices of 131 KB for ONE 128-pixel tile per workgroup measured 74 us against the
-    // tiled kernel's 55 (TPSPP_C1X1_512=1 selects it for the bit-identity test).
+    // tiled kernel's 55.
     if (P.Cin == 256 && P.Cout == 512) return launch<8, 16, 2>(P, st);
-    static const bool c512 = getenv("TPSPP_C1X1_512") != nullptr;
-    if (c512 && P.Cin == 512 && P.Cout == 512) return launch<4, 32, 4>(P, st);
     return false;
 }
 

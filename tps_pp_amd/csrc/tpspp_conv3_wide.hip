@@ -29,7 +29,7 @@
 // Measured (batch 512, 30 launches back to back, scripts/debug/bench_wide.py; tiled kernel -> this one): 128 -> 128 @8x32 58.7 ->
 // 40.8 us, 256 -> 256 @8x32 196 -> 143 us (1.08 PFLOP/s), 512 -> 512 @4x16 192 -> 148 us; matrix pipe busy 54 - 55 % on the two
 // large shapes before the last two changes (SQ_VALU_MFMA_BUSY_CYCLES at the ~1.75 GHz the chip holds under this load; tiled:
-// 34 - 38 %).  Where the rest goes, by switching parts off (-DTPSPP_WIDE_LAB, results then wrong): no weight loads inside the
+// 34 - 38 %).  Where the rest goes, by switching parts off (timing builds, results then wrong): no weight loads inside the
 // loop 121 us, the same loads but always hitting L1 148 us (it is the vector-memory -> register path itself, not L2: 16 KB per
 // wavefront and chunk), no DMA 139 us, no epilogue 132 us, neither loads nor epilogue 102 us (1.5 PFLOP/s: what the loop
 // with its LDS reads and one barrier per chunk delivers); the weight loads 8 taps ahead instead of 5, or spread between the
@@ -37,7 +37,6 @@
 // was 12 % with the loads next to their use), a chunk's DMA instructions are issued one per tap.
 // Bound: the matrix pipe (0.5 LDS reads and 0.25 global 16-byte loads per instruction) -- at 43 - 55 % of it.
 #include "tpspp_conv_bf16_impl.h"
-#include <cstdlib>
 
 namespace {
 
@@ -78,10 +77,7 @@ struct WCfg {
 };
 
 // EPI bit 0: + blocked bf16 residual (res_mode 1 / 2); bit 1: fp32 NCHW output (the backbone's last block) instead of blocked bf16.
-// LAB (timing experiments only, TPSPP_WIDE_LAB in the environment; results are WRONG for LAB != 0): bit 0 no barrier per chunk,
-// bit 1 no weight loads inside the loop, bit 2 no DMA inside the loop, bit 3 no epilogue stores / residual loads, bit 4 the
-// weight loads re-read the same 8 KB (L1 hits); TPSPP_WIDE_LAB=108: the product kernel with the weight loads 8 taps ahead
-template <int TH, int TW, int NI, int EPI, int kGPD, int LAB = 0, int KS = 3>
+template <int TH, int TW, int NI, int EPI, int kGPD, int KS = 3>
 __global__ void __launch_bounds__(256, 2)
 conv3_wide_kernel(const BParams P)
 {
@@ -184,7 +180,7 @@ conv3_wide_kernel(const BParams P)
             const int c = c0 + cc;
             // buffer (c + 2) % 3 was read during chunk c - 1: every wavefront is past the barrier that ended it, so chunk c + 2 may
             // land there -- its DMA instructions are issued one per tap (taps 0 .. MAXJ - 1), not in a burst
-            const bool more = c + 2 < nchunks && !(LAB & 4);
+            const bool more = c + 2 < nchunks;
             const u32x4* const pb = sB + (c % kGNB) * BUFU;
             auto fetch_b = [&](int tap, int slot) {
                 const int ky = tap / 3, kx = tap - ky * 3;
@@ -202,10 +198,9 @@ conv3_wide_kernel(const BParams P)
                     for (int i = tap * DPS; i < (tap + 1) * DPS && i < MAXJ; ++i) dma_one(c + 2, i);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!(LAB & 2)) {   // the weight fragments of tap T + kGPD -> the slot tap T - 1 has just freed
+                {                             // the weight fragments of tap T + kGPD -> the slot tap T - 1 has just freed
                     const int Tn = T + kGPD;
-                    int Tc = Tn < taps_total ? Tn : taps_total - 1;            // (past the end: a harmless re-read)
-                    if constexpr (LAB & 16) Tc &= 3;                           // (lab: the same 8 KB again and again -- L1 hits)
+                    const int Tc = Tn < taps_total ? Tn : taps_total - 1;      // (past the end: a harmless re-read)
                     fa[(tl + kGPD) % kGRing][0] = wA[(size_t)Tc * 128];
                     fa[(tl + kGPD) % kGRing][1] = wA[(size_t)Tc * 128 + 32];
                 }
@@ -224,23 +219,11 @@ conv3_wide_kernel(const BParams P)
             // end of chunk c: this wavefront's reads of buffer c % 3 are complete (their data has been multiplied); its DMA of
             // chunk c + 1 -- older than the 2 kGPD weight loads and the MAXJ DMA instructions that may still be in flight -- is
             // complete; then the barrier makes both true for the workgroup
-            if constexpr (LAB & 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * kGPD + MAXJ) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * kGPD + MAXJ) : "memory");
         }
     }
 
     // ---- epilogue: bias, residual, ReLU; blocked bf16 units (the two half-wavefronts hold the halves of a 16-byte unit) -------
-    if constexpr (LAB & 8) {
-        float s_ = 0.0f;
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) s_ += acc[f][h2][i];
-        if (s_ == 123.456f) reinterpret_cast<float*>(P.out)[0] = s_;
-        return;
-    }
     const bool relu1 = P.relu == 1;
     const int CGo = P.Cout >> 3;
     float bq[2][4][4];
@@ -328,32 +311,13 @@ bool launch_w(const BParams& P, hipStream_t st)
     if (blocks > 0x7fffffffL) return false;
     const dim3 grid((unsigned)blocks);
     constexpr int PD = WK<KS>::PD;
-#ifdef TPSPP_WIDE_LAB
-    if constexpr (KS == 3) {
-    if (const char* lv = getenv("TPSPP_WIDE_LAB")) {
-        switch (atoi(lv)) {
-        case 1: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 1>), grid, dim3(256), 0, st, P); return true;
-        case 2: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 2>), grid, dim3(256), 0, st, P); return true;
-        case 4: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 4>), grid, dim3(256), 0, st, P); return true;
-        case 8: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 8>), grid, dim3(256), 0, st, P); return true;
-        case 7: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 7>), grid, dim3(256), 0, st, P); return true;
-        case 15: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 15>), grid, dim3(256), 0, st, P); return true;
-        case 16: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 16>), grid, dim3(256), 0, st, P); return true;
-        case 24: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 24>), grid, dim3(256), 0, st, P); return true;
-        case 10: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 5, 10>), grid, dim3(256), 0, st, P); return true;
-        case 108: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, 8, 0>), grid, dim3(256), 0, st, P); return true;   // weight loads 8 taps ahead
-        default: break;
-        }
-    }
-    }
-#endif
     if (P.out_f32 == 1) {
-        if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 3, PD, 0, KS>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 2, PD, 0, KS>), grid, dim3(256), 0, st, P);
+        if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 3, PD, KS>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 2, PD, KS>), grid, dim3(256), 0, st, P);
         return true;
     }
-    if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, PD, 0, KS>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 0, PD, 0, KS>), grid, dim3(256), 0, st, P);
+    if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, PD, KS>), grid, dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 0, PD, KS>), grid, dim3(256), 0, st, P);
     return true;
 }
 
@@ -382,8 +346,7 @@ bool conv3_wide_launch(const BParams& P, hipStream_t st)
 bool conv1x1_wide_launch(const BParams& P, hipStream_t st)
 {
     if (P.nsrc != 1 || P.src[0].f32 != 2 || P.src[0].lh || P.src[0].lw || (P.out_f32 != 2 && P.out_f32 != 1) || P.post_scale || P.relu > 1) return false;
-    static const bool all = getenv("TPSPP_C1X1_WIDE_ALL") != nullptr;        // (lab: every qualifying 1x1 layer, not only Cin >= 256)
-    if ((P.Cin % 64) || (P.Cout % 128) || P.src[0].C != P.Cin || (P.Cin < 256 && !all)) return false;
+    if ((P.Cin % 64) || (P.Cout % 128) || P.src[0].C != P.Cin || P.Cin < 256) return false;
     if (P.res_mode && P.res_f32 != 2) return false;
     if (P.Ho != P.Hi || P.Wo != P.Wi) return false;
     if (P.Ho == 8 && P.Wo == 32) return launch_w<8, 32, 1, 1>(P, st);

@@ -971,8 +971,7 @@ __device__ __forceinline__ unsigned dpack2(float lo, float hi)
 // (the projection's loads alone, 2000 dependent launches): launch order 5.03 us, 4 token blocks x half the tiles 4.77 us,
 // 8 x a quarter 5.30 us, all 16 x an eighth 5.56 us -- X, freshly written elsewhere, costs more per byte than W.
 // In the decoder (same box, interleaved): bf16 15.36 -> 15.19 ms, bf16x3 20.49 -> 20.42 ms, exact fp32 23.24 -> 23.30 (left
-// in launch order).  Only the 16-token-block grids of batch 512 with an even number of tile rows are remapped
-// (TPSPP_HEAD_PLAIN_ORDER=1: never).
+// in launch order).  Only the 16-token-block grids of batch 512 with an even number of tile rows are remapped.
 __device__ __forceinline__ void dec_gemm_tile(int& bx, int& by, bool remap)
 {
     bx = blockIdx.x; by = blockIdx.y;
@@ -1097,121 +1096,6 @@ dec_gemm_x3_kernel(const DGemm P)
     }
 }
 
-// ---- q projection + cross-attention of a layer-step in ONE launch (round 4; the review's item 3) ------------------------------
-// A workgroup owns 16 images x one head: (A) their 64 q features = LN(y) Wq + b exactly as dec_gemm_x3_kernel<8, true>
-// computes them -- the same loads, k split, products, reduction order and epilogue, for the head's two 32-output tiles, the
-// 16 tokens in the lower half of the MFMA's columns -- left in LDS; (B) each of the four wavefronts then runs cross_attend for
-// four of the sixteen (image, head) pairs.  Bit for bit the two launches it replaces.  Grid (Nb / 16, H) = 256 workgroups at
-// batch 512: the 128 KB of the head's weight slice is read once per 16 images as before (33 MB of L2 reads per launch).
-// MEASURED (batch 512, 40 steps, scripts/debug/dec_fusion_ab.py, interleaved runs on one box): the greedy decoder takes
-// 24.9 ms with it against 21.8 ms with the two launches (bf16x3 head), 18.05 against 16.65 ms (bf16 head): +13 / +6 us per
-// layer-step.  The separate attention launch runs 16 wavefronts per CU, one (image, head) each, and is bound by the keys' and
-// values' bytes; here four wavefronts per CU walk four pairs each, one after the other, behind the projection's own load ->
-// product -> reduce chain, and what the fusion removes -- one kernel boundary, ~1.5-2 us -- is less than what the lost
-// parallelism costs.  Hence opt-in only (TPSPP_HEAD_QCROSS=1), kept as the measured form of the review's proposal.
-template <typename KV>
-__global__ void __launch_bounds__(256)
-dec_q_cross_x3_kernel(const DGemm P, const KV* __restrict__ Kx_t, const KV* __restrict__ Vx_t, int H, int T,
-                      const int* __restrict__ valid_len, float* __restrict__ out)
-{
-    constexpr int KSW = 8;
-    __shared__ float sRed[4][2][16][kWave];
-    __shared__ float sS1[8][32], sS2[8][32];
-    __shared__ __attribute__((aligned(16))) float sQ[16][kDK];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1);
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31, l15 = lane & 15;
-    const int m0 = blockIdx.x * 16, h = blockIdx.y;
-    const int KS = P.K >> 4;
-    const int m = m0 + l15;
-    const int mc = m < P.M ? m : P.M - 1;
-    const float4* xp = reinterpret_cast<const float4*>(P.X + (size_t)mc * P.K + 16 * (wv * KSW) + 8 * half);
-    float4 xa[KSW][2];
-    du32x4 ah[2][KSW], al[2][KSW];
-#pragma unroll
-    for (int j = 0; j < KSW; ++j) { xa[j][0] = xp[4 * j]; xa[j][1] = xp[4 * j + 1]; }
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl) {
-        const du32x4* wp = P.Wp + ((size_t)((2 * h + tl) * KS + wv * KSW) * 4 + half) * 32 + l31;
-#pragma unroll
-        for (int j = 0; j < KSW; ++j) { ah[tl][j] = wp[(size_t)j * 128]; al[tl][j] = wp[(size_t)j * 128 + 64]; }
-    }
-    const int c = 8 * wv + 4 * half;                       // + 32 tl: this lane's four q features of the head (epilogue)
-    float4 cs[2], b4[2];
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl) {
-        cs[tl] = *reinterpret_cast<const float4*>(P.colsum + kDK * h + 32 * tl + c);
-        b4[tl] = P.bias ? *reinterpret_cast<const float4*>(P.bias + kDK * h + 32 * tl + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    f32x16_t acc[2];
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[tl][i] = 0.0f;
-    float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < KSW; ++j) {
-        const float x[8] = {xa[j][0].x, xa[j][0].y, xa[j][0].z, xa[j][0].w, xa[j][1].x, xa[j][1].y, xa[j][1].z, xa[j][1].w};
-        du32x4 bh, bl;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const unsigned pk = dpack2(x[2 * q], x[2 * q + 1]);
-            const float h0 = __builtin_bit_cast(float, pk << 16), h1 = __builtin_bit_cast(float, pk & 0xffff0000u);
-            bh[q] = pk;
-            bl[q] = dpack2(x[2 * q] - h0, x[2 * q + 1] - h1);
-            s1 += x[2 * q] + x[2 * q + 1];
-            s2 = fmaf(x[2 * q], x[2 * q], s2);
-            s2 = fmaf(x[2 * q + 1], x[2 * q + 1], s2);
-        }
-        const dbf16x8 Bh = __builtin_bit_cast(dbf16x8, bh), Bl = __builtin_bit_cast(dbf16x8, bl);
-#pragma unroll
-        for (int tl = 0; tl < 2; ++tl) {
-            const dbf16x8 Ah = __builtin_bit_cast(dbf16x8, ah[tl][j]), Al = __builtin_bit_cast(dbf16x8, al[tl][j]);
-            acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[tl], 0, 0, 0);
-            acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[tl], 0, 0, 0);
-            acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[tl], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int tl = 0; tl < 2; ++tl)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sRed[wv][tl][r][lane] = acc[tl][r];
-    sS1[wv * 2 + half][l31] = s1; sS2[wv * 2 + half][l31] = s2;
-    __syncthreads();
-    if (l31 < 16) {
-        float t1 = 0.0f, t2 = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { t1 += sS1[j][l31]; t2 += sS2[j][l31]; }
-        const float mean = t1 / (float)P.K;
-        const float rstd = 1.0f / sqrtf(fmaxf(t2 / (float)P.K - mean * mean, 0.0f) + P.eps);
-#pragma unroll
-        for (int tl = 0; tl < 2; ++tl) {
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                v[e] = (sRed[0][tl][4 * wv + e][lane] + sRed[1][tl][4 * wv + e][lane]) +
-                       (sRed[2][tl][4 * wv + e][lane] + sRed[3][tl][4 * wv + e][lane]);
-            v[0] = rstd * (v[0] - mean * cs[tl].x); v[1] = rstd * (v[1] - mean * cs[tl].y);
-            v[2] = rstd * (v[2] - mean * cs[tl].z); v[3] = rstd * (v[3] - mean * cs[tl].w);
-            if (P.bias) { v[0] += b4[tl].x; v[1] += b4[tl].y; v[2] += b4[tl].z; v[3] += b4[tl].w; }
-            *reinterpret_cast<float4*>(&sQ[l31][32 * tl + c]) = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    }
-    __syncthreads();
-    constexpr int EPL = Wide<KV>::EPL, GS = kDK / EPL;
-    const int dl = lane % GS;
-    for (int t = wv; t < 16; t += 4) {
-        const int b = m0 + t;
-        if (b >= P.M) break;                               // wave-uniform
-        float q[EPL];
-#pragma unroll
-        for (int e = 0; e < EPL; ++e) q[e] = sQ[t][EPL * dl + e] * 0.125f;
-        int nvalid = valid_len ? valid_len[b] : T;
-        nvalid = nvalid < T ? nvalid : T;
-        cross_attend<KV>(q, Kx_t, Vx_t, P.Co, P.M, T, nvalid, b, h, lane, out, 0);
-    }
-}
-
 #include "tpspp_head_persist.h"
 
 // The same GEMM with exact fp32 products (v_mfma_f32_32x32x2_f32) for the exact-fp32 configuration: the weight arrives
@@ -1323,10 +1207,6 @@ dec_gemm_f32_kernel(const DGemmF P)
     }
 }
 
-// (TPSPP_HEAD_NARROW_QKV=1: one 32-output tile per workgroup for the q|k|v projection as well, as before round 4)
-const bool g_head_narrow_qkv = getenv("TPSPP_HEAD_NARROW_QKV") != nullptr;
-const bool g_head_plain_order = getenv("TPSPP_HEAD_PLAIN_ORDER") != nullptr;
-
 // launches the step GEMM; false when the shape has no instantiation (K must be 256 or 512, Co a multiple of 4)
 bool dec_gemm_x3(hipStream_t st, const float* X, const void* Wp, const float* bias, const float* colsum, float eps,
                  const float* res, int act, int M, int K, int Co, float* out, bool f32 = false)
@@ -1334,14 +1214,14 @@ bool dec_gemm_x3(hipStream_t st, const float* X, const void* Wp, const float* bi
     if ((K != 256 && K != 512) || (Co & 3) || M <= 0) return false;
     const dim3 grid((unsigned)((M + 31) / 32), (unsigned)((Co + 31) / 32));
     // the q|k|v projection (1536 outputs, folded LayerNorm) of the three-term form: three tiles per workgroup, one round of
-    // 256 workgroups instead of 768 in two (bf16x3 decoder 20.85 -> 20.45 ms, bf16 15.68 -> 15.33, bit-identical scores,
-    // scripts/debug/dec_fusion_ab.py TPSPP_HEAD_NARROW_QKV).  Not the exact-fp32 form: its 96 fp32 matrix instructions per
-    // wavefront are the launch's time either way (23.40 -> 23.72 ms with three tiles).
-    if (!f32 && K == 512 && colsum && Co >= 1024 && !g_head_narrow_qkv) {
+    // 256 workgroups instead of 768 in two (bf16x3 decoder 20.85 -> 20.45 ms, bf16 15.68 -> 15.33 against one tile per
+    // workgroup, bit-identical scores).  Not the exact-fp32 form: its 96 fp32 matrix instructions per wavefront are the
+    // launch's time either way (23.40 -> 23.72 ms with three tiles).
+    if (!f32 && K == 512 && colsum && Co >= 1024) {
         const dim3 grid3((unsigned)((M + 31) / 32), (unsigned)(((Co + 31) / 32 + 2) / 3));
         DGemm P;
         P.X = X; P.Wp = reinterpret_cast<const du32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
-        P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = g_head_plain_order ? 0 : 1;
+        P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = 1;
         hipLaunchKernelGGL((dec_gemm_x3_kernel<8, true, 3>), grid3, dim3(256), 0, st, P);
         return true;
     }
@@ -1360,7 +1240,7 @@ bool dec_gemm_x3(hipStream_t st, const float* X, const void* Wp, const float* bi
     }
     DGemm P;
     P.X = X; P.Wp = reinterpret_cast<const du32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
-    P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = g_head_plain_order ? 0 : 1;
+    P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = 1;
     if (K == 512) {
         if (colsum) hipLaunchKernelGGL((dec_gemm_x3_kernel<8, true>), grid, dim3(256), 0, st, P);
         else        hipLaunchKernelGGL((dec_gemm_x3_kernel<8, false>), grid, dim3(256), 0, st, P);
@@ -1390,15 +1270,8 @@ transpose2d_b16_kernel(const unsigned short* __restrict__ in, int rows, int cols
     }
 }
 
-// lab switch (TPSPP_HEAD_NO_TOKGEMM=1 in the environment): the wide projections through the convolution kernel as before
-const bool g_head_no_tokgemm = getenv("TPSPP_HEAD_NO_TOKGEMM") != nullptr;
-// TPSPP_HEAD_QCROSS=1: the q projection and the cross-attention of a decoder layer-step as ONE launch (dec_q_cross_x3_kernel).
-// Off by default: bit-identical and slower (see the kernel's header).
-const bool g_head_qcross = getenv("TPSPP_HEAD_QCROSS") != nullptr;
 // TPSPP_HEAD_NO_PERSIST=1: the reduced-precision step pipeline as ~50 launches per step (rounds 3-4) instead of ONE persistent
-// launch per step (tpspp_head_persist.h); bit-identical scores -- for A/B runs and the bit-identity test
-// TPSPP_HEAD_CROSS1=1: the cross-attention with one head per wavefront as before round 5 (A/B runs)
-const bool g_head_cross1 = getenv("TPSPP_HEAD_CROSS1") != nullptr;
+// launch per decode (tpspp_head_persist.h); bit-identical scores -- for A/B runs and the bit-identity test
 bool head_no_persist() { return getenv("TPSPP_HEAD_NO_PERSIST") != nullptr; }
 long long* g_head_trace = nullptr;     // tpspp_head_set_trace
 
@@ -1416,7 +1289,7 @@ struct Gemm {
         tpspp::TokGemmArgs ta;
         ta.X = X; ta.W = W16; ta.bias = bias; ta.res = res; ta.out = out; ta.out_f32 = out_f32;
         ta.K = K; ta.Co = Co; ta.M = M; ta.act = act; ta.x3 = split3; ta.kgc = tpspp_conv_bf16_chunk_channels(1) / 8;
-        if (!g_head_no_tokgemm && tpspp::tok_gemm_applicable(ta)) {
+        if (tpspp::tok_gemm_applicable(ta)) {
             tpspp::launch_tok_gemm(ta, st);
             rc = tpspp::check_launch("token GEMM");
             return;
@@ -1808,7 +1681,7 @@ TPSPP_EXPORT int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T
     const unsigned pair_blocks = (unsigned)((N * H + 3) / 4);
     int rc = 0;
     // ---- the step as ONE persistent launch (tpspp_head_persist.h): every head configuration, d_model 512, 8 heads ----
-    bool persist = fast && C == 512 && H == 8 && num_out <= 128 && n_layers <= kPMaxLayers && !g_head_qcross && !head_no_persist();
+    bool persist = fast && C == 512 && H == 8 && num_out <= 128 && n_layers <= kPMaxLayers && !head_no_persist();
     const bool tbig = T > kWave;                              // more than 64 encoder tokens: the kernel's other instantiation
     auto kern = tbig ? (b16 ? (d_inner == 256 ? dec_step_persist_kernel<unsigned short, 2, false, true> : dec_step_persist_kernel<unsigned short, 4, false, true>)
                             : gemm_f32 ? (d_inner == 256 ? dec_step_persist_kernel<float, 2, true, true> : dec_step_persist_kernel<float, 4, true, true>)
@@ -1855,8 +1728,8 @@ TPSPP_EXPORT int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T
         // barrier timeout: wall-clock milliseconds (default 4000) -> units of 1024 ticks of the 100 MHz clock
         { const char* tv = getenv("TPSPP_HEAD_TIMEOUT_MS"); const long ms = tv ? atol(tv) : 4000; PS.timeout_k = (int)((ms < 1 ? 1 : ms > 60000 ? 60000 : ms) * 100000 / 1024); }
         { const char* tv = getenv("TPSPP_HEAD_TEST_STALL"); PS.test_stall_step = tv ? atoi(tv) : -1; }
-        // odd clusters start 15 us late (TPSPP_HEAD_STAGGER_US overrides; 0 = together): bf16x3 20.0 -> 19.4 ms, bf16 15.4 -> 15.0
-        { const char* sv = getenv("TPSPP_HEAD_STAGGER_US"); PS.stagger = (sv ? atoi(sv) : (N > 32 ? 15 : 0)) * 100; }
+        // odd clusters start 15 us late (against all together: bf16x3 20.0 -> 19.4 ms, bf16 15.4 -> 15.0)
+        PS.stagger = (N > 32 ? 15 : 0) * 100;
         // requirement (2): behind the previous persistent decode of this device, whatever stream it ran on
         std::lock_guard<std::mutex> lk(g_persist_mu);
         PersistDevice& PD = g_persist_dev[dev];
@@ -1868,28 +1741,18 @@ TPSPP_EXPORT int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T
             return tpspp::check_launch("tpspp_nrtr_decoder_fwd(memset)");
         hipLaunchKernelGGL(dec_embed_kernel, dim3((unsigned)((C * N + 255) / 256)), dim3(256), 0, st, emb, pos_table, tokens, Lt, 0, C,
                            N, x, 1);
-        const int per_step = 8 * n_layers + 2;                 // cluster barriers of one step
         // ONE launch per decode: the kernel loops over the steps, clusters run their 40 steps independently of each other.
         // (With the clusters spread over the XCDs -- the first version of this kernel -- one launch per step was faster:
         // 23.04 against 23.25 ms; with a cluster per XCD and ordinary stores the step loop inside wins: fp32 22.12 -> 21.58 ms,
-        // bf16x3 19.67 -> 19.07, bf16 14.29 -> 13.83 at batch 512.)  TPSPP_HEAD_STEP_LAUNCHES=1: one launch per step -- same
-        // scores (tests/test_gpu_head.py), for A/B runs.
-        const int per_launch = getenv("TPSPP_HEAD_STEP_LAUNCHES") ? 1 : L;
+        // bf16x3 19.67 -> 19.07, bf16 14.29 -> 13.83 at batch 512.)
         const int img_per_launch = 256 * groups;               // every cluster of a launch resident: `groups` x 8 clusters x 32 images
-        for (int s = 0; s < L; s += per_launch) {
-            // (+ one placement-check barrier per launch)
-            PS.x = x; PS.y = y; PS.step = s; PS.nsteps = per_launch; PS.bar_base = s * per_step + s / per_launch;
-            for (int n0 = 0; n0 < N; n0 += img_per_launch) {
-                const int nimg = N - n0 < img_per_launch ? N - n0 : img_per_launch;
-                PS.n0 = n0; PS.counters = pcounters + (n0 >> 5) * 32;
-                PS.nclusters = (nimg + 31) / 32;
-                // cluster c = 8 j + x is the 16 blocks 8 (16 j + ct) + x: one XCD per cluster (see the kernel)
-                hipLaunchKernelGGL(kern, dim3((unsigned)((PS.nclusters + 7) / 8 * 128)), dim3(512), sizeof(PShared), st, PS);
-            }
-            if (per_launch == 1) {
-                if (n_layers & 1) { float* t = x; x = y; y = t; }  // (the kernel swaps x / y once per layer)
-                if (s + 1 < L) { float* t = x; x = y; y = t; }     // the next step's embedding went to y
-            }
+        PS.x = x; PS.y = y; PS.step = 0; PS.nsteps = L; PS.bar_base = 0;
+        for (int n0 = 0; n0 < N; n0 += img_per_launch) {
+            const int nimg = N - n0 < img_per_launch ? N - n0 : img_per_launch;
+            PS.n0 = n0; PS.counters = pcounters + (n0 >> 5) * 32;
+            PS.nclusters = (nimg + 31) / 32;
+            // cluster c = 8 j + x is the 16 blocks 8 (16 j + ct) + x: one XCD per cluster (see the kernel)
+            hipLaunchKernelGGL(kern, dim3((unsigned)((PS.nclusters + 7) / 8 * 128)), dim3(512), sizeof(PShared), st, PS);
         }
         const hipError_t rec = hipEventRecord(PD.done, st);
         PD.recorded = PD.recorded || rec == hipSuccess;
@@ -1914,21 +1777,10 @@ TPSPP_EXPORT int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T
                 hipLaunchKernelGGL(attn_dec_self_wide_kernel<float>, dim3(pair_blocks), dim3(256), 0, st, qkv, C, N, H, s, L, Kc[l],
                                    Vc[l], tokens, Lt, padding_idx, a, 0);
             dec_gemm_x3(st, a, w[D_WFC_X], w[D_BFC], nullptr, 0.0f, x, 0, N, C, C, y, gemm_f32);              // y = x + fc(a)
-            if (!gemm_f32 && C == 512 && g_head_qcross) {
-                // q projection + cross-attention in one launch (dec_q_cross_x3_kernel)
-                DGemm Q;
-                Q.X = y; Q.Wp = reinterpret_cast<const du32x4*>(w[D_Q_X]); Q.bias = w[D_Q_B]; Q.colsum = w[D_Q_CS]; Q.res = nullptr;
-                Q.out = nullptr; Q.M = N; Q.K = C; Q.Co = C; Q.eps = 1e-5f; Q.act = 0;
-                const dim3 qgrid((unsigned)((N + 15) / 16), (unsigned)H);
-                if (b16)
-                    hipLaunchKernelGGL(dec_q_cross_x3_kernel<unsigned short>, qgrid, dim3(256), 0, st, Q,
-                                       reinterpret_cast<const unsigned short*>(Kx[l]),
-                                       reinterpret_cast<const unsigned short*>(Vx[l]), H, T, valid_len, a);
-                else
-                    hipLaunchKernelGGL(dec_q_cross_x3_kernel<float>, qgrid, dim3(256), 0, st, Q, Kx[l], Vx[l], H, T, valid_len, a);
-            } else {
+            // (q projection and cross-attention as two launches: fused into one they measured slower, bf16x3 decoder 24.9
+            // against 21.8 ms, bf16 18.05 against 16.65 ms at batch 512 -- DESIGN.md)
             dec_gemm_x3(st, y, w[D_Q_X], w[D_Q_B], w[D_Q_CS], 1e-5f, nullptr, 0, N, C, C, qkv, gemm_f32);
-            if (T <= kWave && (H & 1) == 0 && !g_head_cross1) {
+            if (T <= kWave && (H & 1) == 0) {
                 // two heads per wavefront (round 5): both heads' keys, then both heads' values in flight together
                 const unsigned blocks2 = (unsigned)((N * (H / 2) + 3) / 4);
                 if (b16)
@@ -1945,7 +1797,6 @@ TPSPP_EXPORT int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T
             else
                 hipLaunchKernelGGL(attn_dec_cross_wide_kernel<float>, dim3(pair_blocks), dim3(256), 0, st, qkv, Kx[l], Vx[l], C,
                                    N, H, T, valid_len, a, 0);
-            }
             dec_gemm_x3(st, a, w[D_WFC2_X], w[D_BFC2], nullptr, 0.0f, y, 0, N, C, C, x, gemm_f32);            // x = y + fc(a)
             dec_gemm_x3(st, x, w[D_W1_X], w[D_W1_B], w[D_W1_CS], 1e-5f, nullptr, 2, N, C, d_inner, hid, gemm_f32);
             dec_gemm_x3(st, hid, w[D_W2_X], w[D_B2], nullptr, 0.0f, x, 0, N, d_inner, C, y, gemm_f32);        // y = x + w2(...)

@@ -525,8 +525,8 @@ dec_step_persist_kernel(const PStep P)
         }
     };
     if (tid == 0) S.timeout_k = P.timeout_k;
-    // (one launch per step, TPSPP_HEAD_STEP_LAUNCHES: a decode that has failed in an earlier launch does not wait out a timeout
-    // in each of the remaining ones)
+    // (a launch that starts past step 0 -- the host starts every decode at step 0 -- does not continue a decode that has
+    // already failed)
     if (P.step > 0 && __hip_atomic_load(P.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) { fail_from(P.step); return; }
     // ---- placement check (one extra cluster barrier per launch): every workgroup ORs the id of the XCD it runs on into the
     // cluster's mask; one bit set = the whole cluster shares an L2 and its exchanged data goes out as ORDINARY stores (the
@@ -536,8 +536,7 @@ dec_step_persist_kernel(const PStep P)
     {
         if (tid == 0) {
             const unsigned id = (unsigned)__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;       // HW_REG_XCC_ID[3:0]
-            // (word 1 of the cluster's counters is zeroed once per decode, not per launch: with one launch per step a
-            // misplacement seen once keeps the cluster on write-through stores for the rest of the decode -- conservative)
+            // (word 1 of the cluster's counters is zeroed once per decode, not per launch)
             __hip_atomic_fetch_or(cnt + 1, 1 << id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
@@ -630,15 +629,15 @@ dec_step_persist_kernel(const PStep P)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(v0), "+v"(v1)::"memory");
             float* o = P.out + ((size_t)b * P.Lsteps + step) * Cc;
             const bool more = step + 1 < P.Lsteps;
-            // the next step's embedding goes to y (which becomes the next launch's x: the host swaps as the launch path does)
+            // the next step's embedding goes to y (which becomes the next step's x, as in the launch pipeline)
             auto embed_next = [&](int tok) {
                 if (more) {
                     const float* er = P.emb + (size_t)tok * C;
                     const float* pr = P.pos + (size_t)(step + 1) * C;
                     // (st16_x: an ordinary store when `plain` -- safe because the row's only reader is this cluster's next step,
-                    // i.e. the SAME XCD inside the SAME launch (its L2 holds the line); without the placement guarantee, or with
-                    // one launch per step on a cluster that was ever seen spread over XCDs, write-through: a plain store would
-                    // leave the line in this XCD's L2 and a reader on another XCD could be served a stale copy)
+                    // i.e. the SAME XCD inside the SAME launch (its L2 holds the line); without the placement guarantee
+                    // write-through: a plain store would leave the line in this XCD's L2 and a reader on another XCD could be
+                    // served a stale copy)
                     for (int c = 4 * lane; c < C; c += 4 * kWave) {
                         const float4 e4 = *reinterpret_cast<const float4*>(er + c), p4 = *reinterpret_cast<const float4*>(pr + c);
                         st16_x(y + (size_t)b * C + c, hf32x4{e4.x + p4.x, e4.y + p4.y, e4.z + p4.z, e4.w + p4.w}, plain);

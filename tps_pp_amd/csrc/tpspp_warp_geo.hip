@@ -96,14 +96,12 @@ bool plan_span(int C, int H, int W, int F, SpanPlan* p)
             }
             if (bestB) {
                 // windows requested at launch (SPEC) for the SAME decomposition: both regions' windows (band rows + 2 x margin)
-                // at once; margin 2 rows (TPSPP_SPAN_MARGIN overrides: 1 -> more wavefronts on the global-memory path at
-                // +-1.6 rows of displacement, 3 -> three workgroups per CU; both slower) -- only where four workgroups still
+                // at once; margin 2 rows (1: more wavefronts on the global-memory path at +-1.6 rows of displacement, 3: three
+                // workgroups per CU; both measured slower) -- only where four workgroups still
                 // share a CU (<= 40 KB: 64x200 45.4 against 48.8 us, 48x160 26.4 against 29.9; 64x256 would need 50 KB and
                 // measures 56.8 against 52.5 -- or fewer, smaller workgroups: worse --: it keeps the measured spans)
                 if (!g_span_no_spec) {
-                    const char* mv = getenv("TPSPP_SPAN_MARGIN");
-                    int mg = mv ? atoi(mv) : 2;
-                    if (mg < 0) mg = 0;
+                    const int mg = 2;
                     const int rows = (p->RG / p->bands) * BH;
                     int win = rows + 2 * mg;
                     if (win > H) win = H;
@@ -136,8 +134,6 @@ void launch_span_one(const tpspp_span::SpanParams& P, const SpanPlan& pl, hipStr
     hipLaunchKernelGGL(kern, dim3(blocks), dim3((unsigned)(pl.NWv * kWave)), pl.lds, st, P);
 }
 
-int g_span_no_fixed = 0;     // lab knob (TPSPP_SPAN_RUNTIME=1): the run-time-geometry form for the instantiated geometries as well
-
 // the instantiated geometries (C = 3, no auxiliary outputs): taken when the plan is exactly the one they were compiled for
 template <typename G, bool SPEC>
 bool span_fixed_matches(const tpspp_span::SpanParams& P, const SpanPlan& pl)
@@ -150,8 +146,7 @@ template <int C>
 void launch_span_aux(const tpspp_span::SpanParams& P, const SpanPlan& pl, hipStream_t st)
 {
     if constexpr (C == 3) {
-        static const bool rt = getenv("TPSPP_SPAN_RUNTIME") != nullptr;
-        if (!rt && !g_span_no_fixed && !P.grid && !P.idx && !P.force_gather) {
+        if (!P.grid && !P.idx && !P.force_gather) {
             using G64x200 = tpspp_span::SpanFix<64, 200, 8, 13, 8, 8, 2>;
             using G48x160 = tpspp_span::SpanFix<48, 160, 16, 5, 12, 4, 2>;
             using G64x256 = tpspp_span::SpanFix<64, 256, 32, 4, 32, 8, 0>;

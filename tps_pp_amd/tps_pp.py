@@ -22,13 +22,9 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-import os
-
 from .precision import default_compute_dtype
 from . import constants, ops
 from .registry import BACKBONES, PREPROCESSOR
-
-_NO_DOWN_FUSED = os.environ.get("TPSPP_NO_DOWN_FUSED") == "1"      # lab switch, see _regress_hip_bf16
 
 
 class ConvModule(nn.Module):
@@ -514,8 +510,8 @@ class TPS_PP(nn.Module):
                 if fc is None or fc[0] != fkey:
                     self._front16_cache = fc = (fkey, ops.FrontWeightsBf16(self, x3))
                 # round 4: feat0 / feat1 are not stored where the stride-2 layers can recompute them from outs[0] / outs[1]
-                # (tpspp_down_fused.hip; TPSPP_NO_DOWN_FUSED=1 keeps the two-kernel route for A/B runs)
-                fused = (not _NO_DOWN_FUSED and ops.down_fused_bf16_applicable(o0, cw["down0_1"])
+                # (tpspp_down_fused.hip)
+                fused = (ops.down_fused_bf16_applicable(o0, cw["down0_1"])
                          and ops.down_fused_bf16_applicable(o1, cw["down1_1"]))
                 feat0, feat1, feat2, feat_grid = ops.front_bf16(o0, o1, x, fc[1], fg_dtype, blocked=True, store01=not fused)
                 if fused:
@@ -636,7 +632,7 @@ class TPS_PP(nn.Module):
             if fc is None or fc[0] != fkey:
                 self._front_cache = fc = (fkey, ops.FrontWeights(self))
             fw = fc[1]
-            fused = (not _NO_DOWN_FUSED and ops.down_fused_f32_applicable(o0, cw["down0_1"])
+            fused = (ops.down_fused_f32_applicable(o0, cw["down0_1"])
                      and ops.down_fused_f32_applicable(o1, cw["down1_1"]))
             feat0, feat1, feat2, feat_grid = ops.front(o0, o1, x, fw, store01=not fused)
             if fused:           # round 4: feat0 / feat1 never reach HBM (tpspp_down_fused.hip, exact-fp32 form)
