@@ -31,10 +31,11 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 5   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 6   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
-                               5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy */
+                               5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
+                               6: tpspp_conv2d_bwd_data / _bwd_weight / _bwd_weight_workspace_floats, tpspp_conv2d_prep_weight */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -251,6 +252,52 @@ int tpspp_conv2d_fwd(const float* const* src_ptrs, const int* src_dims, int nsrc
                      const float* residual, const float* post_scale, const float* post_shift,
                      int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
                      float* out, int Ho, int Wo, tpspp_stream_t stream);
+
+/*
+ * Backward of tpspp_conv2d_fwd with res_mode = 0 and no post-affine, i.e. of
+ *     y = act(conv2d(cat_c(up(src_0), up(src_1), up(src_2)), W) + bias),   act: relu = 0 none, 1 ReLU,
+ * on the fp32 matrix cores (exact fp32 products, fp32 accumulation).  Sizes and source descriptions as
+ * tpspp_conv2d_fwd takes them (src_dims + 5*i = {C_i, H_i, W_i, uh_i, uw_i}, 1x1 or 3x3 "same" padding), with the
+ * stride restricted to sh, sw in {1, 2}.  The gradient reaching the convolution is dz = dy * [y > 0] for ReLU
+ * (PyTorch's threshold_backward on the in-place ReLU's output: no gradient where y == 0), dz = dy otherwise; it is
+ * formed as dy is read and never stored.  `y` is the forward's output (read only with relu = 1, may be NULL otherwise).
+ *
+ * Data gradient: dsrc_ptrs[i] (N, C_i, H_i, W_i) receives source i's gradient, NULL skips that source (at least one
+ * must be given).  An upsampled source's gradient is the sum over its uh x uw footprint; source pixels no output reads
+ * (1x1 kernel at stride 2) get exact zeros.  Every element of a requested gradient is written.
+ *   weight (Cout, Cin_total, KH, KW): PyTorch's layout, read as it is.
+ */
+int tpspp_conv2d_bwd_data(float* const* dsrc_ptrs, const int* src_dims, int nsrc, const float* weight,
+                          const float* dy, const float* y, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
+                          int Ho, int Wo, tpspp_stream_t stream);
+
+/*
+ * Floats of workspace tpspp_conv2d_bwd_weight needs for these sizes (0 for N == 0 or invalid sizes).
+ */
+size_t tpspp_conv2d_bwd_weight_workspace_floats(const int* src_dims, int nsrc, int N, int Cout, int KH, int KW,
+                                                int Ho, int Wo);
+
+/*
+ * Weight and bias gradient: dweight (Cout, Cin_total, KH, KW) in PyTorch's layout and dbias (Cout); either may be
+ * NULL (not both); with dweight NULL only the bias reduction runs (no GEMM), in the same order and to the same bits.  The sources are read as the forward read them (concatenated, upsampled on the fly).
+ * The reduction over N*Ho*Wo is a FIXED split-K: the terms are cut into slices whose number depends on the sizes only,
+ * each slice writes its partial sums to `ws` (ws_floats >= tpspp_conv2d_bwd_weight_workspace_floats(...), checked) and
+ * a second launch adds the slices in a fixed order.  No atomics: the result is bitwise reproducible from run to run and
+ * from stream to stream (a property the library backward-weights solvers do not promise).
+ * replaces: the autograd of nn.Conv2d (mmcv ConvModule, + nn.Upsample, torch.cat) at
+ *           backbones/tps_pp/tps_pp.py:126-131,149-169,537-562
+ */
+int tpspp_conv2d_bwd_weight(const float* const* src_ptrs, const int* src_dims, int nsrc, const float* dy,
+                            const float* y, int relu, int N, int Cout, int KH, int KW, int sh, int sw, int Ho, int Wo,
+                            float* dweight, float* dbias, float* ws, size_t ws_floats, tpspp_stream_t stream);
+
+/*
+ * The forward's weight layouts built on the device from PyTorch's (Cout, Cin, KH, KW) weight (a training step changes
+ * the weights every step): weight_t (Cin*KH*KW, Cout) and/or weight_tiled as tpspp_conv2d_fwd takes them (either may
+ * be NULL, not both).
+ */
+int tpspp_conv2d_prep_weight(const float* weight, int Cout, int Cin, int KH, int KW, float* weight_t,
+                             float* weight_tiled, tpspp_stream_t stream);
 
 /*
  * DGAB block of the TPS++ regressor on a (N, C, 16, 64) feature map x with the point features

@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
@@ -32,6 +32,11 @@ _SIGNATURES = {
     "tpspp_warp_plan_destroy": ([_f], None),
     "tpspp_conv2d_fwd": ([_f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
     "tpspp_conv2d_bf16_fwd": ([_f, _f, _i, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _f], _i),
+    "tpspp_conv2d_bwd_data": ([_f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f], _i),
+    "tpspp_conv2d_bwd_weight_workspace_floats": ([_f, _i, _i, _i, _i, _i, _i, _i], ctypes.c_size_t),
+    "tpspp_conv2d_bwd_weight": ([_f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, ctypes.c_size_t,
+                                 _f], _i),
+    "tpspp_conv2d_prep_weight": ([_f, _i, _i, _i, _i, _f, _f, _f], _i),
     "tpspp_conv_bf16_chunk_channels": ([_i], _i),
     "tpspp_dgab_fwd": ([_f] * 16 + [_i, _i, _f], _i),
     "tpspp_dgab_bf16_fwd": ([_f] * 16 + [_i, _i, _i, _f], _i),

@@ -606,6 +606,15 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
+    def set_train_backend(self, mode):
+        """Kernels of the TPS++ regressor's convolutions in the training graph (TPS_PP.set_train_backend): "torch"
+        (default, PyTorch's) or "hip" (the HIP forward / backward kernels).  No effect on the eval path."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
+            self.tpsnet.set_train_backend(mode)
+        return self
+
     def extract_feat(self, img, test=False, **kwargs):
         if self.preprocessor is not None:
             img = self.preprocessor(img)

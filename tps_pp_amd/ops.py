@@ -456,6 +456,195 @@ def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=No
     return out
 
 
+# ---- backward of the fused convolution (tpspp_conv_bwd.hip): training the regressor on the HIP kernels -------------
+def _conv_sources(who, srcs):
+    """srcs entries `tensor` or `(tensor, uh, uw)` -> (contiguous tensors, flat src_dims, N, device, Hi, Wi)."""
+    ts, dims = [], []
+    for e in srcs:
+        t, uh, uw = (e, 1, 1) if isinstance(e, torch.Tensor) else e
+        t = _chk(f"{who} source", t, 4)
+        ts.append(t)
+        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw)]
+    N, dev, Hi, Wi = _chk_conv_sources(who, ts, dims, 5)
+    return ts, dims, N, dev, Hi, Wi
+
+
+def _conv_out_size(who, Hi, Wi, kernel, stride):
+    sh, sw = (stride, stride) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
+    if sh not in (1, 2) or sw not in (1, 2):
+        raise ValueError(f"{who}: stride must be 1 or 2 along each axis, got {(sh, sw)}")
+    if kernel not in (1, 3):
+        raise ValueError(f"{who}: kernel must be 1x1 or 3x3")
+    pad = (kernel - 1) // 2
+    return sh, sw, (Hi + 2 * pad - kernel) // sh + 1, (Wi + 2 * pad - kernel) // sw + 1
+
+
+def _chk_grad_out(who, dy, y, relu, shape, dev):
+    dy = _chk("dy", dy, 4)
+    if tuple(dy.shape) != shape or dy.device != dev:
+        raise ValueError(f"{who}: dy must be {shape} on {dev}, got {tuple(dy.shape)} on {dy.device}")
+    if relu:
+        if y is None:
+            raise ValueError(f"{who}: relu=True needs the forward's output y (the mask is y > 0)")
+        y = _chk("y", y, 4)
+        if tuple(y.shape) != shape or y.device != dev:
+            raise ValueError(f"{who}: y must have dy's shape and device")
+    else:
+        y = None
+    return dy, y
+
+
+def prep_conv_weight_device(weight, bias=None, src_channels=None):
+    """ConvWeight for `conv2d` built on the device by `tpspp_conv2d_prep_weight` from PyTorch's (Cout, Cin, KH, KW)
+    weight: the training step's form of `prep_conv_weight` (no host-side rearrangement; bias is used as it is)."""
+    w = _chk("weight", weight.detach(), 4)
+    cout, cin, kh, kw = w.shape
+    if kh != kw or kh not in (1, 3):
+        raise ValueError("prep_conv_weight_device: kernel must be 1x1 or 3x3")
+    kc = int(_lib.lib().tpspp_conv_chunk_channels(int(kh)))
+    wt = torch.empty((cin * kh * kw, cout), device=w.device, dtype=torch.float32)
+    tiled = None
+    if src_channels is None or len(src_channels) == 1 or all(c % kc == 0 for c in src_channels):
+        tiled = torch.empty(((cin + kc - 1) // kc, kh * kw, kc, cout), device=w.device, dtype=torch.float32)
+    with torch.cuda.device(w.device):
+        rc = _lib.lib().tpspp_conv2d_prep_weight(_ptr(w), cout, cin, kh, kw, _ptr(wt), _ptr(tiled), _stream(w))
+    _lib.check(rc, "tpspp_conv2d_prep_weight")
+    b = None if bias is None else _chk("bias", bias.detach(), 1)
+    return ConvWeight(wt, tiled, b, kh)
+
+
+def conv2d_bwd_data(dy, weight, srcs, stride=(1, 1), y=None, relu=True, need=None):
+    """Gradients of `conv2d(srcs, ..., relu)` (res_mode 0) with respect to its sources (`tpspp_conv2d_bwd_data`).
+
+    dy (N, Cout, Ho, Wo); weight (Cout, Cin, KH, KW) as PyTorch holds it; srcs as `conv2d` takes them (only their
+    shapes and upsampling factors are used); y the forward's output (needed with relu: the mask is y > 0).
+    need: per-source flags (default all).  Returns a list with one (N, C_i, H_i, W_i) tensor or None per source."""
+    import ctypes
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_data", srcs)
+    w = _chk("weight", weight.detach(), 4)
+    cout, cin, kh, kw = w.shape
+    if kh != kw or cin != sum(t.shape[1] for t in ts) or w.device != dev:
+        raise ValueError("conv2d_bwd_data: weight must be (Cout, sum C_i, K, K) on the sources' device")
+    sh, sw, Ho, Wo = _conv_out_size("conv2d_bwd_data", Hi, Wi, kh, stride)
+    dy, y = _chk_grad_out("conv2d_bwd_data", dy, y, relu, (N, cout, Ho, Wo), dev)
+    need = [True] * len(ts) if need is None else [bool(v) for v in need]
+    outs = [torch.empty_like(t) if nd else None for t, nd in zip(ts, need)]
+    if N == 0 or not any(need):
+        return outs
+    ptrs = (ctypes.c_void_p * len(ts))(*[0 if o is None else o.data_ptr() for o in outs])
+    dim_arr = (ctypes.c_int * len(dims))(*dims)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_conv2d_bwd_data(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
+                                              len(ts), _ptr(w), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, kh, kw,
+                                              sh, sw, Ho, Wo, _stream(dy))
+    _lib.check(rc, "tpspp_conv2d_bwd_data")
+    return outs
+
+
+def conv2d_bwd_weight_workspace_floats(srcs_dims, N, Cout, kernel, Ho, Wo):
+    """Floats of workspace `conv2d_bwd_weight` needs (`tpspp_conv2d_bwd_weight_workspace_floats`): srcs_dims the flat
+    {C, H, W, uh, uw} per source; 0 for N = 0.  The split-K slice count behind it depends on the shapes only."""
+    import ctypes
+    dim_arr = (ctypes.c_int * len(srcs_dims))(*srcs_dims)
+    return int(_lib.lib().tpspp_conv2d_bwd_weight_workspace_floats(ctypes.cast(dim_arr, ctypes.c_void_p),
+                                                                    len(srcs_dims) // 5, N, Cout, kernel, kernel,
+                                                                    Ho, Wo))
+
+
+def conv2d_bwd_weight(srcs, dy, kernel, stride=(1, 1), y=None, relu=True, want_weight=True, want_bias=True):
+    """Weight and bias gradients of `conv2d(srcs, ..., relu)` (res_mode 0) (`tpspp_conv2d_bwd_weight`): a fixed
+    split-K without atomics, bitwise reproducible.  Returns (dW (Cout, Cin, K, K) | None, db (Cout) | None)."""
+    import ctypes
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_weight", srcs)
+    sh, sw, Ho, Wo = _conv_out_size("conv2d_bwd_weight", Hi, Wi, int(kernel), stride)
+    if dy.dim() != 4:
+        raise ValueError("conv2d_bwd_weight: dy must be (N, Cout, Ho, Wo)")
+    cout, cin = dy.shape[1], sum(t.shape[1] for t in ts)
+    dy, y = _chk_grad_out("conv2d_bwd_weight", dy, y, relu, (N, cout, Ho, Wo), dev)
+    dw = torch.empty((cout, cin, kernel, kernel), device=dev, dtype=torch.float32) if want_weight else None
+    db = torch.empty((cout,), device=dev, dtype=torch.float32) if want_bias else None
+    if N == 0:
+        if dw is not None:
+            dw.zero_()
+        if db is not None:
+            db.zero_()
+        return dw, db
+    if dw is None and db is None:
+        return dw, db
+    nws = conv2d_bwd_weight_workspace_floats(dims, N, cout, int(kernel), Ho, Wo)
+    ws = torch.empty((nws,), device=dev, dtype=torch.float32)
+    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    dim_arr = (ctypes.c_int * len(dims))(*dims)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_conv2d_bwd_weight(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
+                                                len(ts), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, int(kernel),
+                                                int(kernel), sh, sw, Ho, Wo, _ptr(dw), _ptr(db), _ptr(ws), nws,
+                                                _stream(dy))
+    _lib.check(rc, "tpspp_conv2d_bwd_weight")
+    return dw, db
+
+
+class _ConvFunction(torch.autograd.Function):
+    """Differentiable `conv2d` (res_mode 0): HIP forward (`tpspp_conv2d_fwd`), HIP backward (`tpspp_conv2d_bwd_data`,
+    `tpspp_conv2d_bwd_weight`).  Saves the sources, the weight and the output y (the ReLU mask is y > 0)."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, cfg, *ts):
+        ups, stride, relu, cw = cfg
+        if cw is None:
+            cw = prep_conv_weight_device(weight, bias, [t.shape[1] for t in ts])
+        entries = [(t, uh, uw) for t, (uh, uw) in zip(ts, ups)]
+        y = conv2d(entries, cw, stride, relu=relu)
+        ctx.cfg = (ups, stride, relu, weight.shape[-1], bias is not None)
+        ctx.save_for_backward(weight, y, *ts)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        ups, stride, relu, kernel, has_bias = ctx.cfg
+        weight, y, *ts = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy = gy.float().contiguous()
+        entries = [(t, uh, uw) for t, (uh, uw) in zip(ts, ups)]
+        dsrc = [None] * len(ts)
+        if any(need[3:]):
+            dsrc = conv2d_bwd_data(gy, weight, entries, stride, y=y, relu=relu, need=need[3:])
+        dw = db = None
+        if need[0] or (has_bias and need[1]):
+            dw, db = conv2d_bwd_weight(entries, gy, kernel, stride, y=y, relu=relu, want_weight=need[0],
+                                       want_bias=has_bias and need[1])
+        return (dw, db, None, *dsrc)
+
+
+def conv2d_autograd(srcs, weight, bias, stride=(1, 1), relu=True, cw=None):
+    """`conv2d` inside an autograd graph: y = act(conv(cat_c(up(src_i)), weight) + bias), act ReLU or none.
+
+    srcs as `conv2d` takes them (tensors or (tensor, uh, uw)); weight (Cout, Cin, K, K) and bias (Cout) | None are the
+    layer's parameters (gradients reach them); cw: the forward's ConvWeight prepared from them (a cache the caller keys on
+    the parameters' versions), built on the device here if None.  The backward honours `needs_input_grad`: no data-gradient
+    launch when no source needs one, no weight-gradient launch for a frozen layer."""
+    if not 1 <= len(srcs) <= 3:
+        raise ValueError("conv2d_autograd: 1..3 sources")
+    ts, ups = [], []
+    for e in srcs:
+        t, uh, uw = (e, 1, 1) if isinstance(e, torch.Tensor) else e
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("conv2d_autograd: expected tensors")
+        if not t.is_cuda:
+            raise _lib.TpsppError(f"conv2d_autograd: tensor is on {t.device}; the HIP path needs a GPU tensor "
+                                  "(no CPU fallback)")
+        ts.append(t)
+        ups.append((int(uh), int(uw)))
+    _chk("weight", weight, 4)
+    if bias is not None:
+        _chk("bias", bias, 1)
+    if relu not in (0, 1, False, True):
+        raise ValueError("conv2d_autograd: relu must be True (ReLU) or False (none)")
+    st = (stride, stride) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
+    return _ConvFunction.apply(weight, bias, (tuple(ups), st, int(bool(relu)), cw), *ts)
+
+
 def _chk16(name, t, ndim=None):
     """bf16 path: a GPU tensor that is float32 or bfloat16."""
     if not isinstance(t, torch.Tensor):

@@ -15,7 +15,8 @@ Every stage of `forward` in eval mode runs on the hand-written HIP kernels of li
     them fused, the DGAB chain, the score and the per-point FC stacks.
 In training mode (`module.train()`) the transformation stage still runs on the HIP kernels in both
 directions while the regressor is the plain PyTorch composition of the same layers, so that autograd
-reaches its parameters (logged once).  No CPU fallback: CPU tensors raise.
+reaches its parameters (logged once); `set_train_backend("hip")` puts its convolutions on the HIP forward / backward
+kernels (tpspp_conv_bwd.hip).  No CPU fallback: CPU tensors raise.
 """
 import numpy as np
 import torch
@@ -364,7 +365,7 @@ class TPS_PP(nn.Module):
         for k in head + rest + tail:
             self._modules[k] = self._modules.pop(k)           # re-insert: dicts keep insertion order
         self.type = variant
-        for c in ("_cw_cache", "_cw16_cache", "_front_cache", "_front16_cache"):
+        for c in ("_cw_cache", "_cw16_cache", "_front_cache", "_front16_cache", "_train_cw_cache"):
             if hasattr(self, c):
                 delattr(self, c)
 
@@ -685,13 +686,104 @@ class TPS_PP(nn.Module):
                                        in1=batch_img, want_grid=want_grid, P_hat_t=P_hat_t)
         return (out0, out1, grid) if want_grid else (out0, out1)
 
+    # ---- training graph of the regressor's convolutions on the HIP kernels (tpspp_conv_bwd.hip) -------------------
+    def set_train_backend(self, mode):
+        """Which kernels the convolutions of the control-point regressor use in the training graph (`.train()`, or
+        eval mode with inputs that carry gradients): "torch" (default) -- the PyTorch composition of the layers, as the
+        reference runs them; "hip" -- every ConvModule on `ops.conv2d_autograd` (HIP forward and backward, the
+        concatenation and nearest upsampling in front of down_feat / k_encoder.0 / k_decoder folded in).  CBAM, DGAB,
+        the TPE layers and the score stay PyTorch in either mode; the warp is `ops.warp_autograd` in both.  Touches
+        neither the parameters, the state_dict nor the eval path."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")
+
+    def _train_conv(self, name, mod, srcs, stride):
+        """One ConvModule (conv + in-place ReLU) on `ops.conv2d_autograd`; the forward's weight layouts are cached
+        per layer and rebuilt on the device when the parameters change (data_ptr / _version: an optimiser step, an
+        in-place op on the parameter, load_state_dict).  An edit through `param.data` bumps the version counter of a
+        different tensor and is NOT seen: after one, call `invalidate_train_cache()` (otherwise the forward would use the
+        stale layout while the backward reads the current weight)."""
+        conv = mod.conv
+        if tuple(conv.padding) != ((conv.kernel_size[0] - 1) // 2, (conv.kernel_size[1] - 1) // 2):
+            raise ValueError(f"TPS_PP.{name}: the HIP training path needs 'same' padding")
+        w, b = conv.weight, conv.bias
+        key = (w.data_ptr(), w._version, b.data_ptr(), b._version, tuple(t.shape[1] for t in
+                                                                          (e if isinstance(e, torch.Tensor) else e[0]
+                                                                           for e in srcs)))
+        cache = self.__dict__.setdefault("_train_cw_cache", {})
+        ent = cache.get(name)
+        if ent is None or ent[0] != key:
+            chans = list(key[-1])
+            ent = cache[name] = (key, ops.prep_conv_weight_device(w, b, chans))
+        return ops.conv2d_autograd(srcs, w, b, stride, relu=True, cw=ent[1])
+
+    def invalidate_train_cache(self):
+        """Drop the HIP training path's cached forward weight layouts (needed only after edits through `param.data`)."""
+        self.__dict__.pop("_train_cw_cache", None)
+        return self
+
+    def _regress_train_hip(self, batch_img, outs):
+        """`_regress_torch` with every ConvModule on the HIP forward / backward kernels: the concatenations, the
+        `up_sample` in front of down_feat and the decoder's nn.Upsample are folded into the convolutions; the skip
+        additions stay plain tensor adds (the ReLU mask needs each convolution's own output)."""
+        cv = self._train_conv
+        x, o0, o1 = batch_img.contiguous(), outs[0].contiguous(), outs[1].contiguous()
+
+        def scale(up):
+            f = up.scale_factor
+            f = f if isinstance(f, (tuple, list)) else (f, f)
+            if up.mode != "nearest" or any(float(v) != int(v) for v in f):
+                raise ValueError("TPS_PP: the HIP training path folds integer nearest upsampling only")
+            return int(f[0]), int(f[1])
+
+        if self.type == "ResNet45v2":
+            feat0 = cv("down0", self.down0, [o0], self.down0.conv.stride)
+            feat1 = cv("down1", self.down1, [o1], self.down1.conv.stride)
+            feat2 = cv("down2", self.down2, [x], self.down2.conv.stride)
+            feat_cat = [cv("down0_1", self.down0_1, [feat0], self.down0_1.conv.stride),
+                        cv("down1_1", self.down1_1, [feat1], self.down1_1.conv.stride), feat2]
+            uh, uw = scale(self.up_sample)
+            feat_grid = cv("down_feat", self.down_feat, [feat0, feat1, (feat2, uh, uw)], self.down_feat.conv.stride)
+        else:
+            feat_cat = [cv("down0", self.down0, [o0], self.down0.conv.stride),
+                        cv("down1", self.down1, [o1], self.down1.conv.stride),
+                        cv("down2", self.down2, [x], self.down2.conv.stride)]
+            feat_grid = batch_img
+        E = self.MSFA.conv
+        features = []
+        k = feat_cat
+        for i, layer in enumerate(E.k_encoder):
+            k = cv(f"enc{i}", layer, k if i == 0 else [k], layer.conv.stride)
+            features.append(k)
+        point = features[-1]
+        k = E.atten(point)
+        n = len(E.k_decoder)
+        for i in range(n):
+            up, layer = E.k_decoder[i][0], E.k_decoder[i][1]
+            uh, uw = scale(up)
+            k = cv(f"dec{i}", layer, [(k, uh, uw)], layer.conv.stride)
+            if i < n - 1:
+                k = k + features[n - 2 - i]
+        control_point, atten_score = self.TPE(point, k)
+        return control_point, atten_score, feat_grid
+
     def _forward_autograd(self, batch_img, outs):
         """Training graph: the transformation stage runs on the HIP kernels in both
-        directions (`ops.warp_autograd`: tpspp_warp_fwd / tpspp_warp_bwd); the control-point regressor is
-        the plain PyTorch composition of the same layers, so autograd reaches its parameters (its backward
-        kernels are not part of this path).  GPU tensors only."""
+        directions (`ops.warp_autograd`: tpspp_warp_fwd / tpspp_warp_bwd); the control-point regressor is the
+        composition of the same layers, its convolutions on PyTorch's kernels (train backend "torch", the default) or
+        on the HIP forward / backward kernels (`set_train_backend("hip")`), so autograd reaches its parameters.  GPU
+        tensors only."""
         ops.require_gpu(batch_img, "TPS_PP")
-        control_point, atten_score, feat_grid = self._regress_torch(batch_img, outs)
+        if self.train_backend == "hip":
+            control_point, atten_score, feat_grid = self._regress_train_hip(batch_img, outs)
+        else:
+            control_point, atten_score, feat_grid = self._regress_torch(batch_img, outs)
         at = self.atten_tps
         P_xy, P_hat_t = at.device_constants(batch_img.device)
         output, mp_img = ops.warp_autograd(feat_grid.float(), control_point.float(), at.hat_C, at.P_hat,
@@ -724,10 +816,16 @@ class TPS_PP(nn.Module):
             # too.  Plain eval inference takes the HIP kernels (they record no autograd graph).
             if not getattr(self, "_logged_autograd", False):
                 import logging
-                logging.getLogger("tps_pp_amd").warning(
-                    "TPS_PP.train(): control-point regressor as a PyTorch composition (library kernels, fp32) so that "
-                    "autograd reaches its parameters; warp forward / backward on the HIP kernels. Call .eval() for the "
-                    "all-HIP inference path.")
+                if self.train_backend == "hip":
+                    logging.getLogger("tps_pp_amd").warning(
+                        "TPS_PP.train(): control-point regressor with its convolutions on the HIP forward / backward "
+                        "kernels (CBAM, DGAB, TPE and the score as PyTorch compositions); warp forward / backward on the "
+                        "HIP kernels. Call .eval() for the all-HIP inference path.")
+                else:
+                    logging.getLogger("tps_pp_amd").warning(
+                        "TPS_PP.train(): control-point regressor as a PyTorch composition (library kernels, fp32) so that "
+                        "autograd reaches its parameters; warp forward / backward on the HIP kernels. Call .eval() for the "
+                        "all-HIP inference path (or set_train_backend(\"hip\") for the convolutions of training).")
                 self._logged_autograd = True
             self._check_geometry(batch_img, outs)
             return self._forward_autograd(batch_img.float(), [o.float() for o in outs])
