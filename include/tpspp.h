@@ -31,11 +31,14 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 6   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 7   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
                                5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
-                               6: tpspp_conv2d_bwd_data / _bwd_weight / _bwd_weight_workspace_floats, tpspp_conv2d_prep_weight */
+                               6: tpspp_conv2d_bwd_data / _bwd_weight / _bwd_weight_workspace_floats, tpspp_conv2d_prep_weight;
+                               7: the regressor's training kernels: tpspp_mm_f32, tpspp_linear_bwd_weight (+ _workspace_floats),
+                                  tpspp_act_bwd, tpspp_plane_ln_fwd / _bwd (+ _workspace_floats), tpspp_dgab_pool_fwd / _bwd,
+                                  tpspp_dgab_gate_fwd / _bwd, tpspp_cbam_train_fwd, tpspp_cbam_bwd (+ _workspace_floats) */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -298,6 +301,136 @@ int tpspp_conv2d_bwd_weight(const float* const* src_ptrs, const int* src_dims, i
  */
 int tpspp_conv2d_prep_weight(const float* weight, int Cout, int Cin, int KH, int KW, float* weight_t,
                              float* weight_tiled, tpspp_stream_t stream);
+
+/*
+ * Training kernels of the control-point regressor's other layers (ABI 7; train backend "hip_all", tpspp_regressor_bwd.hip).
+ * The autograd functions of tps_pp_amd/ops.py (dgab_autograd, score_autograd, cbam_autograd, tpe_points_autograd) compose
+ * DGAB, the score, CBAM and the localization FCs, forward and backward, from the entry points below.  fp32 throughout.
+ * REPRODUCIBLE: no atomics; every reduction over rows is a fixed split (slice count a function of the sizes alone) whose
+ * slices write slabs into the caller's workspace, added in slice order by a second launch: gradients are bitwise identical
+ * across calls and streams.  Host arrays (`*_strides`, `x_layout`) are read during the call only.
+ */
+
+/*
+ * Strided batched matrix product on the fp32 matrix cores (v_mfma_f32_32x32x2_f32; fp32 accumulation in four k chains
+ * interleaved by pairs of k, added pairwise at the end):
+ *   C[b][i][j] = epi(alpha * sum_{k < K_b} A[b][i][k] * B[b][j][k] + bias[j])  (+ R[b][i][j] when R != NULL)
+ * for b < batch, i < M, j < N.  Element (b, i, k) of A is A[b*a_strides[0] + i*a_strides[1] + k*a_strides[2]] (B and C / R
+ * likewise with b_strides, c_strides), in elements: tokens can be read from and written to NCHW maps in place.
+ * epilogue: 0 none, 1 ReLU, 2 GELU (erf form), 3 tanh.  bias (N) or NULL.  k_total > 0 splits one long reduction over the
+ * batch (K_b = min(K, k_total - b*K)), <= 0: K_b = K.  C must not alias A, B or R.
+ * replaces: nn.Linear (+ ReLU / GELU) and the score's einsum + tanh in the autograd graph of backbones/tps_pp/DGAB.py:7-23,55,
+ *           backbones/tps_pp/tps_pp.py:293-323
+ */
+int tpspp_mm_f32(int batch, int M, int N, int K, const float* A, const long long* a_strides, const float* B,
+                 const long long* b_strides, float* C, const long long* c_strides, const float* bias, const float* R,
+                 int epilogue, float alpha, int k_total, tpspp_stream_t stream);
+
+/*
+ * Floats of workspace tpspp_linear_bwd_weight needs: S * O * (K + 1), S = ceil(M / L), L = max(256, ceil(M / 512))
+ * rounded up to a multiple of 16 (0 for non-positive sizes).
+ */
+size_t tpspp_linear_bwd_weight_workspace_floats(long long M, int O, int K);
+
+/*
+ * Weight and bias gradient of a Linear layer y = x W^T + b over M rows:
+ *   dweight (O, K) = sum_r dy[r][:]^T x[r][:],   dbias (O) = sum_r dy[r][:]    (either may be NULL, not both)
+ * dy (M, O) dense.  x row r = (q, i), q = r / x_layout[0], i = r % x_layout[0]: x[q*x_layout[1] + i*x_layout[2] + k*x_layout[3]]
+ * (dense rows: {M, 0, K, 1}; NCHW tokens: {H*W, C*H*W, 1, H*W}); x_act 2: the layer's input is GELU(x) (x = the previous
+ * layer's pre-activation, applied as x is staged), 0: x itself.  M < 2^31.  Fixed split-K into slices of L rows (see the
+ * workspace query), matrix cores for dweight, then the ordered slab sum.
+ * replaces: the autograd of nn.Linear (weight, bias) at backbones/tps_pp/DGAB.py:7-23,32-34, backbones/tps_pp/tps_pp.py:240-287
+ */
+int tpspp_linear_bwd_weight(const float* dy, const float* x, const long long* x_layout, int x_act, long long M, int O,
+                            int K, float* dweight, float* dbias, float* ws, size_t ws_floats, tpspp_stream_t stream);
+
+/*
+ * Pointwise backward of an activation over n elements: out = grad * f'(.), from t:
+ *   op 0 ReLU (t = its output: grad where t > 0), op 1 GELU, erf form (t = its input), op 2 tanh(scale * u)
+ *   (t = its output: grad * (1 - t^2) * scale, the gradient with respect to u).  out may alias grad.
+ * replaces: threshold_backward, GeluBackward, TanhBackward + MulBackward in the autograd graph of tps_pp.py:293-323, DGAB.py:7-23
+ */
+int tpspp_act_bwd(int op, long long n, const float* grad, const float* t, float scale, float* out, tpspp_stream_t stream);
+
+/*
+ * LayerNorm over planes: x (rows, P) -> y = (x - mean) * rstd * w + b, w / b (P), rstd = 1 / sqrt(biased var + eps);
+ * mean, rstd (rows) saved for the backward.  One workgroup per plane, fixed reduction tree.
+ * replaces: nn.LayerNorm([high, width]) (norm1, norm2) at backbones/tps_pp/DGAB.py:58-77
+ */
+int tpspp_plane_ln_fwd(const float* x, const float* w, const float* b, long long rows, int P, float eps, float* y,
+                       float* mean, float* rstd, tpspp_stream_t stream);
+
+/*
+ * Floats of workspace tpspp_plane_ln_bwd needs when it forms parameter gradients: S * 2 * P, S = ceil(rows / L),
+ * L = max(16, ceil(rows / 512)) rounded up to a multiple of 16.
+ */
+size_t tpspp_plane_ln_bwd_workspace_floats(long long rows, int P);
+
+/*
+ * Backward of tpspp_plane_ln_fwd from the saved mean / rstd: dx (rows, P) = the input gradient (added to dx's contents when
+ * accumulate = 1), or NULL; dweight, dbias (P) = sum over planes of dy * xhat and of dy (fixed split over planes), or NULL.
+ * replaces: the autograd of norm1 / norm2, backbones/tps_pp/DGAB.py:58-77
+ */
+int tpspp_plane_ln_bwd(const float* dy, const float* x, const float* w, const float* mean, const float* rstd, long long rows,
+                       int P, float* dx, int accumulate, float* dweight, float* dbias, float* ws, size_t ws_floats,
+                       tpspp_stream_t stream);
+
+/*
+ * DGAB's pooled gate inputs: xn (N, C, H, W) (the norm1 output), y (N, C, T) the point map (en_feat, T = its H*W) ->
+ *   catw (N, C, W + T) = [mean over H of xn, y],  cath (N, C, H + T) = [mean over W of xn, y].
+ * H, W <= 256, H * W <= 4096.  One workgroup per (n, c) plane.
+ * replaces: torch.cat([x.mean(2), y], 2), torch.cat([x.mean(3), y], 2)   backbones/tps_pp/DGAB.py:37-41
+ */
+int tpspp_dgab_pool_fwd(const float* xn, const float* y, int N, int C, int H, int W, int T, float* catw, float* cath,
+                        tpspp_stream_t stream);
+
+/*
+ * Backward of tpspp_dgab_pool_fwd: dxn[n][c][i][j] += dcatw[n][c][j] / H + dcath[n][c][i] / W (accumulates);
+ * dy (N, C, T) = dcatw[.., W:] + dcath[.., H:] (written; NULL: not formed).
+ * replaces: the autograd of backbones/tps_pp/DGAB.py:36-41
+ */
+int tpspp_dgab_pool_bwd(const float* dcatw, const float* dcath, int N, int C, int H, int W, int T, float* dxn, float* dy,
+                        tpspp_stream_t stream);
+
+/*
+ * DGAB's gating: w (N, C, W + 1) = mlp_w output, h (N, C, H + 1) = mlp_h output, xn (N, C, H, W) ->
+ *   A[n][c][i][j] = softmax(h[n][c][:H])[i] * xn * h[n][c][H] + softmax(w[n][c][:W])[j] * xn * w[n][c][W].
+ * replaces: backbones/tps_pp/DGAB.py:40-45 (softmaxes, gates, the two products and their sum; proj follows on tpspp_mm_f32)
+ */
+int tpspp_dgab_gate_fwd(const float* xn, const float* w, const float* h, int N, int C, int H, int W, float* A,
+                        tpspp_stream_t stream);
+
+/*
+ * Backward of tpspp_dgab_gate_fwd: dxn = dA * (vh[i] gh + vw[j] gw) (written), dw (N, C, W + 1) and dh (N, C, H + 1) =
+ * the gradients of the pre-softmax gate vectors (softmax backward included).
+ * replaces: the autograd of backbones/tps_pp/DGAB.py:40-45
+ */
+int tpspp_dgab_gate_bwd(const float* dA, const float* xn, const float* w, const float* h, int N, int C, int H, int W,
+                        float* dxn, float* dw, float* dh, tpspp_stream_t stream);
+
+/*
+ * CBAM forward for training: x (N, C, H, W), shared_MLP weights w1 (Cr, C), w2 (C, Cr) (bias-free 1x1 convolutions),
+ * spatial conv cw (1, 2, 3, 3), cb (1) -> out (N, C, H, W), and the gates ca (N, C), sa (N, H*W).  C <= 256, Cr <= 64,
+ * H*W <= 256, C*H*W <= 4096.  One workgroup per image.
+ * replaces: backbones/tps_pp/tps_pp.py:27-82 as called at :163, in the training graph
+ */
+int tpspp_cbam_train_fwd(const float* x, const float* w1, const float* w2, const float* cw, const float* cb, int N, int C,
+                         int Cr, int H, int W, float* out, float* ca, float* sa, tpspp_stream_t stream);
+
+/* Floats of workspace tpspp_cbam_bwd needs: N * (2 * C * Cr + 19) (per-image slabs). */
+size_t tpspp_cbam_bwd_workspace_floats(int N, int C, int Cr);
+
+/*
+ * Backward of CBAM (recomputes the forward's gates from x): dx (N, C, H, W) written; dw1 (Cr, C), dw2 (C, Cr), dcw (18),
+ * dcb (1) = per-image slabs summed in image order, each NULL when not wanted.  The maxima route their gradient to the
+ * first maximal element (torch.max's choice on ties).
+ * replaces: the autograd of backbones/tps_pp/tps_pp.py:27-82
+ */
+int tpspp_cbam_bwd(const float* dout, const float* x, const float* w1, const float* w2, const float* cw, const float* cb,
+                   int N, int C, int Cr, int H, int W, float* dx, float* dw1, float* dw2, float* dcw, float* dcb, float* ws,
+                   size_t ws_floats, tpspp_stream_t stream);
+
+
 
 /*
  * DGAB block of the TPS++ regressor on a (N, C, 16, 64) feature map x with the point features

@@ -1,13 +1,17 @@
-"""Training of TPS_PP's regressor convolutions on the HIP kernels (tpspp_conv_bwd.hip) at batch 512, fp32; one JSON line.
+"""Training of TPS_PP's control-point regressor on the HIP kernels at batch 512, fp32; one JSON line.
 
 (a) every ConvModule of the ResNet45v2 wiring: HIP backward (data gradient + weight / bias gradient) against
     torch.ops.aten.convolution_backward on the same tensors -- the library is handed the logical (concatenated,
     upsampled) input and the masked dZ ready-made, the HIP kernels build both on the fly -- in ms and TFLOP/s from the
     shapes (backward = 2 x the forward's 2*N*Ho*Wo*Cout*Cin*K*K);
-(b) a whole TPS_PP training step (forward + backward, no optimiser) with set_train_backend("torch") against "hip":
-    alternating timed regions, the median of each, in images/s.
+(b) the regressor's other blocks -- DGAB, the score (feat_linear, p_linear, product, tanh), CBAM and the localization
+    FCs -- forward and forward + backward on the HIP kernels of set_train_backend("hip_all") (tpspp_regressor_bwd.hip)
+    against the PyTorch composition of the same module on the same tensors, in ms;
+(c) a whole TPS_PP training step (forward + backward, no optimiser) with set_train_backend("torch"), "hip" and
+    "hip_all": alternating timed regions, the median of each, in images/s.
 
-    python scripts/bench_train.py [--batch 512] [--reps 20] [--regions 7] [--steps 3]
+    python scripts/bench_train.py [--batch 512] [--reps 20] [--regions 7] [--steps 3] [--skip-conv]
+--skip-conv leaves (a) out (the line then carries the blocks and the step only: profiles/train_regressor_line.json).
 Kernel times: `rocprofv3 --kernel-trace --stats -- python3 scripts/bench_train.py --reps 3 --regions 1` (own run).
 """
 import argparse
@@ -99,19 +103,68 @@ def step_rates(dev, N, regions, steps):
         res = m(x, outs)
         (res["output"].square().mean() + res["mp_img"].square().mean()).backward()
 
-    times = {"torch": [], "hip": []}
-    for mode in ("torch", "hip"):           # warm-up of both (kernel selection, caches)
+    modes = ("torch", "hip", "hip_all")
+    times = {k: [] for k in modes}
+    for mode in modes:                      # warm-up of each (kernel selection, caches)
         m.set_train_backend(mode)
         for _ in range(3):
             step()
     torch.cuda.synchronize()
     for _ in range(regions):
-        for mode in ("torch", "hip"):
+        for mode in modes:
             m.set_train_backend(mode)
             step()
             times[mode].append(timed(step, steps, warm=0))
     med = {k: statistics.median(v) for k, v in times.items()}
     return {k: round(N / (v / 1e3), 1) for k, v in med.items()}, {k: round(v, 3) for k, v in med.items()}
+
+
+def block_rows(dev, N, reps):
+    """Each block of the regressor's TPE / CBAM at batch N: the HIP autograd function of "hip_all" against the PyTorch
+    composition of the same module (library kernels), forward alone and forward + backward (every input and parameter
+    gradient) for the same incoming gradient."""
+    torch.manual_seed(3)
+    m = TPS_PP().to(dev).train()
+    T = m.TPE
+    with torch.no_grad():
+        T.localization_fc2.weight.normal_(0, 0.02)
+    g = torch.Generator(device=dev).manual_seed(4)
+    de = torch.randn((N, 64, 16, 64), generator=g, device=dev).requires_grad_(True)
+    en = torch.randn((N, 64, 2, 16), generator=g, device=dev).abs().requires_grad_(True)
+    n = N
+    blocks = [
+        ("dgab", [de, en], list(T.atten[0].parameters()),
+         lambda: ops.dgab_autograd(de, en.reshape(n, 64, -1), T.atten[0]),
+         lambda: T.atten[0](de, en.reshape(n, 64, -1).transpose(1, 2))),
+        ("score", [de, en], list(T.feat_linear.parameters()) + list(T.p_linear.parameters()),
+         lambda: ops.score_autograd(de, en, T),
+         lambda: T.get_score(en.reshape(n, 64, -1).transpose(1, 2), de).transpose(1, 2)),
+        ("cbam", [en], list(m.MSFA.conv.atten.parameters()),
+         lambda: ops.cbam_autograd(en, m.MSFA.conv.atten), lambda: m.MSFA.conv.atten(en)),
+        ("localization", [en], list(T.localization_fc1.parameters()) + list(T.localization_fc2.parameters()),
+         lambda: ops.tpe_points_autograd(en, T),
+         lambda: T.localization_fc2(T.localization_fc1(en.reshape(n, 64, -1).transpose(1, 2)).reshape(n, -1)).view(
+             n, T.num_fiducial, 2)),
+    ]
+    rows = []
+    for name, ins, params, hip, lib in blocks:
+        r = dict(block=name)
+        for tag, fn in (("hip", hip), ("torch", lib)):
+            out = fn()
+            gout = torch.randn(out.shape, generator=g, device=dev)
+            wrt = ins + params
+
+            def fwd_bwd(fn=fn, gout=gout, wrt=wrt):
+                torch.autograd.grad(fn(), wrt, gout)
+
+            def fwd(fn=fn):
+                with torch.no_grad():
+                    fn()
+            r[f"ms_fwd_{tag}"] = round(timed(fwd, reps), 4)
+            r[f"ms_fwd_bwd_{tag}"] = round(timed(fwd_bwd, reps), 4)
+        r["speedup_fwd_bwd"] = round(r["ms_fwd_bwd_torch"] / r["ms_fwd_bwd_hip"], 3)
+        rows.append(r)
+    return rows
 
 
 def main():
@@ -120,21 +173,27 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--regions", type=int, default=7)
     ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--skip-conv", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.backends.cudnn.benchmark = False
+    blocks = block_rows(dev, a.batch, a.reps)
+    ips, ms = step_rates(dev, a.batch, a.regions, a.steps)
+    step = dict(images_per_s=ips, ms=ms, regions=a.regions, steps_per_region=a.steps)
+    if a.skip_conv:
+        print(json.dumps(dict(metric="tpspp_regressor_train", batch=a.batch, dtype="fp32", blocks=blocks,
+                              train_step=step)))
+        return
     rows = [layer_row(dev, *L, a.batch, a.reps) for L in LAYERS]
     gflop = sum(r["gflop_bwd"] for r in rows)
     t_hip = sum(r["ms_hip"] for r in rows)
     t_lib = sum(r["ms_miopen"] for r in rows)
     enc0 = next(r for r in rows if r["layer"] == "k_encoder.0")
-    ips, ms = step_rates(dev, a.batch, a.regions, a.steps)
     out = dict(metric="tpspp_conv_backward", batch=a.batch, dtype="fp32",
                aggregate=dict(gflop=round(gflop, 1), ms_hip=round(t_hip, 3), ms_miopen=round(t_lib, 3),
                               tflops_hip=round(gflop / t_hip, 2), tflops_miopen=round(gflop / t_lib, 2)),
                k_encoder0_data_vs_fwd=round(enc0["tflops_hip_data"] / enc0["tflops_fwd_hip"], 3),
-               train_step=dict(images_per_s=ips, ms=ms, regions=a.regions, steps_per_region=a.steps),
-               layers=rows)
+               train_step=step, layers=rows, blocks=blocks)
     print(json.dumps(out))
 
 

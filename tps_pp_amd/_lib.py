@@ -8,10 +8,11 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
+_l = ctypes.c_longlong
 
 _SIGNATURES = {
     "tpspp_abi_version": ([], _i),
@@ -37,6 +38,20 @@ _SIGNATURES = {
     "tpspp_conv2d_bwd_weight": ([_f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, ctypes.c_size_t,
                                  _f], _i),
     "tpspp_conv2d_prep_weight": ([_f, _i, _i, _i, _i, _f, _f, _f], _i),
+    "tpspp_mm_f32": ([_i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _i, ctypes.c_float, _i, _f], _i),
+    "tpspp_linear_bwd_weight_workspace_floats": ([_l, _i, _i], ctypes.c_size_t),
+    "tpspp_linear_bwd_weight": ([_f, _f, _f, _i, _l, _i, _i, _f, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_act_bwd": ([_i, _l, _f, _f, ctypes.c_float, _f, _f], _i),
+    "tpspp_plane_ln_fwd": ([_f, _f, _f, _l, _i, ctypes.c_float, _f, _f, _f, _f], _i),
+    "tpspp_plane_ln_bwd_workspace_floats": ([_l, _i], ctypes.c_size_t),
+    "tpspp_plane_ln_bwd": ([_f, _f, _f, _f, _f, _l, _i, _f, _i, _f, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_dgab_pool_fwd": ([_f, _f, _i, _i, _i, _i, _i, _f, _f, _f], _i),
+    "tpspp_dgab_pool_bwd": ([_f, _f, _i, _i, _i, _i, _i, _f, _f, _f], _i),
+    "tpspp_dgab_gate_fwd": ([_f, _f, _f, _i, _i, _i, _i, _f, _f], _i),
+    "tpspp_dgab_gate_bwd": ([_f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, _f], _i),
+    "tpspp_cbam_train_fwd": ([_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f], _i),
+    "tpspp_cbam_bwd_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
+    "tpspp_cbam_bwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
     "tpspp_conv_bf16_chunk_channels": ([_i], _i),
     "tpspp_dgab_fwd": ([_f] * 16 + [_i, _i, _f], _i),
     "tpspp_dgab_bf16_fwd": ([_f] * 16 + [_i, _i, _i, _f], _i),

@@ -607,10 +607,11 @@ class EncodeDecodeRecognizer(nn.Module):
         return self
 
     def set_train_backend(self, mode):
-        """Kernels of the TPS++ regressor's convolutions in the training graph (TPS_PP.set_train_backend): "torch"
-        (default, PyTorch's) or "hip" (the HIP forward / backward kernels).  No effect on the eval path."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
+        "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).
+        No effect on the eval path."""
+        if mode not in ("torch", "hip", "hip_all"):
+            raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
         if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
             self.tpsnet.set_train_backend(mode)
         return self

@@ -1576,3 +1576,407 @@ def warp_autograd(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, 
     """`warp` inside an autograd graph: returns out0 or (out0, out1); gradients flow to in0, ctrl, score, in1."""
     return _WarpFunction.apply(in0, ctrl, score, in1, inv_delta_C, P_hat, P_xy, P_hat_t,
                                (int(out_hw[0]), int(out_hw[1])), int(table_flags))
+
+
+# ---- training graph of the regressor's other layers (train backend "hip_all", tpspp_regressor_bwd.hip) -----------------
+# Every Linear layer, LayerNorm, gate, softmax, activation and CBAM of the control-point regressor forward and backward on
+# HIP kernels.  The kernels read PyTorch's own parameter layouts (an nn.Linear weight (O, K) is the B operand of
+# `tpspp_mm_f32` as it is), so nothing is prepared from the parameters and nothing can go stale.  A token operand is
+# described as (nb, Mi, sb, si, sk): row r = (q, i) with q < nb, i < Mi, feature k at q*sb + i*si + k*sk -- dense rows
+# are (1, M, 0, K, 1), the tokens of an NCHW map (b c h w -> b (h w) c) are (N, H*W, C*H*W, 1, H*W).
+
+def _i64(*v):
+    import ctypes
+    return (ctypes.c_longlong * len(v))(*v)
+
+
+def _vp(arr):
+    import ctypes
+    return ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _dense(M, K):
+    return (1, M, 0, K, 1)
+
+
+def _nchw_tokens(t):
+    n, c = t.shape[0], t.shape[1]
+    hw = t.numel() // max(1, n * c)
+    return (n, hw, c * hw, 1, hw)
+
+
+def mm(A, a_strides, B, b_strides, C, c_strides, batch, M, N, K, bias=None, R=None, epi=0, alpha=1.0, k_total=0):
+    """`tpspp_mm_f32`: C[b][i][j] = epi(alpha * sum_k A[b][i][k] B[b][j][k] + bias[j]) (+ R[b][i][j]); strides in
+    elements, (batch, row, k) for A / B and (batch, row, column) for C and R.  epi: 0 none, 1 ReLU, 2 GELU, 3 tanh."""
+    sa, sb, sc = _i64(*a_strides), _i64(*b_strides), _i64(*c_strides)
+    _lib.check(_lib.lib().tpspp_mm_f32(batch, M, N, K, _ptr(A), _vp(sa), _ptr(B), _vp(sb), _ptr(C), _vp(sc), _ptr(bias),
+                                       _ptr(R), epi, float(alpha), k_total, _stream(C)), "tpspp_mm_f32")
+    return C
+
+
+def linear_fwd(x, desc, weight, bias=None, epi=0, R=None):
+    """y (rows, O) dense = epi(x W^T + b) (+ R) for the token operand x described by `desc`."""
+    nb, Mi, sb, si, sk = desc
+    O, K = weight.shape
+    y = torch.empty((nb * Mi, O), device=weight.device, dtype=torch.float32)
+    mm(x, (sb, si, sk), weight, (0, K, 1), y, (Mi * O, O, 1), nb, Mi, O, K, bias=bias, R=R, epi=epi)
+    return y
+
+
+def linear_bwd_data(dy, weight, out, desc):
+    """out (token operand `desc`) = dy (rows, O) W; dy dense."""
+    nb, Mi, sb, si, sk = desc
+    O, K = weight.shape
+    mm(dy, (Mi * O, O, 1), weight, (0, 1, K), out, (sb, si, sk), nb, Mi, K, O)
+    return out
+
+
+def linear_bwd_weight_workspace_floats(M, O, K):
+    return int(_lib.lib().tpspp_linear_bwd_weight_workspace_floats(int(M), int(O), int(K)))
+
+
+def linear_bwd_weight(dy, x, desc, O, K, want_weight=True, want_bias=True, x_gelu=False):
+    """(dW (O, K) | None, db (O) | None) of a Linear layer from dy (rows, O) dense and its input x (`desc`), or GELU(x)
+    with x_gelu: `tpspp_linear_bwd_weight`, fixed split-K, bitwise reproducible."""
+    if not (want_weight or want_bias):
+        return None, None
+    nb, Mi, sb, si, sk = desc
+    M = nb * Mi
+    dev = dy.device
+    dw = torch.empty((O, K), device=dev, dtype=torch.float32) if want_weight else None
+    db = torch.empty((O,), device=dev, dtype=torch.float32) if want_bias else None
+    n = linear_bwd_weight_workspace_floats(M, O, K)
+    ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32)
+    lay = _i64(Mi, sb, si, sk)
+    _lib.check(_lib.lib().tpspp_linear_bwd_weight(_ptr(dy), _ptr(x), _vp(lay), 2 if x_gelu else 0, M, O, K, _ptr(dw), _ptr(db), _ptr(ws), n,
+                                                  _stream(dy)), "tpspp_linear_bwd_weight")
+    return dw, db
+
+
+ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2
+
+
+def act_bwd(op, g, t, scale=1.0, out=None):
+    """`tpspp_act_bwd`: g * f'(.) for ReLU (t = output), GELU (t = input) or tanh(scale * u) (t = output, d/du)."""
+    out = torch.empty_like(g) if out is None else out
+    _lib.check(_lib.lib().tpspp_act_bwd(op, g.numel(), _ptr(g), _ptr(t), float(scale), _ptr(out), _stream(g)),
+               "tpspp_act_bwd")
+    return out
+
+
+def plane_ln_fwd(x, weight, bias, eps):
+    """nn.LayerNorm over the last weight.numel() elements: (y, mean, rstd)."""
+    P = weight.numel()
+    rows = x.numel() // P
+    y = torch.empty_like(x)
+    mean = torch.empty((rows,), device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    _lib.check(_lib.lib().tpspp_plane_ln_fwd(_ptr(x), _ptr(weight), _ptr(bias), rows, P, float(eps), _ptr(y), _ptr(mean),
+                                             _ptr(rstd), _stream(x)), "tpspp_plane_ln_fwd")
+    return y, mean, rstd
+
+
+def plane_ln_bwd_workspace_floats(rows, P):
+    return int(_lib.lib().tpspp_plane_ln_bwd_workspace_floats(int(rows), int(P)))
+
+
+def plane_ln_bwd(dy, x, weight, mean, rstd, dx=None, accumulate=False, want_params=True):
+    """Backward of `plane_ln_fwd`: writes (or adds to) dx when given; returns (dweight, dbias) | (None, None)."""
+    P = weight.numel()
+    rows = x.numel() // P
+    dev = x.device
+    dw = db = None
+    n = 0
+    if want_params:
+        dw = torch.empty((P,), device=dev, dtype=torch.float32)
+        db = torch.empty((P,), device=dev, dtype=torch.float32)
+        n = plane_ln_bwd_workspace_floats(rows, P)
+    ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32) if want_params else None
+    if dx is None and not want_params:
+        return None, None
+    _lib.check(_lib.lib().tpspp_plane_ln_bwd(_ptr(dy), _ptr(x), _ptr(weight), _ptr(mean), _ptr(rstd), rows, P, _ptr(dx),
+                                             int(bool(accumulate)), _ptr(dw), _ptr(db), _ptr(ws), n, _stream(x)),
+               "tpspp_plane_ln_bwd")
+    return (dw.view(weight.shape), db.view(weight.shape)) if want_params else (None, None)
+
+
+def _need(ctx, i):
+    return bool(ctx.needs_input_grad[i])
+
+
+class _DgabFunction(torch.autograd.Function):
+    """DGAB (`DGAB.py:58-77`) forward and backward on HIP kernels.  Saves x, y, the gate vectors w / h, x1 = x + attn and
+    both LayerNorms' statistics; xn, A, the norm2 output and fc1's pre-activation are recomputed in the backward (GELU of
+    it inside fc2's weight-gradient staging)."""
+
+    @staticmethod
+    def forward(ctx, x, y, ln1w, ln1b, mww, mhw, pw, pb, ln2w, ln2b, f1w, f1b, f2w, f2b, eps1, eps2):
+        L = _lib.lib()
+        N, C, H, W = x.shape
+        T = y.shape[2]
+        st = _stream(x)
+        xn, m1, r1 = plane_ln_fwd(x, ln1w, ln1b, eps1)
+        catw = torch.empty((N * C, W + T), device=x.device, dtype=torch.float32)
+        cath = torch.empty((N * C, H + T), device=x.device, dtype=torch.float32)
+        _lib.check(L.tpspp_dgab_pool_fwd(_ptr(xn), _ptr(y), N, C, H, W, T, _ptr(catw), _ptr(cath), st), "tpspp_dgab_pool_fwd")
+        wv = linear_fwd(catw, _dense(N * C, W + T), mww)
+        hv = linear_fwd(cath, _dense(N * C, H + T), mhw)
+        A = torch.empty_like(x)
+        _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
+        rows = N * C * H
+        x1 = linear_fwd(A, _dense(rows, W), pw, pb, R=x).view(N, C, H, W)
+        del A, xn, catw, cath
+        x2n, m2, r2 = plane_ln_fwd(x1, ln2w, ln2b, eps2)
+        g = linear_fwd(x2n, _dense(rows, W), f1w, f1b, epi=2)
+        out = linear_fwd(g, _dense(rows, f1w.shape[0]), f2w, f2b, R=x1).view(N, C, H, W)
+        ctx.eps = (eps1, eps2)
+        ctx.save_for_backward(x, y, wv, hv, x1, m1, r1, m2, r2, ln1w, ln1b, mww, mhw, pw, pb, ln2w, ln2b, f1w, f1b, f2w)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        (x, y, wv, hv, x1, m1, r1, m2, r2, ln1w, ln1b, mww, mhw, pw, pb, ln2w, ln2b, f1w, f1b, f2w) = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:14]):
+            return (None,) * 16
+        L = _lib.lib()
+        N, C, H, W = x.shape
+        T = y.shape[2]
+        rows, hid = N * C * H, f1w.shape[0]
+        st = _stream(x)
+        eps1, eps2 = ctx.eps
+        gout = gout.float().contiguous()
+        # ---- mlp (fc1 - GELU - fc2 along W) and norm2; x2n and u recomputed
+        x2n, _, _ = plane_ln_fwd(x1, ln2w, ln2b, eps2)
+        u = linear_fwd(x2n, _dense(rows, W), f1w, f1b)
+        # fc2's input GELU(u) is formed from u as the weight gradient stages it
+        dw_f2, db_f2 = linear_bwd_weight(gout, u, _dense(rows, hid), W, hid, need[12], need[13], x_gelu=True)
+        du = linear_bwd_data(gout, f2w, torch.empty((rows, hid), device=x.device, dtype=torch.float32), _dense(rows, hid))
+        act_bwd(ACT_GELU, du, u, out=du)
+        del u
+        dw_f1, db_f1 = linear_bwd_weight(du, x2n, _dense(rows, W), hid, W, need[10], need[11])
+        dx2n = linear_bwd_data(du, f1w, torch.empty((rows, W), device=x.device, dtype=torch.float32), _dense(rows, W))
+        del du
+        dx1 = gout.clone()
+        dw_ln2, db_ln2 = plane_ln_bwd(dx2n, x1, ln2w, m2, r2, dx=dx1, accumulate=True, want_params=need[8] or need[9])
+        del dx2n, x2n
+        # ---- attention: proj, gate, mlp_w / mlp_h, the pooled means; xn and A recomputed
+        xn, _, _ = plane_ln_fwd(x, ln1w, ln1b, eps1)
+        dw_p = db_p = None
+        if need[6] or need[7]:
+            A = torch.empty_like(x)
+            _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
+            dw_p, db_p = linear_bwd_weight(dx1, A, _dense(rows, W), W, W, need[6], need[7])
+            del A
+        dA = linear_bwd_data(dx1, pw, torch.empty((rows, W), device=x.device, dtype=torch.float32), _dense(rows, W))
+        dxn = torch.empty_like(x)
+        dwv, dhv = torch.empty_like(wv), torch.empty_like(hv)
+        _lib.check(L.tpspp_dgab_gate_bwd(_ptr(dA), _ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(dxn), _ptr(dwv), _ptr(dhv),
+                                         st), "tpspp_dgab_gate_bwd")
+        del dA
+        dw_mw = dw_mh = None
+        if need[4] or need[5]:
+            catw = torch.empty((N * C, W + T), device=x.device, dtype=torch.float32)
+            cath = torch.empty((N * C, H + T), device=x.device, dtype=torch.float32)
+            _lib.check(L.tpspp_dgab_pool_fwd(_ptr(xn), _ptr(y), N, C, H, W, T, _ptr(catw), _ptr(cath), st),
+                       "tpspp_dgab_pool_fwd")
+            dw_mw, _ = linear_bwd_weight(dwv, catw, _dense(N * C, W + T), W + 1, W + T, need[4], False)
+            dw_mh, _ = linear_bwd_weight(dhv, cath, _dense(N * C, H + T), H + 1, H + T, need[5], False)
+            del catw, cath
+        dcatw = linear_bwd_data(dwv, mww, torch.empty((N * C, W + T), device=x.device, dtype=torch.float32),
+                                _dense(N * C, W + T))
+        dcath = linear_bwd_data(dhv, mhw, torch.empty((N * C, H + T), device=x.device, dtype=torch.float32),
+                                _dense(N * C, H + T))
+        dy = torch.empty_like(y) if need[1] else None
+        _lib.check(L.tpspp_dgab_pool_bwd(_ptr(dcatw), _ptr(dcath), N, C, H, W, T, _ptr(dxn), _ptr(dy), st),
+                   "tpspp_dgab_pool_bwd")
+        del dcatw, dcath
+        dx = dx1 if need[0] else None
+        dw_ln1, db_ln1 = plane_ln_bwd(dxn, x, ln1w, m1, r1, dx=dx, accumulate=True, want_params=need[2] or need[3])
+        return (dx, dy, dw_ln1 if need[2] else None, db_ln1 if need[3] else None, dw_mw, dw_mh, dw_p, db_p,
+                dw_ln2 if need[8] else None, db_ln2 if need[9] else None, dw_f1, db_f1, dw_f2, db_f2, None, None)
+
+
+def _lin(m):
+    return m.weight, m.bias
+
+
+def dgab_autograd(x, y, blk):
+    """DGAB `blk` (tps_pp.DGAB) on x (N, C, H, W) and the point map y (N, C, T) (en_feat, flattened), differentiable:
+    `tpspp_plane_ln_*`, `tpspp_dgab_pool_*`, `tpspp_dgab_gate_*`, `tpspp_mm_f32`, `tpspp_linear_bwd_weight`, `tpspp_act_bwd`.
+    The backward honours `needs_input_grad`: no launch for a frozen layer's parameters or an input without a gradient."""
+    x = _chk("dgab_autograd x", x, 4)
+    y = _chk("dgab_autograd y", y, 3)
+    at = blk.attn
+    if at.mlp_w[0].bias is not None or at.mlp_h[0].bias is not None:
+        raise ValueError("dgab_autograd: qkv_bias=True is not supported (the reference builds DGAB without it)")
+    if blk.skip_lam != 1.0:
+        raise ValueError("dgab_autograd: skip_lam must be 1")
+    n1, n2 = blk.norm1, blk.norm2
+    return _DgabFunction.apply(x, y, n1.weight, n1.bias, at.mlp_w[0].weight, at.mlp_h[0].weight, *_lin(at.proj),
+                               n2.weight, n2.bias, *_lin(blk.mlp.fc1), *_lin(blk.mlp.fc2), float(n1.eps), float(n2.eps))
+
+
+class _ScoreFunction(torch.autograd.Function):
+    """The attention score (`tps_pp.py:293-312`): S (N, F, H*W) = tanh(scale * p_linear(en) . feat_linear(de)), the
+    (N, F, n) buffer the warp reads (its (N, n, F) transpose is the reference's pc_score).  Saves the Linear layers'
+    outputs and S."""
+
+    @staticmethod
+    def forward(ctx, de, en, f1w, f1b, f2w, f2b, p1w, p1b, p2w, p2b, scale):
+        N = de.shape[0]
+        dd, de_ = _nchw_tokens(de), _nchw_tokens(en)
+        HW, F, D = dd[1], de_[1], f2w.shape[0]
+        a1 = linear_fwd(de, dd, f1w, f1b)
+        a = linear_fwd(a1, _dense(N * HW, f1w.shape[0]), f2w, f2b)
+        p1 = linear_fwd(en, de_, p1w, p1b)
+        b = linear_fwd(p1, _dense(N * F, p1w.shape[0]), p2w, p2b)
+        S = torch.empty((N, F, HW), device=de.device, dtype=torch.float32)
+        mm(b, (F * D, D, 1), a, (HW * D, D, 1), S, (F * HW, HW, 1), N, F, HW, D, epi=3, alpha=scale)
+        ctx.scale = scale
+        ctx.save_for_backward(de, en, a1, a, p1, b, S, f1w, f2w, p1w, p2w)
+        return S
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gS):
+        de, en, a1, a, p1, b, S, f1w, f2w, p1w, p2w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:10]):
+            return (None,) * 11
+        N = de.shape[0]
+        dd, de_ = _nchw_tokens(de), _nchw_tokens(en)
+        HW, F, D = dd[1], de_[1], f2w.shape[0]
+        dev = de.device
+        dT = act_bwd(ACT_TANH, gS.float().contiguous(), S, ctx.scale)
+        res = [None] * 11
+        if need[0] or any(need[2:6]):
+            da = torch.empty((N * HW, D), device=dev, dtype=torch.float32)
+            mm(dT, (F * HW, 1, HW), b, (F * D, 1, D), da, (HW * D, D, 1), N, HW, D, F)
+            res[4], res[5] = linear_bwd_weight(da, a1, _dense(N * HW, f1w.shape[0]), D, f1w.shape[0], need[4], need[5])
+            da1 = linear_bwd_data(da, f2w, torch.empty((N * HW, f1w.shape[0]), device=dev, dtype=torch.float32),
+                                  _dense(N * HW, f1w.shape[0]))
+            del da
+            res[2], res[3] = linear_bwd_weight(da1, de, dd, f1w.shape[0], f1w.shape[1], need[2], need[3])
+            if need[0]:
+                res[0] = linear_bwd_data(da1, f1w, torch.empty_like(de), dd)
+        if need[1] or any(need[6:10]):
+            db = torch.empty((N * F, D), device=dev, dtype=torch.float32)
+            mm(dT, (F * HW, HW, 1), a, (HW * D, 1, D), db, (F * D, D, 1), N, F, D, HW)
+            res[8], res[9] = linear_bwd_weight(db, p1, _dense(N * F, p1w.shape[0]), D, p1w.shape[0], need[8], need[9])
+            dp1 = linear_bwd_data(db, p2w, torch.empty((N * F, p1w.shape[0]), device=dev, dtype=torch.float32),
+                                  _dense(N * F, p1w.shape[0]))
+            res[6], res[7] = linear_bwd_weight(dp1, en, de_, p1w.shape[0], p1w.shape[1], need[6], need[7])
+            if need[1]:
+                res[1] = linear_bwd_data(dp1, p1w, torch.empty_like(en), de_)
+        return tuple(res)
+
+
+def score_autograd(de_feat, en_feat, tpe):
+    """Differentiable score of `Transformation_Parameter_Estimation` `tpe` on de_feat (N, C, H, W) and en_feat (N, C, h, w):
+    returns the (N, F, H*W) buffer; `.transpose(1, 2)` is the reference's (N, H*W, F) pc_score."""
+    de_feat = _chk("score_autograd de_feat", de_feat, 4)
+    en_feat = _chk("score_autograd en_feat", en_feat, 4)
+    f, p = tpe.feat_linear, tpe.p_linear
+    return _ScoreFunction.apply(de_feat, en_feat, *_lin(f[0]), *_lin(f[1]), *_lin(p[0]), *_lin(p[1]), float(tpe.scale))
+
+
+class _CbamFunction(torch.autograd.Function):
+    """CBAM (`tps_pp.py:27-82`): `tpspp_cbam_train_fwd` / `tpspp_cbam_bwd` (the backward recomputes the gates)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2, cw, cb):
+        N, C, H, W = x.shape
+        Cr = w1.shape[0]
+        out = torch.empty_like(x)
+        ca = torch.empty((N, C), device=x.device, dtype=torch.float32)
+        sa = torch.empty((N, H * W), device=x.device, dtype=torch.float32)
+        _lib.check(_lib.lib().tpspp_cbam_train_fwd(_ptr(x), _ptr(w1), _ptr(w2), _ptr(cw), _ptr(cb), N, C, Cr, H, W, _ptr(out),
+                                                   _ptr(ca), _ptr(sa), _stream(x)), "tpspp_cbam_train_fwd")
+        ctx.save_for_backward(x, w1, w2, cw, cb)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, w1, w2, cw, cb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:5]):
+            return (None,) * 5
+        N, C, H, W = x.shape
+        Cr = w1.shape[0]
+        dev = x.device
+        gout = gout.float().contiguous()
+        dx = torch.empty_like(x)          # the kernel forms dx on the way to the parameter gradients in any case
+        g = [torch.empty(t.shape, device=dev, dtype=torch.float32) if need[i + 1] else None
+             for i, t in enumerate((w1, w2, cw, cb))]
+        n = cbam_bwd_workspace_floats(N, C, Cr)
+        ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32)
+        _lib.check(_lib.lib().tpspp_cbam_bwd(_ptr(gout), _ptr(x), _ptr(w1), _ptr(w2), _ptr(cw), _ptr(cb), N, C, Cr, H, W,
+                                             _ptr(dx), *(_ptr(t) for t in g), _ptr(ws), n, _stream(x)), "tpspp_cbam_bwd")
+        return (dx if need[0] else None, *g)
+
+
+def cbam_bwd_workspace_floats(N, C, Cr):
+    return int(_lib.lib().tpspp_cbam_bwd_workspace_floats(int(N), int(C), int(Cr)))
+
+
+def cbam_autograd(x, mod):
+    """CBAM module `mod` (tps_pp.CBAM) on x (N, C, H, W), differentiable, HIP forward and backward."""
+    x = _chk("cbam_autograd x", x, 4)
+    ca, sa = mod.channel_attention, mod.spatial_attention
+    w1, w2 = ca.shared_MLP[0].weight, ca.shared_MLP[2].weight
+    if ca.shared_MLP[0].bias is not None or ca.shared_MLP[2].bias is not None or tuple(sa.conv2d.kernel_size) != (3, 3):
+        raise ValueError("cbam_autograd: expects the reference's CBAM (bias-free shared MLP, 3x3 spatial conv)")
+    return _CbamFunction.apply(x, w1, w2, sa.conv2d.weight, sa.conv2d.bias)
+
+
+class _TpePointsFunction(torch.autograd.Function):
+    """Control points (`tps_pp.py:321-323`): localization_fc2(relu(fc1b(relu(fc1a(tokens)))).view(N, -1)) on
+    `tpspp_mm_f32`, backward on `tpspp_mm_f32` / `tpspp_linear_bwd_weight` / `tpspp_act_bwd`."""
+
+    @staticmethod
+    def forward(ctx, en, aw, ab, bw, bb, cw, cb):
+        N = en.shape[0]
+        de_ = _nchw_tokens(en)
+        T = de_[1]
+        h1 = linear_fwd(en, de_, aw, ab, epi=1)
+        h2 = linear_fwd(h1, _dense(N * T, aw.shape[0]), bw, bb, epi=1)
+        cp = linear_fwd(h2, _dense(N, T * bw.shape[0]), cw, cb)
+        ctx.save_for_backward(en, h1, h2, aw, bw, cw)
+        return cp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gcp):
+        en, h1, h2, aw, bw, cw = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:7]):
+            return (None,) * 7
+        N = en.shape[0]
+        de_ = _nchw_tokens(en)
+        T = de_[1]
+        Ha, Hb = aw.shape[0], bw.shape[0]
+        dev = en.device
+        gcp = gcp.float().contiguous()
+        res = [None] * 7
+        res[5], res[6] = linear_bwd_weight(gcp, h2, _dense(N, T * Hb), cw.shape[0], T * Hb, need[5], need[6])
+        if need[0] or any(need[1:5]):
+            dh2 = linear_bwd_data(gcp, cw, torch.empty((N, T * Hb), device=dev, dtype=torch.float32), _dense(N, T * Hb))
+            act_bwd(ACT_RELU, dh2, h2, out=dh2)
+            res[3], res[4] = linear_bwd_weight(dh2, h1, _dense(N * T, Ha), Hb, Ha, need[3], need[4])
+            dh1 = linear_bwd_data(dh2, bw, torch.empty((N * T, Ha), device=dev, dtype=torch.float32), _dense(N * T, Ha))
+            act_bwd(ACT_RELU, dh1, h1, out=dh1)
+            res[1], res[2] = linear_bwd_weight(dh1, en, de_, Ha, aw.shape[1], need[1], need[2])
+            if need[0]:
+                res[0] = linear_bwd_data(dh1, aw, torch.empty_like(en), de_)
+        return tuple(res)
+
+
+def tpe_points_autograd(en_feat, tpe):
+    """Differentiable control points of `tpe` from en_feat (N, C, h, w): (N, F, 2)."""
+    en_feat = _chk("tpe_points_autograd en_feat", en_feat, 4)
+    f1, f2 = tpe.localization_fc1, tpe.localization_fc2
+    cp = _TpePointsFunction.apply(en_feat, *_lin(f1[0]), *_lin(f1[2]), *_lin(f2))
+    return cp.view(en_feat.shape[0], tpe.num_fiducial, 2)

@@ -16,7 +16,8 @@ Every stage of `forward` in eval mode runs on the hand-written HIP kernels of li
 In training mode (`module.train()`) the transformation stage still runs on the HIP kernels in both
 directions while the regressor is the plain PyTorch composition of the same layers, so that autograd
 reaches its parameters (logged once); `set_train_backend("hip")` puts its convolutions on the HIP forward / backward
-kernels (tpspp_conv_bwd.hip).  No CPU fallback: CPU tensors raise.
+kernels (tpspp_conv_bwd.hip), `set_train_backend("hip_all")` every layer of it (tpspp_regressor_bwd.hip for CBAM, DGAB,
+the score and the localization FCs).  No CPU fallback: CPU tensors raise.
 """
 import numpy as np
 import torch
@@ -687,15 +688,18 @@ class TPS_PP(nn.Module):
         return (out0, out1, grid) if want_grid else (out0, out1)
 
     # ---- training graph of the regressor's convolutions on the HIP kernels (tpspp_conv_bwd.hip) -------------------
+    TRAIN_BACKENDS = ("torch", "hip", "hip_all")
+
     def set_train_backend(self, mode):
-        """Which kernels the convolutions of the control-point regressor use in the training graph (`.train()`, or
-        eval mode with inputs that carry gradients): "torch" (default) -- the PyTorch composition of the layers, as the
-        reference runs them; "hip" -- every ConvModule on `ops.conv2d_autograd` (HIP forward and backward, the
-        concatenation and nearest upsampling in front of down_feat / k_encoder.0 / k_decoder folded in).  CBAM, DGAB,
-        the TPE layers and the score stay PyTorch in either mode; the warp is `ops.warp_autograd` in both.  Touches
-        neither the parameters, the state_dict nor the eval path."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        """Which kernels the control-point regressor uses in the training graph (`.train()`, or eval mode with inputs
+        that carry gradients): "torch" (default) -- the PyTorch composition of the layers, as the reference runs them;
+        "hip" -- every ConvModule on `ops.conv2d_autograd` (HIP forward and backward, the concatenation and nearest
+        upsampling in front of down_feat / k_encoder.0 / k_decoder folded in), CBAM, DGAB, the TPE layers and the score
+        PyTorch; "hip_all" -- the convolutions as "hip" and every other layer on HIP as well (`ops.cbam_autograd`,
+        `ops.dgab_autograd`, `ops.tpe_points_autograd`, `ops.score_autograd`).  The warp is `ops.warp_autograd` in all
+        three.  Touches neither the parameters, the state_dict nor the eval path."""
+        if mode not in self.TRAIN_BACKENDS:
+            raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
         self._train_backend = mode
         return self
 
@@ -728,10 +732,11 @@ class TPS_PP(nn.Module):
         self.__dict__.pop("_train_cw_cache", None)
         return self
 
-    def _regress_train_hip(self, batch_img, outs):
+    def _regress_train_hip(self, batch_img, outs, all_hip=False):
         """`_regress_torch` with every ConvModule on the HIP forward / backward kernels: the concatenations, the
         `up_sample` in front of down_feat and the decoder's nn.Upsample are folded into the convolutions; the skip
-        additions stay plain tensor adds (the ReLU mask needs each convolution's own output)."""
+        additions stay plain tensor adds (the ReLU mask needs each convolution's own output).  all_hip (train backend
+        "hip_all"): CBAM and the TPE block on the HIP kernels too (`_tpe_train_hip_all`)."""
         cv = self._train_conv
         x, o0, o1 = batch_img.contiguous(), outs[0].contiguous(), outs[1].contiguous()
 
@@ -762,7 +767,7 @@ class TPS_PP(nn.Module):
             k = cv(f"enc{i}", layer, k if i == 0 else [k], layer.conv.stride)
             features.append(k)
         point = features[-1]
-        k = E.atten(point)
+        k = ops.cbam_autograd(point, E.atten) if all_hip else E.atten(point)
         n = len(E.k_decoder)
         for i in range(n):
             up, layer = E.k_decoder[i][0], E.k_decoder[i][1]
@@ -770,8 +775,23 @@ class TPS_PP(nn.Module):
             k = cv(f"dec{i}", layer, [(k, uh, uw)], layer.conv.stride)
             if i < n - 1:
                 k = k + features[n - 2 - i]
-        control_point, atten_score = self.TPE(point, k)
+        control_point, atten_score = self._tpe_train_hip_all(point, k) if all_hip else self.TPE(point, k)
         return control_point, atten_score, feat_grid
+
+    def _tpe_train_hip_all(self, en_feat, de_feat):
+        """Transformation_Parameter_Estimation.forward (`tps_pp.py:315-325`) in the training graph, every layer on HIP:
+        DGAB (`ops.dgab_autograd`), the localization FCs (`ops.tpe_points_autograd`) and the score (`ops.score_autograd`,
+        returned as the transposed view of its (N, F, n) buffer, as the eval path does).  The kernels read the layers'
+        parameters in PyTorch's own layout: nothing is prepared from them, so there is no cache to go stale."""
+        T = self.TPE
+        n, c = en_feat.shape[:2]
+        de = de_feat
+        for blk in T.atten:
+            de = ops.dgab_autograd(de, en_feat.reshape(n, c, -1), blk)
+        control_point = ops.tpe_points_autograd(en_feat, T)
+        if T.without_as:
+            return control_point, torch.zeros((n, de.shape[2] * de.shape[3], T.num_fiducial), device=de.device)
+        return control_point, ops.score_autograd(de, en_feat, T).transpose(1, 2)
 
     def _forward_autograd(self, batch_img, outs):
         """Training graph: the transformation stage runs on the HIP kernels in both
@@ -780,8 +800,9 @@ class TPS_PP(nn.Module):
         on the HIP forward / backward kernels (`set_train_backend("hip")`), so autograd reaches its parameters.  GPU
         tensors only."""
         ops.require_gpu(batch_img, "TPS_PP")
-        if self.train_backend == "hip":
-            control_point, atten_score, feat_grid = self._regress_train_hip(batch_img, outs)
+        if self.train_backend in ("hip", "hip_all"):
+            control_point, atten_score, feat_grid = self._regress_train_hip(batch_img, outs,
+                                                                             all_hip=self.train_backend == "hip_all")
         else:
             control_point, atten_score, feat_grid = self._regress_torch(batch_img, outs)
         at = self.atten_tps
@@ -816,7 +837,12 @@ class TPS_PP(nn.Module):
             # too.  Plain eval inference takes the HIP kernels (they record no autograd graph).
             if not getattr(self, "_logged_autograd", False):
                 import logging
-                if self.train_backend == "hip":
+                if self.train_backend == "hip_all":
+                    logging.getLogger("tps_pp_amd").warning(
+                        "TPS_PP.train(): control-point regressor with every layer on the HIP forward / backward kernels "
+                        "(convolutions, CBAM, DGAB, the localization FCs and the score); warp forward / backward on the HIP "
+                        "kernels. Call .eval() for the all-HIP inference path.")
+                elif self.train_backend == "hip":
                     logging.getLogger("tps_pp_amd").warning(
                         "TPS_PP.train(): control-point regressor with its convolutions on the HIP forward / backward "
                         "kernels (CBAM, DGAB, TPE and the score as PyTorch compositions); warp forward / backward on the "
