@@ -31,14 +31,17 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 7   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 8   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
                                5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
                                6: tpspp_conv2d_bwd_data / _bwd_weight / _bwd_weight_workspace_floats, tpspp_conv2d_prep_weight;
                                7: the regressor's training kernels: tpspp_mm_f32, tpspp_linear_bwd_weight (+ _workspace_floats),
                                   tpspp_act_bwd, tpspp_plane_ln_fwd / _bwd (+ _workspace_floats), tpspp_dgab_pool_fwd / _bwd,
-                                  tpspp_dgab_gate_fwd / _bwd, tpspp_cbam_train_fwd, tpspp_cbam_bwd (+ _workspace_floats) */
+                                  tpspp_dgab_gate_fwd / _bwd, tpspp_cbam_train_fwd, tpspp_cbam_bwd (+ _workspace_floats);
+                               8: the backbone's BatchNorm training kernels: tpspp_bn_train_stats (+ _workspace_floats as
+                                  tpspp_bn_stats_workspace_floats), tpspp_bn_eval_stats, tpspp_bn_apply_fwd, tpspp_bn_bwd_reduce
+                                  (+ _workspace_floats), tpspp_bn_bwd_data */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -429,6 +432,83 @@ size_t tpspp_cbam_bwd_workspace_floats(int N, int C, int Cr);
 int tpspp_cbam_bwd(const float* dout, const float* x, const float* w1, const float* w2, const float* cw, const float* cb,
                    int N, int C, int Cr, int H, int W, float* dx, float* dw1, float* dw2, float* dcw, float* dcb, float* ws,
                    size_t ws_floats, tpspp_stream_t stream);
+
+/*
+ * BatchNorm in training mode, fused with the residual add and the ReLU that follow it (ABI 8; the backbone's train backend
+ * "hip", tpspp_bn_train.hip).  The autograd functions of tps_pp_amd/ops.py (bn_stem_autograd, bn_block_autograd) compose
+ * ResNetABI_v2_large's stem and BasicBlocks from tpspp_conv2d_fwd (relu = 0, weights from tpspp_conv2d_prep_weight), the
+ * entry points below, and tpspp_conv2d_bwd_data / _bwd_weight (relu = 0, dz given as dy).  fp32, NCHW, statistics per
+ * channel over M = N*H*W; N*C*H*W < 2^31, C <= 65535.  REPRODUCIBLE: no atomics; every per-channel reduction is a fixed
+ * split into S = ceil(M / 4096) slices (a function of the sizes alone) whose partials go to the caller's workspace and are
+ * combined in slice order (fp64) by a second launch: results are bitwise identical across calls and streams.
+ */
+
+/* Floats of workspace tpspp_bn_train_stats needs: S * C * 3, S = ceil(N*HW / 4096) (0 for non-positive sizes). */
+size_t tpspp_bn_stats_workspace_floats(int N, int C, int HW);
+
+/*
+ * Batch statistics of z (N, C, HW): mean (C) and rstd (C) = 1 / sqrt(biased var + eps).  Per slice (count, mean, M2), the
+ * slice's mean first and the squared deviations from it second, merged with Chan's formula: no E[z^2] - E[z]^2.
+ * running_mean / running_var (C) or both NULL: updated on the device with PyTorch's rule,
+ *   running_mean = (1 - f) running_mean + f mean,  running_var = (1 - f) running_var + f var M / (M - 1),
+ * f = momentum if momentum >= 0, else 1 / (num_batches_tracked + 1) (momentum=None: the cumulative average); then
+ * num_batches_tracked (one int64, or NULL) += 1 by a launch of its own.  An update needs M >= 2.
+ * replaces: the batch statistics and running-statistics update of nn.BatchNorm2d in .train() (F.batch_norm, training=True)
+ *           at backbones/resnet_v2_large.py:131-135,160-196, layers/conv_layer.py:12-33
+ */
+int tpspp_bn_train_stats(const float* z, int N, int C, int HW, float eps, float momentum, long long* num_batches_tracked,
+                         float* running_mean, float* running_var, float* mean, float* rstd, float* ws, size_t ws_floats,
+                         tpspp_stream_t stream);
+
+/*
+ * The statistics an eval-mode BatchNorm normalises with: mean (C) = running_mean, rstd (C) = 1 / sqrt(running_var + eps).
+ * replaces: nn.BatchNorm2d in .eval() inside a training graph (frozen-BatchNorm fine-tuning)
+ */
+int tpspp_bn_eval_stats(const float* running_mean, const float* running_var, int C, float eps, float* mean, float* rstd,
+                        tpspp_stream_t stream);
+
+/*
+ * y (N, C, HW) = act(gamma_a (za - mean_a) rstd_a + beta_a + r), act = ReLU (relu = 1) or none (0), r by res_mode:
+ *   0 nothing; 1 the tensor `residual` (N, C, HW) (identity shortcut); 2 a second normalised branch
+ *   gamma_b (zb - mean_b) rstd_b + beta_b (downsample shortcut).  Per-channel vectors (C).  One pass.
+ * replaces: relu(bn1(conv1 x)), relu(bn2(conv2 .) + x), relu(bn2(conv2 .) + bn_d(conv_d x)) and the stem's relu(bn(conv x))
+ *           at backbones/resnet_v2_large.py:181-186, layers/conv_layer.py:12-33
+ */
+int tpspp_bn_apply_fwd(const float* za, const float* mean_a, const float* rstd_a, const float* gamma_a, const float* beta_a,
+                       int res_mode, const float* residual, const float* zb, const float* mean_b, const float* rstd_b,
+                       const float* gamma_b, const float* beta_b, int relu, int N, int C, int HW, float* y,
+                       tpspp_stream_t stream);
+
+/* Floats of workspace tpspp_bn_bwd_reduce needs: S * C * 3, S = ceil(N*HW / 4096) (0 for non-positive sizes). */
+size_t tpspp_bn_bwd_reduce_workspace_floats(int N, int C, int HW);
+
+/*
+ * dr = dy [y > 0] (relu = 1; y = the forward's output, as tpspp_conv2d_bwd_data reads it) or dy (relu = 0), and per channel
+ *   sum_dr = sum dr,  sum_dr_xa = sum dr xhat_a,  sum_dr_xb = sum dr xhat_b  (xhat = (z - mean) rstd)
+ * in one pass over dr: the beta gradient and the gamma gradients of branch a and, with zb != NULL, branch b.  Fixed split
+ * as tpspp_bn_train_stats (ws_floats >= tpspp_bn_bwd_reduce_workspace_floats(...), checked).
+ * replaces: the autograd of nn.BatchNorm2d (weight, bias), the residual add and nn.ReLU at backbones/resnet_v2_large.py
+ */
+int tpspp_bn_bwd_reduce(const float* dy, const float* y, int relu, const float* za, const float* mean_a, const float* rstd_a,
+                        const float* zb, const float* mean_b, const float* rstd_b, int N, int C, int HW, float* sum_dr,
+                        float* sum_dr_xa, float* sum_dr_xb, float* ws, size_t ws_floats, tpspp_stream_t stream);
+
+/*
+ * Input gradients of the normalised branches from dr (as tpspp_bn_bwd_reduce forms it) and its sums:
+ *   train_x = 1 (batch statistics):  dz_x = gamma_x rstd_x (dr - sum_dr / M - xhat_x sum_dr_xx / M)
+ *   train_x = 0 (running statistics): dz_x = gamma_x rstd_x dr
+ * for x = a (dza, or NULL) and x = b (dzb, or NULL); xhat recomputed from z, mean, rstd.  sum_dr and sum_dr_xx are read
+ * only for a requested branch with train_x = 1 (required there, checked) and may be NULL when no such branch is asked
+ * for: an eval-mode BatchNorm whose gamma and beta are frozen needs no reduction.  The shortcut's gradient:
+ * dres_mode 1 writes dr to dres, 2 adds it (dres = dres + dr, in that order), 0 leaves dres alone.  With dza = dzb = NULL
+ * and relu = 0 the call is the ordered sum dres + dy.
+ * replaces: the autograd of nn.BatchNorm2d (input), the residual add and nn.ReLU at backbones/resnet_v2_large.py
+ */
+int tpspp_bn_bwd_data(const float* dy, const float* y, int relu, const float* za, const float* mean_a, const float* rstd_a,
+                      const float* gamma_a, const float* sum_dr_xa, int train_a, float* dza, const float* zb,
+                      const float* mean_b, const float* rstd_b, const float* gamma_b, const float* sum_dr_xb, int train_b,
+                      float* dzb, const float* sum_dr, float* dres, int dres_mode, int N, int C, int HW,
+                      tpspp_stream_t stream);
 
 
 

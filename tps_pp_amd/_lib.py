@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
@@ -52,6 +52,15 @@ _SIGNATURES = {
     "tpspp_cbam_train_fwd": ([_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f], _i),
     "tpspp_cbam_bwd_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
     "tpspp_cbam_bwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_bn_stats_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
+    "tpspp_bn_train_stats": ([_f, _i, _i, _i, ctypes.c_float, ctypes.c_float, _f, _f, _f, _f, _f, _f, ctypes.c_size_t, _f],
+                             _i),
+    "tpspp_bn_eval_stats": ([_f, _f, _i, ctypes.c_float, _f, _f, _f], _i),
+    "tpspp_bn_apply_fwd": ([_f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f], _i),
+    "tpspp_bn_bwd_reduce_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
+    "tpspp_bn_bwd_reduce": ([_f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_bn_bwd_data": ([_f, _f, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _f],
+                          _i),
     "tpspp_conv_bf16_chunk_channels": ([_i], _i),
     "tpspp_dgab_fwd": ([_f] * 16 + [_i, _i, _f], _i),
     "tpspp_dgab_bf16_fwd": ([_f] * 16 + [_i, _i, _i, _f], _i),

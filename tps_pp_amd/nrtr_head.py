@@ -606,14 +606,22 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
-    def set_train_backend(self, mode):
+    def set_train_backend(self, mode, backbone=None):
         """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
         "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).
-        No effect on the eval path."""
+        backbone: None leaves the backbone's train backend as it is; "torch" or "hip" sets it as well
+        (ResNetABI_v2_large.set_train_backend).  No effect on the eval path."""
         if mode not in ("torch", "hip", "hip_all"):
             raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
+        if backbone is not None:
+            if backbone not in ("torch", "hip"):
+                raise ValueError(f'set_train_backend: backbone must be None, "torch" or "hip", got {backbone!r}')
+            if not hasattr(self.backbone, "set_train_backend"):
+                raise ValueError(f"set_train_backend: {type(self.backbone).__name__} has no HIP training path")
         if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
             self.tpsnet.set_train_backend(mode)
+        if backbone is not None:
+            self.backbone.set_train_backend(backbone)
         return self
 
     def extract_feat(self, img, test=False, **kwargs):
@@ -626,7 +634,8 @@ class EncodeDecodeRecognizer(nn.Module):
     def forward_train(self, img, img_metas, **kwargs):
         """`EncodeDecodeRecognizer.forward_train` (encode_decode_recognizer.py:131-183): valid ratios, features, targets from
         `img_meta['text']`, encoder, teacher-forced decoder, loss dict.  In `.train()` mode every stage is the PyTorch
-        composition of its layers (gradients reach all parameters) and the TPS++ transformation stage runs on the HIP
+        composition of its layers (gradients reach all parameters) -- the backbone and the TPS++ regressor move onto HIP
+        kernels with set_train_backend(..., backbone="hip") -- and the TPS++ transformation stage runs on the HIP
         kernels forward and backward; the loss is the config's (`TFLoss` / `CELoss`: tps_pp_amd/losses.py)."""
         for img_meta in img_metas:
             img_meta["valid_ratio"] = 1.0 * img_meta["resize_shape"][1] / img.size(-1)

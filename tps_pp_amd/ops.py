@@ -1980,3 +1980,359 @@ def tpe_points_autograd(en_feat, tpe):
     f1, f2 = tpe.localization_fc1, tpe.localization_fc2
     cp = _TpePointsFunction.apply(en_feat, *_lin(f1[0]), *_lin(f1[2]), *_lin(f2))
     return cp.view(en_feat.shape[0], tpe.num_fiducial, 2)
+
+
+# ---- BatchNorm training kernels (tpspp_bn_train.hip): training the backbone on the HIP kernels ---------------------------
+def _bn_dims(who, z):
+    z = _chk(f"{who} z", z, 4)
+    N, C, H, W = z.shape
+    return z, N, C, H * W
+
+
+def _chk_vec(who, name, t, C, dev):
+    t = _chk(f"{who} {name}", t, 1)
+    if t.shape[0] != C or t.device != dev:
+        raise ValueError(f"{who}: {name} must be ({C},) on {dev}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def _chk_like(who, name, t, ref):
+    t = _chk(f"{who} {name}", t, 4)
+    if t.shape != ref.shape or t.device != ref.device:
+        raise ValueError(f"{who}: {name} must be {tuple(ref.shape)} on {ref.device}, got {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def bn_stats_workspace_floats(N, C, HW):
+    """Floats of workspace `bn_train_stats` needs (`tpspp_bn_stats_workspace_floats`): 3 per channel and slice of 4096."""
+    return int(_lib.lib().tpspp_bn_stats_workspace_floats(int(N), int(C), int(HW)))
+
+
+def bn_bwd_reduce_workspace_floats(N, C, HW):
+    """Floats of workspace `bn_bwd_reduce` needs (`tpspp_bn_bwd_reduce_workspace_floats`)."""
+    return int(_lib.lib().tpspp_bn_bwd_reduce_workspace_floats(int(N), int(C), int(HW)))
+
+
+def bn_train_stats(z, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, num_batches_tracked=None):
+    """Batch statistics of a training-mode BatchNorm2d (`tpspp_bn_train_stats`): (mean, rstd) per channel of z (N, C, H, W),
+    rstd = 1 / sqrt(biased var + eps).  With running_mean / running_var they are updated on the device with PyTorch's rule
+    (momentum None: the cumulative average, 1 / num_batches_tracked), and num_batches_tracked (int64) is incremented."""
+    z, N, C, HW = _bn_dims("bn_train_stats", z)
+    dev = z.device
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("bn_train_stats: running_mean and running_var go together")
+    if running_mean is not None:
+        for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+            if not t.is_contiguous():
+                raise ValueError(f"bn_train_stats: {name} must be contiguous (it is updated in place)")
+            _chk_vec("bn_train_stats", name, t, C, dev)
+    if num_batches_tracked is not None:
+        if num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1 or num_batches_tracked.device != dev:
+            raise ValueError("bn_train_stats: num_batches_tracked must be one int64 on z's device")
+    if momentum is None and running_mean is not None and num_batches_tracked is None:
+        raise ValueError("bn_train_stats: momentum=None needs num_batches_tracked")
+    mean = torch.empty((C,), device=dev, dtype=torch.float32)
+    rstd = torch.empty((C,), device=dev, dtype=torch.float32)
+    nws = bn_stats_workspace_floats(N, C, HW)
+    ws = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_train_stats(_ptr(z), N, C, HW, float(eps), -1.0 if momentum is None else float(momentum),
+                                             _ptr(num_batches_tracked), _ptr(running_mean), _ptr(running_var), _ptr(mean),
+                                             _ptr(rstd), _ptr(ws), nws, _stream(z))
+    _lib.check(rc, "tpspp_bn_train_stats")
+    return mean, rstd
+
+
+def bn_eval_stats(running_mean, running_var, eps=1e-5):
+    """(mean, rstd) an eval-mode BatchNorm2d normalises with (`tpspp_bn_eval_stats`): a copy of running_mean and
+    1 / sqrt(running_var + eps)."""
+    rm = _chk("bn_eval_stats running_mean", running_mean, 1)
+    rv = _chk_vec("bn_eval_stats", "running_var", running_var, rm.shape[0], rm.device)
+    mean, rstd = torch.empty_like(rm), torch.empty_like(rm)
+    with torch.cuda.device(rm.device):
+        rc = _lib.lib().tpspp_bn_eval_stats(_ptr(rm), _ptr(rv), rm.shape[0], float(eps), _ptr(mean), _ptr(rstd),
+                                            _stream(rm))
+    _lib.check(rc, "tpspp_bn_eval_stats")
+    return mean, rstd
+
+
+def bn_apply(za, stats_a, gamma_a, beta_a, residual=None, zb=None, stats_b=None, gamma_b=None, beta_b=None, relu=True):
+    """y = relu(gamma_a (za - mean_a) rstd_a + beta_a + r) (`tpspp_bn_apply_fwd`), r = nothing, `residual`, or the second
+    normalised branch gamma_b (zb - mean_b) rstd_b + beta_b.  stats_* = (mean, rstd) from `bn_train_stats` / `bn_eval_stats`."""
+    who = "bn_apply"
+    za, N, C, HW = _bn_dims(who, za)
+    dev = za.device
+    ma, ra = (_chk_vec(who, n, t, C, dev) for n, t in zip(("mean_a", "rstd_a"), stats_a))
+    ga, ba = _chk_vec(who, "gamma_a", gamma_a, C, dev), _chk_vec(who, "beta_a", beta_a, C, dev)
+    if residual is not None and zb is not None:
+        raise ValueError("bn_apply: a residual tensor or a second branch, not both")
+    res_mode, mb = 0, (None,) * 5
+    if residual is not None:
+        res_mode, residual = 1, _chk_like(who, "residual", residual, za)
+    elif zb is not None:
+        res_mode = 2
+        mb = (_chk_like(who, "zb", zb, za),) + tuple(_chk_vec(who, n, t, C, dev) for n, t in
+                                                       zip(("mean_b", "rstd_b", "gamma_b", "beta_b"),
+                                                           (*stats_b, gamma_b, beta_b)))
+    y = torch.empty_like(za)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_apply_fwd(_ptr(za), _ptr(ma), _ptr(ra), _ptr(ga), _ptr(ba), res_mode, _ptr(residual),
+                                           *[_ptr(t) for t in mb], int(bool(relu)), N, C, HW, _ptr(y), _stream(za))
+    _lib.check(rc, "tpspp_bn_apply_fwd")
+    return y
+
+
+def bn_bwd_reduce(dy, y, za, stats_a, zb=None, stats_b=None, relu=True):
+    """Per-channel sums of dr = dy [y > 0] (relu) or dy (`tpspp_bn_bwd_reduce`): (sum dr, sum dr xhat_a, sum dr xhat_b or
+    None) = the beta gradient and the gamma gradients of the branches.  Fixed split, bitwise reproducible."""
+    who = "bn_bwd_reduce"
+    za, N, C, HW = _bn_dims(who, za)
+    dev = za.device
+    dy = _chk_like(who, "dy", dy, za)
+    y = _chk_like(who, "y", y, za) if relu else None
+    ma, ra = (_chk_vec(who, n, t, C, dev) for n, t in zip(("mean_a", "rstd_a"), stats_a))
+    mb = rb = sxb = None
+    if zb is not None:
+        zb = _chk_like(who, "zb", zb, za)
+        mb, rb = (_chk_vec(who, n, t, C, dev) for n, t in zip(("mean_b", "rstd_b"), stats_b))
+        sxb = torch.empty((C,), device=dev, dtype=torch.float32)
+    sdr = torch.empty((C,), device=dev, dtype=torch.float32)
+    sxa = torch.empty((C,), device=dev, dtype=torch.float32)
+    nws = bn_bwd_reduce_workspace_floats(N, C, HW)
+    ws = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_bwd_reduce(_ptr(dy), _ptr(y), int(bool(relu)), _ptr(za), _ptr(ma), _ptr(ra), _ptr(zb),
+                                            _ptr(mb), _ptr(rb), N, C, HW, _ptr(sdr), _ptr(sxa), _ptr(sxb), _ptr(ws), nws,
+                                            _stream(dy))
+    _lib.check(rc, "tpspp_bn_bwd_reduce")
+    return sdr, sxa, sxb
+
+
+def bn_bwd_data(dy, y, za=None, stats_a=None, gamma_a=None, sums=None, train_a=True, zb=None, stats_b=None, gamma_b=None,
+                train_b=True, relu=True, dres=None, dres_mode=0, want_a=True, want_b=None):
+    """Input gradients of the normalised branches (`tpspp_bn_bwd_data`): (dza | None, dzb | None).  sums = `bn_bwd_reduce`'s
+    (sum dr, sum dr xhat_a, sum dr xhat_b); train_* False: an eval-mode BatchNorm (dz = gamma rstd dr).  dres_mode 1 writes
+    dr into `dres`, 2 adds it (the shortcut's gradient); with no branch and relu=False that is the ordered sum dres + dy."""
+    who = "bn_bwd_data"
+    dy = _chk(f"{who} dy", dy, 4)
+    N, C, H, W = dy.shape
+    HW, dev = H * W, dy.device
+    y = _chk_like(who, "y", y, dy) if relu else None
+    want_a = want_a and za is not None
+    want_b = (zb is not None) if want_b is None else (want_b and zb is not None)
+    if sums is None and ((want_a and train_a) or (want_b and train_b)):
+        raise ValueError("bn_bwd_data: a training-mode branch needs the sums of bn_bwd_reduce")
+    sdr, sxa, sxb = sums if sums is not None else (None, None, None)
+    args_a = [None] * 6
+    args_b = [None] * 6
+    dza = dzb = None
+    if want_a:
+        dza = torch.empty_like(dy)
+        args_a = [_chk_like(who, "za", za, dy)] + [_chk_vec(who, n, t, C, dev) for n, t in
+                                                    zip(("mean_a", "rstd_a", "gamma_a"), (*stats_a, gamma_a))]
+        args_a += [_chk_vec(who, "sum_dr_xa", sxa, C, dev) if train_a else None, dza]
+    if want_b:
+        dzb = torch.empty_like(dy)
+        args_b = [_chk_like(who, "zb", zb, dy)] + [_chk_vec(who, n, t, C, dev) for n, t in
+                                                    zip(("mean_b", "rstd_b", "gamma_b"), (*stats_b, gamma_b))]
+        args_b += [_chk_vec(who, "sum_dr_xb", sxb, C, dev) if train_b else None, dzb]
+    if (want_a and train_a) or (want_b and train_b):
+        sdr = _chk_vec(who, "sum_dr", sdr, C, dev)
+    if dres_mode:
+        if not isinstance(dres, torch.Tensor) or not dres.is_contiguous():
+            raise ValueError("bn_bwd_data: dres must be a contiguous tensor (it is written in place)")
+        dres = _chk_like(who, "dres", dres, dy)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_bwd_data(_ptr(dy), _ptr(y), int(bool(relu)), *[_ptr(t) for t in args_a[:5]],
+                                          int(bool(train_a)), _ptr(args_a[5]), *[_ptr(t) for t in args_b[:5]],
+                                          int(bool(train_b)), _ptr(args_b[5]), _ptr(sdr), _ptr(dres), int(dres_mode),
+                                          N, C, HW, _stream(dy))
+    _lib.check(rc, "tpspp_bn_bwd_data")
+    return dza, dzb
+
+
+def _bn_stats_of(z, spec):
+    """(mean, rstd) a BatchNorm normalises z with, by its own mode (spec: `_bn_spec`)."""
+    training, eps, momentum, rm, rv, nbt, name = spec
+    if training:
+        if z.shape[0] * z.shape[2] * z.shape[3] == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {z.shape}")
+        return bn_train_stats(z, eps, momentum, rm, rv, nbt)
+    return bn_eval_stats(rm, rv, eps)
+
+
+def _bn_spec(bn, name):
+    if not isinstance(bn, torch.nn.BatchNorm2d):
+        raise ValueError(f"{name}: expected nn.BatchNorm2d, got {type(bn).__name__}")
+    if not bn.affine or not bn.track_running_stats:
+        raise ValueError(f"{name}: the HIP training path needs BatchNorm2d(affine=True, track_running_stats=True)")
+    return (bool(bn.training), float(bn.eps), bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked, name)
+
+
+def _conv_spec(conv, name, bias_ok=False):
+    """(kernel, stride) of an nn.Conv2d the HIP kernels take: 1x1 / 3x3, 'same' padding, stride 1 or 2, no dilation or groups."""
+    if not isinstance(conv, torch.nn.Conv2d):
+        raise ValueError(f"{name}: expected nn.Conv2d, got {type(conv).__name__}")
+    k = conv.kernel_size[0]
+    st = tuple(int(s) for s in conv.stride)
+    if (conv.kernel_size[1] != k or k not in (1, 3) or tuple(conv.padding) != ((k - 1) // 2,) * 2 or
+            tuple(conv.dilation) != (1, 1) or conv.groups != 1 or conv.padding_mode != "zeros" or
+            any(s not in (1, 2) for s in st) or (conv.bias is not None and not bias_ok)):
+        raise ValueError(f"{name}: the HIP training path takes 1x1 / 3x3 convolutions with 'same' zero padding, stride 1 or 2"
+                         f"{', a bias' if bias_ok else ', no bias'}, no dilation and no groups")
+    return k, st
+
+
+def _chk_gpu(who, x):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{who}: expected a torch.Tensor")
+    if not x.is_cuda:
+        raise _lib.TpsppError(f"{who}: tensor is on {x.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+
+
+class _BnStemFunction(torch.autograd.Function):
+    """y = relu(bn(conv(x) + bias)): HIP forward (`conv2d`, `bn_train_stats` / `bn_eval_stats`, `bn_apply`) and backward
+    (`bn_bwd_reduce`, `bn_bwd_data`, `conv2d_bwd_weight`, `conv2d_bwd_data`).  Saves z, y and the per-channel mean / rstd."""
+
+    @staticmethod
+    def forward(ctx, x, w, cb, g, b, cfg):
+        cw, (k, st), spec = cfg
+        x = x.float().contiguous()
+        z = conv2d([x], cw, st, relu=False)
+        mean, rstd = _bn_stats_of(z, spec)
+        y = bn_apply(z, (mean, rstd), g, b, relu=True)
+        ctx.cfg = (k, st, spec[0], cb is not None)
+        ctx.save_for_backward(x, w, g, z, y, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        k, st, train, has_bias = ctx.cfg
+        x, w, g, z, y, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy = gy.float().contiguous()
+        need_z = need[0] or need[1] or (has_bias and need[2])
+        dx = dw = dcb = dg = db = None
+        sums = (None, None, None)
+        if train or need[3] or need[4]:
+            sums = bn_bwd_reduce(gy, y, z, (mean, rstd), relu=True)
+            dg = sums[1] if need[3] else None
+            db = sums[0] if need[4] else None
+        if need_z:
+            dz, _ = bn_bwd_data(gy, y, z, (mean, rstd), g, sums, train, relu=True)
+            if need[1] or (has_bias and need[2]):
+                dw, dcb = conv2d_bwd_weight([x], dz, k, st, relu=False, want_weight=need[1], want_bias=has_bias and need[2])
+            if need[0]:
+                dx = conv2d_bwd_data(dz, w, [x], st, relu=False)[0]
+        return dx, dw, dcb, dg, db, None
+
+
+def bn_stem_autograd(x, conv, bn, cw=None, name="stem"):
+    """relu(bn(conv(x))) -- ResNetABI_v2_large's stem -- inside an autograd graph on the HIP kernels.  conv: nn.Conv2d
+    (bias allowed); bn: nn.BatchNorm2d, which follows its own mode (.training: batch statistics, running statistics and
+    num_batches_tracked updated on the device; .eval(): running statistics).  cw: the forward's ConvWeight (a cache the
+    caller keys on the parameters' versions), built on the device here if None.  The backward honours
+    `needs_input_grad`."""
+    _chk_gpu(name, x)
+    kst = _conv_spec(conv, f"{name} conv", bias_ok=True)
+    spec = _bn_spec(bn, f"{name} bn")
+    if cw is None:
+        cw = prep_conv_weight_device(conv.weight, conv.bias)
+    return _BnStemFunction.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, (cw, kst, spec))
+
+
+class _BnBlockFunction(torch.autograd.Function):
+    """A BasicBlock, y = relu(bn2(conv2(relu(bn1(conv1 x)))) + shortcut), shortcut = x or bn_d(conv_d x): HIP forward and
+    backward.  Saves z1, h = relu(bn1(z1)), z2, z_d, y and the per-channel mean / rstd of each BatchNorm."""
+
+    @staticmethod
+    def forward(ctx, x, w1, g1, b1, w2, g2, b2, wd, gd, bd, cfg):
+        (cw1, cw2, cwd), (kst1, kst2, kstd), (s1, s2, sd) = cfg
+        x = x.float().contiguous()
+        z1 = conv2d([x], cw1, kst1[1], relu=False)
+        st1 = _bn_stats_of(z1, s1)
+        h = bn_apply(z1, st1, g1, b1, relu=True)
+        z2 = conv2d([h], cw2, kst2[1], relu=False)
+        st2 = _bn_stats_of(z2, s2)
+        if cwd is None:
+            zd, std = None, (None, None)
+            y = bn_apply(z2, st2, g2, b2, residual=x, relu=True)
+        else:
+            zd = conv2d([x], cwd, kstd[1], relu=False)
+            std = _bn_stats_of(zd, sd)
+            y = bn_apply(z2, st2, g2, b2, zb=zd, stats_b=std, gamma_b=gd, beta_b=bd, relu=True)
+        ctx.cfg = (kst1, kst2, kstd, s1[0], s2[0], None if sd is None else sd[0], cwd is not None)
+        ctx.save_for_backward(x, w1, g1, w2, g2, wd, gd, z1, h, z2, zd, y, *st1, *st2, *std)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        kst1, kst2, kstd, t1, t2, td, down = ctx.cfg
+        x, w1, g1, w2, g2, wd, gd, z1, h, z2, zd, y, m1, r1, m2, r2, md, rd = ctx.saved_tensors
+        need = ctx.needs_input_grad       # x, w1, g1, b1, w2, g2, b2, wd, gd, bd
+        gy = gy.float().contiguous()
+        grads = [None] * 11
+        # relu(bn2(z2) + shortcut): the sums of both normalised branches in one pass over dr = gy [y > 0]
+        sdr, sx2, sxd = bn_bwd_reduce(gy, y, z2, (m2, r2), zd, (md, rd) if down else None, relu=True)
+        grads[5] = sx2 if need[5] else None
+        grads[6] = sdr if need[6] else None
+        if down:
+            grads[8] = sxd if need[8] else None
+            grads[9] = sdr.clone() if need[9] else None        # both betas see sum dr; two tensors for two parameters
+        up = need[0] or need[1] or need[2] or need[3]       # anything behind conv2's input h
+        want_d = down and (need[0] or need[7])
+        dz2 = dzd = None
+        if need[4] or up or want_d:
+            dz2, dzd = bn_bwd_data(gy, y, z2, (m2, r2), g2, (sdr, sx2, sxd), t2, zb=zd, stats_b=(md, rd), gamma_b=gd,
+                                   train_b=bool(td), relu=True, want_a=need[4] or up, want_b=want_d)
+        if need[4]:
+            grads[4] = conv2d_bwd_weight([h], dz2, kst2[0], kst2[1], relu=False, want_bias=False)[0]
+        if down and need[7]:
+            grads[7] = conv2d_bwd_weight([x], dzd, kstd[0], kstd[1], relu=False, want_bias=False)[0]
+        if up:
+            dh = conv2d_bwd_data(dz2, w2, [h], kst2[1], relu=False)[0]
+            s1 = bn_bwd_reduce(dh, h, z1, (m1, r1), relu=True)
+            grads[2] = s1[1] if need[2] else None
+            grads[3] = s1[0] if need[3] else None
+            if need[0] or need[1]:
+                dz1, _ = bn_bwd_data(dh, h, z1, (m1, r1), g1, s1, t1, relu=True)
+                if need[1]:
+                    grads[1] = conv2d_bwd_weight([x], dz1, kst1[0], kst1[1], relu=False, want_bias=False)[0]
+                if need[0]:
+                    dx = conv2d_bwd_data(dz1, w1, [x], kst1[1], relu=False)[0]
+                    # + the shortcut's gradient, added in this order: dx = conv1's data gradient + shortcut
+                    if down:
+                        dxd = conv2d_bwd_data(dzd, wd, [x], kstd[1], relu=False)[0]
+                        bn_bwd_data(dxd, None, relu=False, dres=dx, dres_mode=2, want_a=False, want_b=False)
+                    else:
+                        bn_bwd_data(gy, y, relu=True, dres=dx, dres_mode=2, want_a=False, want_b=False)
+                    grads[0] = dx
+        return tuple(grads)
+
+
+def bn_block_autograd(x, blk, cws=None, name="block"):
+    """A BasicBlock (conv1, bn1, conv2, bn2, optional downsample = Sequential(conv, bn)) inside an autograd graph on the HIP
+    kernels: every convolution on `conv2d` / `conv2d_bwd_*` (relu = 0), every BatchNorm + shortcut + ReLU on the
+    tpspp_bn_train.hip kernels.  Each BatchNorm follows its own mode.  cws: the forward's ConvWeights (conv1, conv2,
+    downsample conv or None), built on the device here if None.  The backward honours `needs_input_grad`: no data-gradient
+    launch when x needs none, no weight-gradient launch for a frozen convolution; a frozen BatchNorm still passes its
+    input gradient on."""
+    _chk_gpu(name, x)
+    kst1 = _conv_spec(blk.conv1, f"{name}.conv1")
+    kst2 = _conv_spec(blk.conv2, f"{name}.conv2")
+    s1, s2 = _bn_spec(blk.bn1, f"{name}.bn1"), _bn_spec(blk.bn2, f"{name}.bn2")
+    ds = blk.downsample
+    if ds is not None:
+        if not isinstance(ds, torch.nn.Sequential) or len(ds) != 2:
+            raise ValueError(f"{name}.downsample: the HIP training path takes Sequential(Conv2d, BatchNorm2d)")
+        kstd, sd = _conv_spec(ds[0], f"{name}.downsample.0"), _bn_spec(ds[1], f"{name}.downsample.1")
+        wd, gd, bd = ds[0].weight, ds[1].weight, ds[1].bias
+    else:
+        kstd = sd = wd = gd = bd = None
+    if cws is None:
+        cws = (prep_conv_weight_device(blk.conv1.weight), prep_conv_weight_device(blk.conv2.weight),
+               None if ds is None else prep_conv_weight_device(wd))
+    return _BnBlockFunction.apply(x, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight, blk.bn2.weight,
+                                  blk.bn2.bias, wd, gd, bd, (tuple(cws), (kst1, kst2, kstd), (s1, s2, sd)))

@@ -9,9 +9,12 @@ network invoked before stage index 2 on `(x, outs)` (`:183-191`).
 
 Every convolution runs on the hand-written fp32 MFMA kernel with its BatchNorm folded in and the
 residual add + ReLU fused into the second convolution's epilogue (eval mode, GPU tensors; CPU tensors
-raise: there is no CPU path).  Under `.train()` (round 5) the backbone is the PyTorch composition of its own
-layers so that autograd and BatchNorm's batch statistics work; the TPS++ network it calls keeps its
-transformation stage on the HIP kernels, forward and backward.
+raise: there is no CPU path).  The training graph (`.train()`, or eval mode with an input that carries gradients)
+depends on `set_train_backend`: "torch" (default) -- the PyTorch composition of the backbone's own layers, so that
+autograd and BatchNorm's batch statistics work; "hip" -- the stem and every BasicBlock as once-differentiable functions
+on the HIP kernels (`ops.bn_stem_autograd`, `ops.bn_block_autograd`: the fp32 convolution kernels forward and backward,
+BatchNorm in training mode fused with the residual add and the ReLU in tpspp_bn_train.hip).  The TPS++ network it calls
+trains on whichever backend it was given itself.
 """
 import torch
 import torch.nn as nn
@@ -176,14 +179,66 @@ class ResNetABI_v2_large(nn.Module):
                 self._cw_cache = cache = (key, cw)
             return ops.conv2d([x.float().contiguous()], cache[1], 1, True)
 
+    # ---- training graph on the HIP kernels (tpspp_bn_train.hip + the convolution kernels) ------------------------------
+    TRAIN_BACKENDS = ("torch", "hip")
+
+    def set_train_backend(self, mode):
+        """Which kernels the backbone's training graph (`.train()`, or eval mode with an input that carries gradients) runs
+        on: "torch" (default) -- the PyTorch composition of its layers, as the reference runs them; "hip" -- the stem and
+        every BasicBlock on `ops.bn_stem_autograd` / `ops.bn_block_autograd` (HIP forward and backward; each BatchNorm
+        follows its own mode).  Touches neither the parameters, the buffers, the state_dict nor the eval path."""
+        if mode not in self.TRAIN_BACKENDS:
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")
+
+    def _train_cw(self, name, conv):
+        """The forward's weight layouts of one convolution, cached and rebuilt on the device when its parameters change
+        (data_ptr / _version: an optimiser step, an in-place op, load_state_dict).  An edit through `param.data` is NOT
+        seen: call `invalidate_train_cache()` after one."""
+        w, b = conv.weight, conv.bias
+        key = (w.data_ptr(), w._version) + ((b.data_ptr(), b._version) if b is not None else ())
+        cache = self.__dict__.setdefault("_train_cw_cache", {})
+        ent = cache.get(name)
+        if ent is None or ent[0] != key:
+            ent = cache[name] = (key, ops.prep_conv_weight_device(w, b))
+        return ent[1]
+
+    def invalidate_train_cache(self):
+        """Drop the HIP training path's cached forward weight layouts (needed only after edits through `param.data`)."""
+        self.__dict__.pop("_train_cw_cache", None)
+        return self
+
+    def _forward_train_hip(self, x, tpsnet=None, **kwargs):
+        """`_forward_torch` on the HIP kernels: the same `_run` (stage order, hand-off to `tpsnet`), the stem and each
+        BasicBlock one autograd function."""
+        names = {id(blk): f"{name}.{j}" for name in self.res_layers for j, blk in enumerate(getattr(self, name))}
+
+        def stem(t):
+            return ops.bn_stem_autograd(t, self.conv1, self.bn1, self._train_cw("conv1", self.conv1), name="bn1")
+
+        def block(blk, t, inner):
+            n = names[id(blk)]
+            cws = (self._train_cw(f"{n}.conv1", blk.conv1), self._train_cw(f"{n}.conv2", blk.conv2),
+                   self._train_cw(f"{n}.downsample.0", blk.downsample[0]) if blk.downsample is not None else None)
+            return ops.bn_block_autograd(t, blk, cws, name=n)
+
+        return self._run(x, tpsnet, stem, block, **kwargs)
+
     def forward(self, x, tpsnet=None, test=False, **kwargs):
         """(N, 3, H, W) -> dict(output, img_ref); `tpsnet(x, outs, **kwargs)` runs before stage 2 and
         its 'output' replaces x (`resnet_v2_large.py:183-191`)."""
         ops.require_gpu(x, "ResNetABI_v2_large")
         if self.training or (torch.is_grad_enabled() and x.requires_grad):
-            # training graph (round 5; the reference trains through mmocr/apis/train.py:56-70): the stem and the blocks as
-            # PyTorch compositions of their own layers; `tpsnet` (in .train() mode as well) regresses with PyTorch layers and
-            # runs the transformation stage on the HIP kernels in both directions (tps_pp.TPS_PP._forward_autograd)
+            # training graph (the reference trains through mmocr/apis/train.py:56-70): the stem and the blocks as PyTorch
+            # compositions of their own layers ("torch") or on the HIP kernels ("hip", set_train_backend); `tpsnet`
+            # trains on its own train backend
+            if self.train_backend == "hip":
+                return self._forward_train_hip(x.float(), tpsnet, **kwargs)
             return self._forward_torch(x.float(), tpsnet, **kwargs)
         ops.warn_detached_once(self, "ResNetABI_v2_large")
         if x.dtype == torch.bfloat16 or self.compute_dtype == torch.bfloat16:
