@@ -49,6 +49,41 @@ RAGGED = [
 ]
 CASES = [(n, s, co, k, st, 1, True, 4) for n, s, co, k, st in MODULE_LAYERS] + RAGGED
 
+# Every distinct convolution of ResNetABI_v2_large(strides=[2, 1, 2, 1, 2]) on a 32x128 image -- what the backbone's "hip"
+# train backend sends through these kernels (tests/test_memory_safety_host.py holds the table to a constructed model):
+# several 64-channel tiles (blockIdx.y > 0), a Cout loop of up to 8 x 64, Kf up to 4608, Cin = 3 and the Cout = 32 layers.
+# (name, Cin, Cout, K, stride, H, W, bias)
+BACKBONE_LAYERS = [
+    ("conv1", 3, 32, 3, (1, 1), 32, 128, True),
+    ("layer1.0.conv1", 32, 32, 1, (1, 1), 32, 128, False),
+    ("layer1.0.conv2", 32, 32, 3, (2, 2), 32, 128, False),
+    ("layer1.0.downsample", 32, 32, 1, (2, 2), 32, 128, False),
+    ("layer1.1.conv1", 32, 32, 1, (1, 1), 16, 64, False),
+    ("layer1.1.conv2", 32, 32, 3, (1, 1), 16, 64, False),
+    ("layer2.0.conv1", 32, 64, 1, (1, 1), 16, 64, False),
+    ("layer2.0.conv2", 64, 64, 3, (1, 1), 16, 64, False),
+    ("layer2.1.conv1", 64, 64, 1, (1, 1), 16, 64, False),
+    ("layer3.0.conv1", 64, 128, 1, (1, 1), 16, 64, False),
+    ("layer3.0.conv2", 128, 128, 3, (2, 2), 16, 64, False),
+    ("layer3.0.downsample", 64, 128, 1, (2, 2), 16, 64, False),
+    ("layer3.1.conv1", 128, 128, 1, (1, 1), 8, 32, False),
+    ("layer3.1.conv2", 128, 128, 3, (1, 1), 8, 32, False),
+    ("layer4.0.conv1", 128, 256, 1, (1, 1), 8, 32, False),
+    ("layer4.0.conv2", 256, 256, 3, (1, 1), 8, 32, False),
+    ("layer4.1.conv1", 256, 256, 1, (1, 1), 8, 32, False),
+    ("layer5.0.conv1", 256, 512, 1, (1, 1), 8, 32, False),
+    ("layer5.0.conv2", 512, 512, 3, (2, 2), 8, 32, False),
+    ("layer5.0.downsample", 256, 512, 1, (2, 2), 8, 32, False),
+    ("layer5.1.conv1", 512, 512, 1, (1, 1), 4, 16, False),
+    ("layer5.1.conv2", 512, 512, 3, (1, 1), 4, 16, False),
+]
+# one ragged case with several channel tiles on both sides: odd map, stride (2, 1), Cin and Cout no multiple of 64
+BACKBONE_RAGGED = ("ragged.200to136", 200, 136, 3, (2, 1), 7, 13, True)
+# relu = 0 with dZ handed over as dY is how the backbone calls these layers (the BatchNorm kernels have applied the mask:
+# include/tpspp.h); the ReLU-masked form as well; N = 3 and N = 5
+BACKBONE_CASES = [(f"bb.{n}.N{N}.{'relu' if relu else 'dz'}", [(ci, H, W, 1, 1)], co, k, st, relu, bias, N)
+                  for n, ci, co, k, st, H, W, bias in BACKBONE_LAYERS + [BACKBONE_RAGGED] for N in (3, 5) for relu in (0, 1)]
+
 
 def make(spec, cout, k, bias, N, seed):
     g = torch.Generator().manual_seed(seed)
@@ -88,6 +123,7 @@ def fwd64(srcs, spec, w, b, stride, k, relu):
 def check(name, got, want, bound):
     got = got.detach().cpu().double()
     assert got.shape == want.shape, f"{name}: shape {tuple(got.shape)} vs {tuple(want.shape)}"
+    assert torch.isfinite(got).all(), f"{name}: {int((~torch.isfinite(got)).sum())} non-finite elements"
     err = (got - want).abs()
     bad = err > 4e-6 * bound
     assert not bad.any(), (f"{name}: {int(bad.sum())} elements over the bar, worst err {err.max().item():.3e}, "
@@ -113,7 +149,8 @@ def run_layer(cuda, spec, cout, k, stride, relu, bias, N, seed=0):
                 aw=aw, ab=ab)
 
 
-@pytest.mark.parametrize("name,spec,cout,k,stride,relu,bias,N", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.parametrize("name,spec,cout,k,stride,relu,bias,N", CASES + BACKBONE_CASES,
+                         ids=[c[0] for c in CASES + BACKBONE_CASES])
 def test_layer_gradients_against_float64(cuda, name, spec, cout, k, stride, relu, bias, N):
     r = run_layer(cuda, spec, cout, k, stride, relu, bias, N)
     for i, (g, want, a) in enumerate(zip(r["dx"], r["rx"], r["ax"])):

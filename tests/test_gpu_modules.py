@@ -144,6 +144,7 @@ def test_tpspp_stages_against_reference_intermediates(cuda, mode, tol):
             _, _, _, st2 = m.regress_stages(x, outs)
             w[8, :, 1, 1] = old
         e2 = _stage_errors(st2, G)
+        assert all(np.isfinite(e) for e in e2.values()), (stage, e2)      # a NaN stage error is not "within tol"
         failing = [n for n in STAGE_ORDER if e2[n] > tol]
         assert failing and failing[0] == stage, (stage, e2)
     with torch.no_grad():

@@ -1758,7 +1758,7 @@ class _DgabFunction(torch.autograd.Function):
         dw_f1, db_f1 = linear_bwd_weight(du, x2n, _dense(rows, W), hid, W, need[10], need[11])
         dx2n = linear_bwd_data(du, f1w, torch.empty((rows, W), device=x.device, dtype=torch.float32), _dense(rows, W))
         del du
-        dx1 = gout.clone()
+        dx1 = torch.empty_like(gout).copy_(gout)          # (the kernels below accumulate into it in place)
         dw_ln2, db_ln2 = plane_ln_bwd(dx2n, x1, ln2w, m2, r2, dx=dx1, accumulate=True, want_params=need[8] or need[9])
         del dx2n, x2n
         # ---- attention: proj, gate, mlp_w / mlp_h, the pooled means; xn and A recomputed
