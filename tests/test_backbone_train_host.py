@@ -67,9 +67,15 @@ def test_recognizer_switch_keeps_the_backbone_by_default():
 
 
 def test_cache_invalidation_is_available():
+    from tps_pp_amd._prepared import prepared
     m = small_backbone()
-    m.__dict__["_train_cw_cache"] = {"conv1": None}
-    assert m.invalidate_train_cache() is m and "_train_cw_cache" not in m.__dict__
+    builds = []
+    slot = lambda: prepared(m, ("train", "conv1"), [m.conv1.weight], lambda: builds.append(1))      # noqa: E731
+    slot(), slot()
+    assert len(builds) == 1
+    assert m.invalidate_train_cache() is m and not any("_tpspp_prepared" in x.__dict__ for x in m.modules())
+    slot()
+    assert len(builds) == 2                 # nothing was left cached: the next use rebuilds
 
 
 def _slices(M):

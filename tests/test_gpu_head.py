@@ -11,6 +11,7 @@ import torch.nn.functional as F
 import cases
 from oracle import nrtr_oracle as NO
 from tps_pp_amd import AttnConvertor, NRTRDecoder, NRTREncoder, ops
+from tps_pp_amd._prepared import invalidate_prepared
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -322,7 +323,7 @@ def test_head_argument_errors(cuda):
             with pytest.raises(_lib.TpsppError, match="layer_ptrs_len"):
                 dec(feat, out_enc, None, None, train_mode=False)
         finally:
-            dec._w_cache = None                          # rebuild the table for whoever uses the module next
+            invalidate_prepared(dec)                     # rebuild the table for whoever uses the module next
 
 
 @pytest.mark.parametrize("n,seq", [(37, 6), (64, 40), (557, 5)])

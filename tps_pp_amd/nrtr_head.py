@@ -24,6 +24,7 @@ import torch.nn as nn
 
 from .precision import default_compute_dtype
 from . import ops
+from ._prepared import prepared
 from .registry import (CONVERTORS, DECODERS, DETECTORS, ENCODERS, build_backbone, build_convertor,
                        build_decoder, build_encoder, build_preprocessor)
 
@@ -103,10 +104,6 @@ class TFDecoderLayer(nn.Module):
         self.operation_order = operation_order or _DEC_ORDER
         if tuple(self.operation_order) != _DEC_ORDER:
             raise NotImplementedError("the HIP head implements the default pre-norm operation order only")
-
-
-def _state_key(module):
-    return tuple((t.data_ptr(), t._version) for t in list(module.parameters()) + list(module.buffers()))
 
 
 def _f32(t):
@@ -204,9 +201,7 @@ class NRTREncoder(nn.Module):
     def _weights(self):
         x3 = self.compute_dtype == "bf16x3"
         b16 = self.compute_dtype == torch.bfloat16 or x3
-        key = (_state_key(self), b16, x3)
-        cache = getattr(self, "_w_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             ts = []
             # fp32: k-major (in, out); bf16 / bf16x3 (TPSPP_HEAD_BF16[X3]): arranged for the bf16 1x1 convolution kernel
             km = (lambda w: _arranged16(w, x3)) if b16 else ops.kmajor
@@ -223,9 +218,9 @@ class NRTREncoder(nn.Module):
                        None if a.fc.bias is None else _f32(a.fc.bias), _f32(lyr.norm2.weight), _f32(lyr.norm2.bias),
                        km(lyr.mlp.w_1.weight), _f32(lyr.mlp.w_1.bias), km(lyr.mlp.w_2.weight),
                        _f32(lyr.mlp.w_2.bias)]
-            cache = (key, ops.PtrTable(ts), _f32(self.layer_norm.weight), _f32(self.layer_norm.bias))
-            self._w_cache = cache
-        return cache[1:]
+            return ops.PtrTable(ts), _f32(self.layer_norm.weight), _f32(self.layer_norm.bias)
+
+        return prepared(self, "head", [self], build, (b16, x3))
 
     def _forward_graph(self, feat, img_metas=None):
         """`NRTREncoder.forward` (nrtr_encoder.py:66-87) as a PyTorch composition of this module's layers: the TRAINING
@@ -289,9 +284,7 @@ class NRTRDecoder(nn.Module):
     def _weights(self):
         x3 = self.compute_dtype == "bf16x3"
         b16 = self.compute_dtype == torch.bfloat16
-        key = (_state_key(self), b16, x3)
-        cache = getattr(self, "_w_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             ts = []
             # the token-major step pipeline (tpspp_head.hip) takes these shapes only; for every other one the arranged
             # entries stay NULL and the channel-major step kernels run (no arrangement constraint, no wasted copies)
@@ -300,6 +293,9 @@ class NRTRDecoder(nn.Module):
             # the one-off key / value projections of the encoder output: bf16 both; bf16x3 the keys only
             kk = (lambda w: _arranged16(w, x3)) if (b16 or x3) else ops.kmajor
             kv = _arranged16 if b16 else ops.kmajor
+            # the six per-step projections and the classifier arranged for the step GEMM: fp32 fragments, or split hi / lo
+            # bf16 for the reduced-precision head
+            arr = ops.arrange_x3 if (b16 or x3) else ops.arrange_f32
             for lyr in self.layer_stack:
                 sa, ea = lyr.self_attn, lyr.enc_attn
                 wqkv = torch.cat([ops.kmajor(sa.linear_q.weight), ops.kmajor(sa.linear_k.weight),
@@ -312,18 +308,14 @@ class NRTRDecoder(nn.Module):
                 ts += [qkv[0], qkv[1], qkv[2], wfc, None,
                        q[0], q[1], q[2], kk(ea.linear_k.weight), None, kv(ea.linear_v.weight),
                        wfc2, None, w1[0], w1[1], w1[2], w2, _f32(lyr.mlp.w_2.bias)]
-                # the six per-step projections arranged for the step GEMM: fp32 fragments, or split hi / lo bf16 for the
-                # reduced-precision head
-                arr = ops.arrange_x3 if (b16 or x3) else ops.arrange_f32
                 ts += [arr(t) if fast else None for t in (qkv[0], wfc, q[0], wfc2, w1[0], w2)]
             cls = ops.fold_layernorm(self.layer_norm.weight, self.layer_norm.bias, ops.kmajor(self.classifier.weight),
                                      self.classifier.bias)
             # behind the layers: the classifier
-            ts.append((ops.arrange_x3 if (b16 or x3) else ops.arrange_f32)(cls[0]) if fast else None)
-            cache = (key, ops.PtrTable(ts), _f32(self.trg_word_emb.weight), _f32(self.position_enc.position_table[0]),
-                     cls)
-            self._w_cache = cache
-        return cache[1:]
+            ts.append(arr(cls[0]) if fast else None)
+            return ops.PtrTable(ts), _f32(self.trg_word_emb.weight), _f32(self.position_enc.position_table[0]), cls
+
+        return prepared(self, "head", [self], build, (b16, x3))
 
     def _run(self, out_enc, img_metas, forced):
         ops.require_gpu(out_enc, "NRTRDecoder", torch.is_grad_enabled() and out_enc.requires_grad)

@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from ._prepared import prepared
 from .registry import BACKBONES
 
 
@@ -31,16 +32,13 @@ class NRTRModalityTransform(nn.Module):
         pass
 
     def _weights(self):
-        mods = [self.conv_1, self.bn_1, self.conv_2, self.bn_2, self.linear]
-        key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-        cache = getattr(self, "_cw_cache", None)
-        if cache is None or cache[0] != key:
+        def build():
             def stage(conv, bn):
-                return ops.prep_conv_weight(conv.weight, conv_bias=conv.bias, eps=bn.eps,
-                                            post_bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var))
+                return ops.prep_conv_weight(conv.weight, conv_bias=conv.bias, eps=bn.eps, post_bn=ops.bn_tensors(bn))
             lin = ops.prep_conv_weight(self.linear.weight.view(512, 512, 1, 1), conv_bias=self.linear.bias)
-            self._cw_cache = cache = (key, (stage(self.conv_1, self.bn_1), stage(self.conv_2, self.bn_2), lin))
-        return cache[1]
+            return stage(self.conv_1, self.bn_1), stage(self.conv_2, self.bn_2), lin
+
+        return prepared(self, "conv", [self.conv_1, self.bn_1, self.conv_2, self.bn_2, self.linear], build)
 
     def forward(self, x):
         ops.require_gpu(x, "NRTRModalityTransform")

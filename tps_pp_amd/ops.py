@@ -4,6 +4,8 @@ Each function mirrors one PyTorch call site of the reference (cited in the docst
 device pointers + the current HIP stream to libtpspp_hip.so.  Inputs must be fp32 CUDA(HIP) tensors;
 anything else raises -- there is no eager / CPU fallback on purpose.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -17,14 +19,34 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
-def _chk(name, t, ndim=None):
+def _vp(arr):
+    return ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _ptr_array(objs):
+    """Host array of the device pointers of `objs` (None: NULL); `_vp` of it is what a `T* const*` argument takes."""
+    return (ctypes.c_void_p * len(objs))(*[None if o is None else o.data_ptr() for o in objs])
+
+
+def _int_array(values, ctype=ctypes.c_int):
+    return (ctype * len(values))(*values)
+
+
+def _chk_gpu(who, t):
     if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor")
+        raise TypeError(f"{who}: expected a torch.Tensor")
     if not t.is_cuda:
-        raise _lib.TpsppError(f"{name}: tensor is on {t.device}; the HIP path needs a GPU tensor "
-                              "(no CPU fallback)")
-    if t.dtype != torch.float32:
-        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+        raise _lib.TpsppError(f"{who}: tensor is on {t.device}; the HIP path needs a GPU tensor (no CPU fallback)")
+
+
+_F32 = (torch.float32,)
+_F32_BF16 = (torch.float32, torch.bfloat16)         # what the bf16 paths take
+
+
+def _chk(name, t, ndim=None, dtypes=_F32):
+    _chk_gpu(name, t)
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name}: expected {' or '.join(str(d)[6:] for d in dtypes)}, got {t.dtype}")
     if ndim is not None and t.dim() != ndim:
         raise ValueError(f"{name}: expected {ndim} dims, got {tuple(t.shape)}")
     return t.contiguous()
@@ -32,9 +54,7 @@ def _chk(name, t, ndim=None):
 
 def require_gpu(t, who, training=False):
     """Module forwards call this first: the product has no CPU path and no library-kernel path."""
-    if not t.is_cuda:
-        raise _lib.TpsppError(f"{who}: tensor is on {t.device}; the HIP path needs a GPU tensor "
-                              "(no CPU fallback)")
+    _chk_gpu(who, t)
     if training:
         raise NotImplementedError(f"{who} (HIP path) is forward-only: call .eval() and run under "
                                   "torch.no_grad() (SURVEY.md section 8f, row F2)")
@@ -183,6 +203,87 @@ def table_mirror_symmetry(P_hat_host, out_hw, F):
                                                       int(out_hw[1]), int(F)))
 
 
+def _chk_score(who, score, N, n, F):
+    """(N, n, F) as the reference produces it, or a transposed VIEW of an (N, F, n) buffer: the latter is what lets lanes
+    that own consecutive pixels read the score coalesced.  -> (the contiguous buffer, SCORE_TRANSPOSED | 0)."""
+    if not isinstance(score, torch.Tensor) or tuple(score.shape) != (N, n, F):
+        raise ValueError(f"{who}: score must be (N, n, F)")
+    if score.stride() == (F * n, 1, n) and n > 1 and F > 1:
+        return _chk("score", score.transpose(1, 2), 3), SCORE_TRANSPOSED      # the underlying (N, F, n) buffer
+    return _chk("score", score, 3), 0
+
+
+def _warp_call(who, in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, out0, out1, P_hat_t, table_flags,
+               want_grid=False, want_idx=False):
+    """The checks of one `tpspp_warp_fwd` call, for `warp` and `WarpPlan` (who): -> (the checked tensors, in argument
+    order, that must outlive the launch; the final table_flags; the argument tuple).  `warp` takes bfloat16 images
+    (TPSPP_IO_BF16: T, grid and interpolation stay fp32) and allocates the outputs it is not given; a plan is fp32 and works
+    on its caller's buffers."""
+    plan = who == "WarpPlan"
+    table_flags = int(table_flags)
+    io_dtype = torch.float32
+    if not plan and isinstance(in0, torch.Tensor) and in0.dtype == torch.bfloat16:
+        if in1 is not None and in1.dtype != torch.bfloat16:
+            raise TypeError("warp: in0 and in1 must share their dtype")
+        io_dtype = torch.bfloat16
+        table_flags |= IO_BF16
+    io = _F32_BF16 if io_dtype == torch.bfloat16 else _F32
+    in0, ctrl = _chk("in0", in0, 4, io), _chk("ctrl", ctrl, 3)
+    inv_delta_C, P_hat = _chk("inv_delta_C", inv_delta_C, 2), _chk("P_hat", P_hat, 2)
+    N, C0, H0, W0 = in0.shape
+    F = int(ctrl.shape[1])
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    n = Ho * Wo
+    bad_ctrl, bad_inv = ctrl.shape[0] != N or ctrl.shape[2] != 2, tuple(inv_delta_C.shape) != (F + 3, F + 3)
+    if plan and (bad_ctrl or bad_inv):
+        raise ValueError("WarpPlan: ctrl must be (N, F, 2), inv_delta_C (F+3, F+3)")
+    if bad_ctrl:
+        raise ValueError("warp: ctrl must be (N, F, 2)")
+    if bad_inv:
+        raise ValueError("warp: inv_delta_C must be (F+3, F+3)")
+    if P_xy is not None:
+        P_xy = _chk("P_xy", P_xy, 2)
+        if tuple(P_xy.shape) != (n, 2):
+            raise ValueError(f"{who}: P_xy must be (n, 2)")
+    if tuple(P_hat.shape) != (n, F if P_xy is not None else F + 3):
+        raise ValueError(f"{who}: P_hat has shape {tuple(P_hat.shape)}")
+    if score is not None:
+        score, transposed = _chk_score(who, score, N, n, F)
+        table_flags |= transposed
+    if P_hat_t is not None:
+        P_hat_t = _chk_table(who, P_hat, P_hat_t, n, (Ho, Wo), table_flags)
+    elif table_flags & TABLE_PACKED:
+        raise ValueError(f"{who}: TABLE_PACKED without P_hat_t")
+    dev = in0.device
+    if out0 is None and not plan:
+        out0 = torch.empty((N, C0, Ho, Wo), device=dev, dtype=io_dtype)
+    C1 = H1 = W1 = 0
+    if in1 is not None:
+        in1 = _chk("in1", in1, 4, io)
+        _, C1, H1, W1 = in1.shape
+        if plan and (in1.shape[0] != N or in1.device != dev):
+            raise ValueError("WarpPlan: in1 must have in0's batch size and device")
+        if in1.shape[0] != N:
+            raise ValueError("warp: in1 batch mismatch")
+        if in1.device != dev:
+            raise ValueError("warp: in1 must be on in0's device")
+        if out1 is None and not plan:
+            out1 = torch.empty((N, C1, Ho, Wo), device=dev, dtype=io_dtype)
+        _chk_out(who, "out1", out1, (N, C1, Ho, Wo), io_dtype, dev)
+    elif out1 is not None:
+        raise ValueError(f"{who}: out1 given without in1")
+    _chk_out(who, "out0", out0, (N, C0, Ho, Wo), io_dtype, dev)
+    for nm, t in (("ctrl", ctrl), ("inv_delta_C", inv_delta_C), ("P_hat", P_hat), ("P_xy", P_xy), ("score", score)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"{who}: {nm} must be on in0's device")
+    grid = torch.empty((N, n, 2), device=dev, dtype=torch.float32) if want_grid else None
+    idx = torch.empty((N, n, 2), device=dev, dtype=torch.int32) if want_idx else None
+    args = (_ptr(in0), C0, H0, W0, _ptr(in1), C1, H1, W1, _ptr(ctrl), _ptr(score), _ptr(inv_delta_C), _ptr(P_hat),
+            P_hat.shape[1], _ptr(P_xy), _ptr(P_hat_t), table_flags, N, F, Ho, Wo, _ptr(out0), _ptr(out1), _ptr(grid),
+            _ptr(idx), _stream(in0))
+    return (in0, in1, ctrl, score, inv_delta_C, P_hat, P_xy, P_hat_t, out0, out1, grid, idx), table_flags, args
+
+
 def warp(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None,
          want_grid=False, want_idx=False, out0=None, out1=None, P_hat_t=None, table_flags=0):
     """Fused build_P_prime + grid_sample(s): one kernel, T in LDS, grid in registers.
@@ -191,77 +292,13 @@ def warp(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None,
     classic:  in0 = image, P_hat = GridGenerator.P_hat (n, F+3)     (tps_preprocessor.py:71-83)
     TPS_PP :  in0 = feat_grid, in1 = x, P_hat (n, F) + P_xy (n, 2) + score (N, n, F)
                                                                      (tps_pp.py:597-615)
-    """
-    io16 = isinstance(in0, torch.Tensor) and in0.dtype == torch.bfloat16
-    if io16:          # bf16 images in and out (TPSPP_IO_BF16): T, grid and interpolation stay fp32
-        if in1 is not None and in1.dtype != torch.bfloat16:
-            raise TypeError("warp: in0 and in1 must share their dtype")
-        in0 = _chk16("in0", in0, 4)
-        table_flags = int(table_flags) | IO_BF16
-    else:
-        in0 = _chk("in0", in0, 4)
-    io_dtype = torch.bfloat16 if io16 else torch.float32
-    ctrl = _chk("ctrl", ctrl, 3)
-    inv_delta_C, P_hat = _chk("inv_delta_C", inv_delta_C, 2), _chk("P_hat", P_hat, 2)
-    N, C0, H0, W0 = in0.shape
-    F = int(ctrl.shape[1])
-    Ho, Wo = int(out_hw[0]), int(out_hw[1])
-    n = Ho * Wo
-    if ctrl.shape[0] != N or ctrl.shape[2] != 2:
-        raise ValueError("warp: ctrl must be (N, F, 2)")
-    if tuple(inv_delta_C.shape) != (F + 3, F + 3):
-        raise ValueError("warp: inv_delta_C must be (F+3, F+3)")
-    if P_xy is not None:
-        P_xy = _chk("P_xy", P_xy, 2)
-        if tuple(P_xy.shape) != (n, 2):
-            raise ValueError("warp: P_xy must be (n, 2)")
-    if tuple(P_hat.shape) != (n, F if P_xy is not None else F + 3):
-        raise ValueError(f"warp: P_hat has shape {tuple(P_hat.shape)}")
-    if score is not None:
-        # (N, n, F) as the reference produces it, or a transposed VIEW of an (N, F, n) buffer: the
-        # latter is what lets lanes that own consecutive pixels read the score coalesced
-        if not isinstance(score, torch.Tensor) or score.dim() != 3 or tuple(score.shape) != (N, n, F):
-            raise ValueError("warp: score must be (N, n, F)")
-        if score.stride() == (F * n, 1, n) and n > 1 and F > 1:
-            table_flags = int(table_flags) | SCORE_TRANSPOSED
-            score = _chk("score", score.transpose(1, 2), 3)      # the underlying (N, F, n) buffer
-        else:
-            score = _chk("score", score, 3)
-    if P_hat_t is not None:
-        P_hat_t = _chk_table("warp", P_hat, P_hat_t, n, (Ho, Wo), table_flags)
-    elif int(table_flags) & TABLE_PACKED:
-        raise ValueError("warp: TABLE_PACKED without P_hat_t")
-    C1 = H1 = W1 = 0
-    if in1 is not None:
-        in1 = _chk16("in1", in1, 4) if io16 else _chk("in1", in1, 4)
-        if in1.shape[0] != N:
-            raise ValueError("warp: in1 batch mismatch")
-        _, C1, H1, W1 = in1.shape
-    dev = in0.device
-    if out0 is None:
-        out0 = torch.empty((N, C0, Ho, Wo), device=dev, dtype=io_dtype)
-    if in1 is not None and out1 is None:
-        out1 = torch.empty((N, C1, Ho, Wo), device=dev, dtype=io_dtype)
-    _chk_out("warp", "out0", out0, (N, C0, Ho, Wo), io_dtype, dev)
-    if in1 is not None:
-        if in1.device != dev:
-            raise ValueError("warp: in1 must be on in0's device")
-        _chk_out("warp", "out1", out1, (N, C1, Ho, Wo), io_dtype, dev)
-    elif out1 is not None:
-        raise ValueError("warp: out1 given without in1")
-    for nm, t in (("ctrl", ctrl), ("inv_delta_C", inv_delta_C), ("P_hat", P_hat), ("P_xy", P_xy), ("score", score)):
-        if t is not None and t.device != dev:
-            raise ValueError(f"warp: {nm} must be on in0's device")
-    grid = torch.empty((N, n, 2), device=dev, dtype=torch.float32) if want_grid else None
-    idx = torch.empty((N, n, 2), device=dev, dtype=torch.int32) if want_idx else None
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_warp_fwd(_ptr(in0), C0, H0, W0, _ptr(in1), C1, H1, W1, _ptr(ctrl),
-                                       _ptr(score), _ptr(inv_delta_C), _ptr(P_hat), P_hat.shape[1],
-                                       _ptr(P_xy), _ptr(P_hat_t), int(table_flags), N, F, Ho, Wo,
-                                       _ptr(out0), _ptr(out1),
-                                       _ptr(grid), _ptr(idx), _stream(in0))
+    bfloat16 in0 / in1 give bfloat16 outputs (TPSPP_IO_BF16)."""
+    keep, _, args = _warp_call("warp", in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, out0, out1, P_hat_t,
+                               table_flags, want_grid, want_idx)
+    with torch.cuda.device(keep[0].device):
+        rc = _lib.lib().tpspp_warp_fwd(*args)
     _lib.check(rc, "tpspp_warp_fwd")
-    return out0, out1, grid, idx
+    return keep[8:]
 
 
 class WarpPlan:
@@ -274,56 +311,10 @@ class WarpPlan:
 
     def __init__(self, in0, ctrl, inv_delta_C, P_hat, out_hw, out0, P_xy=None, score=None, in1=None, out1=None,
                  P_hat_t=None, table_flags=0):
-        import ctypes
-        in0, ctrl = _chk("in0", in0, 4), _chk("ctrl", ctrl, 3)
-        inv_delta_C, P_hat = _chk("inv_delta_C", inv_delta_C, 2), _chk("P_hat", P_hat, 2)
-        N, C0, H0, W0 = in0.shape
-        F = int(ctrl.shape[1])
-        Ho, Wo = int(out_hw[0]), int(out_hw[1])
-        n = Ho * Wo
-        if ctrl.shape[0] != N or ctrl.shape[2] != 2 or tuple(inv_delta_C.shape) != (F + 3, F + 3):
-            raise ValueError("WarpPlan: ctrl must be (N, F, 2), inv_delta_C (F+3, F+3)")
-        if P_xy is not None:
-            P_xy = _chk("P_xy", P_xy, 2)
-            if tuple(P_xy.shape) != (n, 2):
-                raise ValueError("WarpPlan: P_xy must be (n, 2)")
-        if tuple(P_hat.shape) != (n, F if P_xy is not None else F + 3):
-            raise ValueError(f"WarpPlan: P_hat has shape {tuple(P_hat.shape)}")
-        if score is not None:
-            if tuple(score.shape) != (N, n, F):
-                raise ValueError("WarpPlan: score must be (N, n, F)")
-            if score.stride() == (F * n, 1, n) and n > 1 and F > 1:
-                table_flags = int(table_flags) | SCORE_TRANSPOSED
-                score = _chk("score", score.transpose(1, 2), 3)
-            else:
-                score = _chk("score", score, 3)
-        if P_hat_t is not None:
-            P_hat_t = _chk_table("WarpPlan", P_hat, P_hat_t, n, (Ho, Wo), table_flags)
-        elif int(table_flags) & TABLE_PACKED:
-            raise ValueError("WarpPlan: TABLE_PACKED without P_hat_t")
-        dev = in0.device
-        C1 = H1 = W1 = 0
-        if in1 is not None:
-            in1 = _chk("in1", in1, 4)
-            _, C1, H1, W1 = in1.shape
-            if in1.shape[0] != N or in1.device != dev:
-                raise ValueError("WarpPlan: in1 must have in0's batch size and device")
-            _chk_out("WarpPlan", "out1", out1, (N, C1, Ho, Wo), torch.float32, dev)
-        elif out1 is not None:
-            raise ValueError("WarpPlan: out1 given without in1")
-        _chk_out("WarpPlan", "out0", out0, (N, C0, Ho, Wo), torch.float32, dev)
-        for nm, t in (("ctrl", ctrl), ("inv_delta_C", inv_delta_C), ("P_hat", P_hat), ("P_xy", P_xy), ("score", score)):
-            if t is not None and t.device != dev:
-                raise ValueError(f"WarpPlan: {nm} must be on in0's device")
-        self._keep = (in0, in1, ctrl, score, inv_delta_C, P_hat, P_xy, P_hat_t, out0, out1)
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        self._args = (vp(_ptr(in0)), ci(C0), ci(H0), ci(W0), vp(_ptr(in1)), ci(C1), ci(H1), ci(W1), vp(_ptr(ctrl)),
-                      vp(_ptr(score)), vp(_ptr(inv_delta_C)), vp(_ptr(P_hat)), ci(P_hat.shape[1]), vp(_ptr(P_xy)),
-                      vp(_ptr(P_hat_t)), ci(int(table_flags)), ci(N), ci(F), ci(Ho), ci(Wo), vp(_ptr(out0)),
-                      vp(_ptr(out1)), vp(0), vp(0), vp(_stream(in0)))
-        self._fn = _lib.lib().tpspp_warp_fwd
+        self._keep, _, self._args = _warp_call("WarpPlan", in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, out0,
+                                               out1, P_hat_t, table_flags)
         self.out0, self.out1 = out0, out1
-        self._dev = in0.device
+        self._dev = self._keep[0].device
         # round 6: the arguments live on the library's side (tpspp_warp_plan_create); run() hands over one pointer instead of
         # marshalling 25 arguments per launch (1.6 of ~4.3 us of host time per call)
         L = _lib.lib()
@@ -343,7 +334,6 @@ class WarpPlan:
         """One launch on the stream that was current when the plan was built; pass `stream` (a torch.cuda.Stream)
         to launch on another one (the caller orders the buffers' producers / consumers on it)."""
         if stream is not None:
-            import ctypes
             rc = self._run_on(self._handle, ctypes.c_void_p(stream.cuda_stream))
         else:
             rc = self._run(self._handle)
@@ -361,11 +351,15 @@ class ConvWeight:
         self.post_scale, self.post_shift = post_scale, post_shift
 
 
-def prep_conv_weight(weight, bn=None, conv_bias=None, eps=1e-5, src_channels=None, post_bn=None):
-    """PyTorch conv weight (Cout, Cin, KH, KW) [+ eval-mode BatchNorm (gamma, beta, mean, var), folded:
-    y = gamma * (conv(x) + b - mean) / sqrt(var + eps) + beta] -> ConvWeight.
-    `src_channels`: channel counts of the concatenated sources (chunks never straddle a source).
-    `post_bn`: a BatchNorm that FOLLOWS the activation (applied as a per-channel affine in the epilogue)."""
+def bn_tensors(bn):
+    """(gamma, beta, mean, var) of an nn.BatchNorm2d, as the `bn` / `post_bn` arguments of `prep_conv_weight[_bf16]`."""
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var
+
+
+def _fold_bn(weight, bn, conv_bias, eps, post_bn):
+    """fp32 (w, b | None, post_scale | None, post_shift | None): an eval-mode BatchNorm (gamma, beta, mean, var) folded
+    into the convolution, y = gamma * (conv(x) + b - mean) / sqrt(var + eps) + beta; `post_bn`: a BatchNorm that FOLLOWS
+    the activation, as the per-channel affine of the epilogue."""
     w = weight.detach().float()
     b = None if conv_bias is None else conv_bias.detach().float()
     if bn is not None:
@@ -373,6 +367,26 @@ def prep_conv_weight(weight, bn=None, conv_bias=None, eps=1e-5, src_channels=Non
         scale = gamma / torch.sqrt(var + eps)
         w = w * scale.view(-1, 1, 1, 1)
         b = beta - mean * scale if b is None else beta + (b - mean) * scale
+    ps = pb = None
+    if post_bn is not None:
+        gamma, beta, mean, var = (t.detach().float() for t in post_bn)
+        ps = (gamma / torch.sqrt(var + eps)).contiguous()
+        pb = (beta - mean * ps).contiguous()
+    return w, None if b is None else b.contiguous(), ps, pb
+
+
+def _hi_lo(w):
+    """The two bf16 terms of the three-term split ("bf16x3") of an fp32 weight: hi = bf16(w), lo = bf16(w - hi)."""
+    hi = w.to(torch.bfloat16)
+    return hi, (w - hi.float()).to(torch.bfloat16)
+
+
+def prep_conv_weight(weight, bn=None, conv_bias=None, eps=1e-5, src_channels=None, post_bn=None):
+    """PyTorch conv weight (Cout, Cin, KH, KW) [+ eval-mode BatchNorm (gamma, beta, mean, var), folded: `_fold_bn`]
+    -> ConvWeight.
+    `src_channels`: channel counts of the concatenated sources (chunks never straddle a source).
+    `post_bn`: a BatchNorm that FOLLOWS the activation (applied as a per-channel affine in the epilogue)."""
+    w, b, ps, pb = _fold_bn(weight, bn, conv_bias, eps, post_bn)
     cout, cin, kh, kw = w.shape
     wt = w.reshape(cout, -1).t().contiguous()
     kc = int(_lib.lib().tpspp_conv_chunk_channels(int(kh)))
@@ -383,28 +397,44 @@ def prep_conv_weight(weight, bn=None, conv_bias=None, eps=1e-5, src_channels=Non
         wp[:, :cin] = w
         # (cout, chunk, ci, ky, kx) -> (chunk, ky, kx, ci, cout)
         tiled = wp.view(cout, nch, kc, kh, kw).permute(1, 3, 4, 2, 0).contiguous()
-    ps = pb = None
-    if post_bn is not None:
-        gamma, beta, mean, var = (t.detach().float() for t in post_bn)
-        ps = (gamma / torch.sqrt(var + eps)).contiguous()
-        pb = (beta - mean * ps).contiguous()
-    return ConvWeight(wt, tiled, None if b is None else b.contiguous(), kh, ps, pb)
+    return ConvWeight(wt, tiled, b, kh, ps, pb)
 
 
-def _chk_conv_sources(who, ts, dims, stride_of_dims):
-    """Every source reaches the kernel as a raw pointer with only its (C, H, W, uh, uw): batch size, device and the
-    shared logical size (H*uh, W*uw) are checked here."""
+def _split_sources(srcs):
+    """srcs entries `map` or `(map, uh, uw)` -> [(map, uh, uw)]."""
+    return [tuple(e) if isinstance(e, (tuple, list)) else (e, 1, 1) for e in srcs]
+
+
+def _conv_sources(who, srcs, label="conv source", layouts=False):
+    """The sources of one convolution -> (contiguous tensors, flat src_dims, N, device, Hi, Wi).  src_dims holds
+    {C, H, W, uh, uw} per source; layouts (the bf16 form): float32 / bfloat16 NCHW tensors and `Blocked` maps, with the
+    layout code as a sixth entry.  Every source reaches the kernel as a raw pointer with only those numbers: batch size,
+    device and the shared logical size (H*uh, W*uw) are checked here."""
+    ts, dims = [], []
+    for t, uh, uw in _split_sources(srcs):
+        code = [_layout_code(t)] if layouts else []
+        t = _BlkView(t) if layouts and isinstance(t, Blocked) else _chk(label, t, 4, _F32_BF16 if layouts else _F32)
+        ts.append(t)
+        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw)] + code
+    per = 6 if layouts else 5
     N, dev = ts[0].shape[0], ts[0].device
     Hi, Wi = ts[0].shape[2] * dims[3], ts[0].shape[3] * dims[4]
     for i, t in enumerate(ts):
-        d = dims[stride_of_dims * i: stride_of_dims * (i + 1)]
+        uh, uw = dims[per * i + 3], dims[per * i + 4]
         if t.shape[0] != N or t.device != dev:
             raise ValueError(f"{who}: source {i} must have the first source's batch size and device")
-        if d[3] < 1 or d[4] < 1 or (t.shape[2] * d[3], t.shape[3] * d[4]) != (Hi, Wi):
+        if uh < 1 or uw < 1 or (t.shape[2] * uh, t.shape[3] * uw) != (Hi, Wi):
             raise ValueError(f"{who}: source {i} does not have the shared logical size {(Hi, Wi)}")
     if not 1 <= len(ts) <= 3:
         raise ValueError(f"{who}: 1..3 sources")
-    return N, dev, Hi, Wi
+    return ts, dims, N, dev, Hi, Wi
+
+
+def _conv_out_size(Hi, Wi, kernel, stride):
+    """(sh, sw, Ho, Wo) of a "same"-padded convolution."""
+    sh, sw = (stride, stride) if isinstance(stride, int) else stride
+    pad = (kernel - 1) // 2
+    return sh, sw, (Hi + 2 * pad - kernel) // sh + 1, (Wi + 2 * pad - kernel) // sw + 1
 
 
 def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=None):
@@ -413,19 +443,9 @@ def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=No
     srcs: list of 1..3 entries `tensor` or `(tensor, uh, uw)`: channel-concatenated, each nearest-
     upsampled by (uh, uw) on the fly.  cw: ConvWeight from `prep_conv_weight` ("same" padding).
     residual/res_mode: 1 = act(conv)+res, 2 = act(conv+res).  relu: False/0 none, True/1 ReLU, 2 GELU (erf)."""
-    import ctypes
     weight_t, bias, kernel = cw.wt, cw.bias, cw.kernel
-    ts, dims = [], []
-    for e in srcs:
-        t, uh, uw = (e, 1, 1) if isinstance(e, torch.Tensor) else e
-        t = _chk("conv source", t, 4)
-        ts.append(t)
-        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw)]
-    N, dev, Hi, Wi = _chk_conv_sources("conv2d", ts, dims, 5)
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    pad = (kernel - 1) // 2
-    Ho = (Hi + 2 * pad - kernel) // sh + 1
-    Wo = (Wi + 2 * pad - kernel) // sw + 1
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d", srcs)
+    sh, sw, Ho, Wo = _conv_out_size(Hi, Wi, kernel, stride)
     weight_t = _chk("weight_t", weight_t, 2)
     Cout = weight_t.shape[1]
     if weight_t.shape[0] != sum(t.shape[1] for t in ts) * kernel * kernel:
@@ -444,39 +464,24 @@ def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=No
         _chk_out("conv2d", "out", out, (N, Cout, Ho, Wo), torch.float32, dev)
     if N == 0:          # an empty batch has no device pointer to hand over
         return out
-    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    dim_arr = (ctypes.c_int * len(dims))(*dims)
-    with torch.cuda.device(ts[0].device):
-        rc = _lib.lib().tpspp_conv2d_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
-                                         len(ts), _ptr(weight_t), _ptr(cw.tiled), _ptr(bias), _ptr(residual),
-                                         _ptr(cw.post_scale), _ptr(cw.post_shift), int(res_mode),
-                                         int(relu), N, Cout, kernel, kernel, sh, sw, _ptr(out), Ho, Wo,
-                                         _stream(ts[0]))
+    ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_conv2d_fwd(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(weight_t), _ptr(cw.tiled), _ptr(bias),
+                                         _ptr(residual), _ptr(cw.post_scale), _ptr(cw.post_shift), int(res_mode),
+                                         int(relu), N, Cout, kernel, kernel, sh, sw, _ptr(out), Ho, Wo, _stream(ts[0]))
     _lib.check(rc, "tpspp_conv2d_fwd")
     return out
 
 
 # ---- backward of the fused convolution (tpspp_conv_bwd.hip): training the regressor on the HIP kernels -------------
-def _conv_sources(who, srcs):
-    """srcs entries `tensor` or `(tensor, uh, uw)` -> (contiguous tensors, flat src_dims, N, device, Hi, Wi)."""
-    ts, dims = [], []
-    for e in srcs:
-        t, uh, uw = (e, 1, 1) if isinstance(e, torch.Tensor) else e
-        t = _chk(f"{who} source", t, 4)
-        ts.append(t)
-        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw)]
-    N, dev, Hi, Wi = _chk_conv_sources(who, ts, dims, 5)
-    return ts, dims, N, dev, Hi, Wi
-
-
-def _conv_out_size(who, Hi, Wi, kernel, stride):
+def _bwd_out_size(who, Hi, Wi, kernel, stride):
+    """`_conv_out_size` under the rule of the backward kernels: stride 1 or 2, kernel 1x1 or 3x3."""
     sh, sw = (stride, stride) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
     if sh not in (1, 2) or sw not in (1, 2):
         raise ValueError(f"{who}: stride must be 1 or 2 along each axis, got {(sh, sw)}")
     if kernel not in (1, 3):
         raise ValueError(f"{who}: kernel must be 1x1 or 3x3")
-    pad = (kernel - 1) // 2
-    return sh, sw, (Hi + 2 * pad - kernel) // sh + 1, (Wi + 2 * pad - kernel) // sw + 1
+    return _conv_out_size(Hi, Wi, kernel, (sh, sw))
 
 
 def _chk_grad_out(who, dy, y, relu, shape, dev):
@@ -519,23 +524,20 @@ def conv2d_bwd_data(dy, weight, srcs, stride=(1, 1), y=None, relu=True, need=Non
     dy (N, Cout, Ho, Wo); weight (Cout, Cin, KH, KW) as PyTorch holds it; srcs as `conv2d` takes them (only their
     shapes and upsampling factors are used); y the forward's output (needed with relu: the mask is y > 0).
     need: per-source flags (default all).  Returns a list with one (N, C_i, H_i, W_i) tensor or None per source."""
-    import ctypes
-    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_data", srcs)
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_data", srcs, "conv2d_bwd_data source")
     w = _chk("weight", weight.detach(), 4)
     cout, cin, kh, kw = w.shape
     if kh != kw or cin != sum(t.shape[1] for t in ts) or w.device != dev:
         raise ValueError("conv2d_bwd_data: weight must be (Cout, sum C_i, K, K) on the sources' device")
-    sh, sw, Ho, Wo = _conv_out_size("conv2d_bwd_data", Hi, Wi, kh, stride)
+    sh, sw, Ho, Wo = _bwd_out_size("conv2d_bwd_data", Hi, Wi, kh, stride)
     dy, y = _chk_grad_out("conv2d_bwd_data", dy, y, relu, (N, cout, Ho, Wo), dev)
     need = [True] * len(ts) if need is None else [bool(v) for v in need]
     outs = [torch.empty_like(t) if nd else None for t, nd in zip(ts, need)]
     if N == 0 or not any(need):
         return outs
-    ptrs = (ctypes.c_void_p * len(ts))(*[0 if o is None else o.data_ptr() for o in outs])
-    dim_arr = (ctypes.c_int * len(dims))(*dims)
+    ptrs, dim_arr = _ptr_array(outs), _int_array(dims)
     with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bwd_data(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
-                                              len(ts), _ptr(w), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, kh, kw,
+        rc = _lib.lib().tpspp_conv2d_bwd_data(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(w), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, kh, kw,
                                               sh, sw, Ho, Wo, _stream(dy))
     _lib.check(rc, "tpspp_conv2d_bwd_data")
     return outs
@@ -544,19 +546,16 @@ def conv2d_bwd_data(dy, weight, srcs, stride=(1, 1), y=None, relu=True, need=Non
 def conv2d_bwd_weight_workspace_floats(srcs_dims, N, Cout, kernel, Ho, Wo):
     """Floats of workspace `conv2d_bwd_weight` needs (`tpspp_conv2d_bwd_weight_workspace_floats`): srcs_dims the flat
     {C, H, W, uh, uw} per source; 0 for N = 0.  The split-K slice count behind it depends on the shapes only."""
-    import ctypes
-    dim_arr = (ctypes.c_int * len(srcs_dims))(*srcs_dims)
-    return int(_lib.lib().tpspp_conv2d_bwd_weight_workspace_floats(ctypes.cast(dim_arr, ctypes.c_void_p),
-                                                                    len(srcs_dims) // 5, N, Cout, kernel, kernel,
-                                                                    Ho, Wo))
+    dim_arr = _int_array(srcs_dims)
+    return int(_lib.lib().tpspp_conv2d_bwd_weight_workspace_floats(_vp(dim_arr), len(srcs_dims) // 5, N, Cout, kernel,
+                                                                    kernel, Ho, Wo))
 
 
 def conv2d_bwd_weight(srcs, dy, kernel, stride=(1, 1), y=None, relu=True, want_weight=True, want_bias=True):
     """Weight and bias gradients of `conv2d(srcs, ..., relu)` (res_mode 0) (`tpspp_conv2d_bwd_weight`): a fixed
     split-K without atomics, bitwise reproducible.  Returns (dW (Cout, Cin, K, K) | None, db (Cout) | None)."""
-    import ctypes
-    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_weight", srcs)
-    sh, sw, Ho, Wo = _conv_out_size("conv2d_bwd_weight", Hi, Wi, int(kernel), stride)
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bwd_weight", srcs, "conv2d_bwd_weight source")
+    sh, sw, Ho, Wo = _bwd_out_size("conv2d_bwd_weight", Hi, Wi, int(kernel), stride)
     if dy.dim() != 4:
         raise ValueError("conv2d_bwd_weight: dy must be (N, Cout, Ho, Wo)")
     cout, cin = dy.shape[1], sum(t.shape[1] for t in ts)
@@ -573,11 +572,9 @@ def conv2d_bwd_weight(srcs, dy, kernel, stride=(1, 1), y=None, relu=True, want_w
         return dw, db
     nws = conv2d_bwd_weight_workspace_floats(dims, N, cout, int(kernel), Ho, Wo)
     ws = torch.empty((nws,), device=dev, dtype=torch.float32)
-    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    dim_arr = (ctypes.c_int * len(dims))(*dims)
+    ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
     with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bwd_weight(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
-                                                len(ts), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, int(kernel),
+        rc = _lib.lib().tpspp_conv2d_bwd_weight(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, int(kernel),
                                                 int(kernel), sh, sw, Ho, Wo, _ptr(dw), _ptr(db), _ptr(ws), nws,
                                                 _stream(dy))
     _lib.check(rc, "tpspp_conv2d_bwd_weight")
@@ -627,13 +624,10 @@ def conv2d_autograd(srcs, weight, bias, stride=(1, 1), relu=True, cw=None):
     if not 1 <= len(srcs) <= 3:
         raise ValueError("conv2d_autograd: 1..3 sources")
     ts, ups = [], []
-    for e in srcs:
-        t, uh, uw = (e, 1, 1) if isinstance(e, torch.Tensor) else e
+    for t, uh, uw in _split_sources(srcs):
         if not isinstance(t, torch.Tensor):
             raise TypeError("conv2d_autograd: expected tensors")
-        if not t.is_cuda:
-            raise _lib.TpsppError(f"conv2d_autograd: tensor is on {t.device}; the HIP path needs a GPU tensor "
-                                  "(no CPU fallback)")
+        _chk_gpu("conv2d_autograd", t)
         ts.append(t)
         ups.append((int(uh), int(uw)))
     _chk("weight", weight, 4)
@@ -643,20 +637,6 @@ def conv2d_autograd(srcs, weight, bias, stride=(1, 1), relu=True, cw=None):
         raise ValueError("conv2d_autograd: relu must be True (ReLU) or False (none)")
     st = (stride, stride) if isinstance(stride, int) else (int(stride[0]), int(stride[1]))
     return _ConvFunction.apply(weight, bias, (tuple(ups), st, int(bool(relu)), cw), *ts)
-
-
-def _chk16(name, t, ndim=None):
-    """bf16 path: a GPU tensor that is float32 or bfloat16."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch.Tensor")
-    if not t.is_cuda:
-        raise _lib.TpsppError(f"{name}: tensor is on {t.device}; the HIP path needs a GPU tensor "
-                              "(no CPU fallback)")
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{name}: expected float32 or bfloat16, got {t.dtype}")
-    if ndim is not None and t.dim() != ndim:
-        raise ValueError(f"{name}: expected {ndim} dims, got {tuple(t.shape)}")
-    return t.contiguous()
 
 
 class ConvWeightBf16:
@@ -671,13 +651,7 @@ class ConvWeightBf16:
 def prep_conv_weight_bf16(weight, bn=None, conv_bias=None, eps=1e-5, post_bn=None, x3=False):
     """PyTorch conv weight (Cout, Cin, KH, KW) [+ eval-mode BatchNorm folded in fp32, then rounded] ->
     ConvWeightBf16.  Same folding rules as `prep_conv_weight`.  x3: the "bf16x3" split (hi and lo slabs per chunk)."""
-    w = weight.detach().float()
-    b = None if conv_bias is None else conv_bias.detach().float()
-    if bn is not None:
-        gamma, beta, mean, var = (t.detach().float() for t in bn)
-        scale = gamma / torch.sqrt(var + eps)
-        w = w * scale.view(-1, 1, 1, 1)
-        b = beta - mean * scale if b is None else beta + (b - mean) * scale
+    w, b, ps, pb = _fold_bn(weight, bn, conv_bias, eps, post_bn)
     cout, cin, kh, kw = w.shape
     kc = int(_lib.lib().tpspp_conv_bf16_chunk_channels(int(kh)))
     ct, nch = (cout + 63) // 64, (cin + kc - 1) // kc
@@ -685,18 +659,11 @@ def prep_conv_weight_bf16(weight, bn=None, conv_bias=None, eps=1e-5, post_bn=Non
     wp[:cout, :cin] = w
     # (ctile, co, chunk, kgroup, k8, ky, kx) -> (ctile, chunk, ky, kx, kgroup, co, k8)
     arranged = wp.view(ct, 64, nch, kc // 8, 8, kh, kw).permute(0, 2, 5, 6, 3, 1, 4).contiguous()
-    if x3:          # [ctile][chunk][hi|lo][tap...]: hi = bf16(w), lo = bf16(w - hi)
-        hi = arranged.to(torch.bfloat16)
-        lo = (arranged - hi.float()).to(torch.bfloat16)
-        arranged = torch.stack([hi, lo], dim=2).contiguous()
+    if x3:          # [ctile][chunk][hi|lo][tap...]
+        arranged = torch.stack(_hi_lo(arranged), dim=2).contiguous()
     else:
         arranged = arranged.to(torch.bfloat16)
-    ps = pb = None
-    if post_bn is not None:
-        gamma, beta, mean, var = (t.detach().float() for t in post_bn)
-        ps = (gamma / torch.sqrt(var + eps)).contiguous()
-        pb = (beta - mean * ps).contiguous()
-    return ConvWeightBf16(arranged, None if b is None else b.contiguous(), kh, cin, cout, ps, pb, x3)
+    return ConvWeightBf16(arranged, b, kh, cin, cout, ps, pb, x3)
 
 
 class Blocked:
@@ -704,18 +671,20 @@ class Blocked:
     per pixel -- that the bf16 convolutions exchange among themselves (`tpspp_conv2d_bf16_fwd`, layout code 2: a
     16-byte unit of it is a unit of the kernel's LDS patch).  `shape` is the logical (N, C, H, W)."""
 
+    _dtype = torch.bfloat16
+
     def __init__(self, t):
-        if t.dtype != torch.bfloat16 or t.dim() != 5 or t.shape[4] != 8 or not t.is_contiguous():
-            raise ValueError("Blocked: needs a contiguous bfloat16 (N, C/8, H, W, 8) tensor")
+        if t.dtype != self._dtype or t.dim() != 5 or t.shape[4] != 8 or not t.is_contiguous():
+            raise ValueError(f"{type(self).__name__}: needs a contiguous {str(self._dtype)[6:]} (N, C/8, H, W, 8) tensor")
         self.t = t
         self.shape = (t.shape[0], t.shape[1] * 8, t.shape[2], t.shape[3])
         self.dtype, self.device = t.dtype, t.device
         self.requires_grad, self.is_cuda = False, t.is_cuda      # (a product of the HIP inference kernels: no autograd graph)
 
-    @staticmethod
-    def from_nchw(x):
+    @classmethod
+    def from_nchw(cls, x):
         n, c, h, w = x.shape
-        return Blocked(x.to(torch.bfloat16).reshape(n, c // 8, 8, h, w).permute(0, 1, 3, 4, 2).contiguous())
+        return cls(x.to(cls._dtype).reshape(n, c // 8, 8, h, w).permute(0, 1, 3, 4, 2).contiguous())
 
     def nchw(self):
         n, c, h, w = self.shape
@@ -744,17 +713,7 @@ class Blocked32(Blocked):
     use between convolutions (layout code 3: a patch position's 8 channels are two 16-byte loads instead of eight 4-byte
     loads from eight planes)."""
 
-    def __init__(self, t):
-        if t.dtype != torch.float32 or t.dim() != 5 or t.shape[4] != 8 or not t.is_contiguous():
-            raise ValueError("Blocked32: needs a contiguous float32 (N, C/8, H, W, 8) tensor")
-        self.t = t
-        self.shape = (t.shape[0], t.shape[1] * 8, t.shape[2], t.shape[3])
-        self.dtype, self.device = t.dtype, t.device
-
-    @staticmethod
-    def from_nchw(x):
-        n, c, h, w = x.shape
-        return Blocked32(x.float().reshape(n, c // 8, 8, h, w).permute(0, 1, 3, 4, 2).contiguous())
+    _dtype = torch.float32
 
 
 def _layout_code(t):
@@ -767,26 +726,15 @@ def conv2d_bf16(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, o
     """Fused conv on the bf16 matrix cores (`tpspp_conv2d_bf16_fwd`): same call shape as `conv2d`; every
     source / the residual may be float32 or bfloat16 NCHW or a `Blocked` bf16 map, the output is `out_dtype`
     (`out_blocked`: a `Blocked` bf16 map, for layers that only feed other convolutions)."""
-    import ctypes
-    ts, dims = [], []
-    for e in srcs:
-        t, uh, uw = e if isinstance(e, tuple) else (e, 1, 1)
-        code = _layout_code(t)
-        t = _BlkView(t) if isinstance(t, Blocked) else _chk16("conv source", t, 4)
-        ts.append(t)
-        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw), code]
-    N, dev, Hi, Wi = _chk_conv_sources("conv2d_bf16", ts, dims, 6)
+    ts, dims, N, dev, Hi, Wi = _conv_sources("conv2d_bf16", srcs, layouts=True)
     if sum(t.shape[1] for t in ts) != cw.cin:
         raise ValueError("conv2d_bf16: source channels != Cin of the weight")
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
     kernel, Cout = cw.kernel, cw.cout
-    pad = (kernel - 1) // 2
-    Ho = (Hi + 2 * pad - kernel) // sh + 1
-    Wo = (Wi + 2 * pad - kernel) // sw + 1
+    sh, sw, Ho, Wo = _conv_out_size(Hi, Wi, kernel, stride)
     res_code = 0
     if residual is not None:
         if not isinstance(residual, Blocked):
-            residual = _chk16("residual", residual, 4)
+            residual = _chk("residual", residual, 4, _F32_BF16)
         if tuple(residual.shape) != (N, Cout, Ho, Wo) or res_mode not in (1, 2) or residual.device != dev:
             raise ValueError("conv2d_bf16: residual shape / device / res_mode")
         res_code = _layout_code(residual)
@@ -812,12 +760,10 @@ def conv2d_bf16(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, o
         raise ValueError("conv2d_bf16: Blocked (bfloat16) maps go with plain bf16 weights, Blocked32 (float32) maps with x3 weights")
     if N == 0:          # an empty batch has no device pointer to hand over
         return out
-    ptrs = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-    dim_arr = (ctypes.c_int * len(dims))(*dims)
+    ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
     first = ts[0].keep if isinstance(ts[0], _BlkView) else ts[0]
     with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bf16_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(dim_arr, ctypes.c_void_p),
-                                              len(ts), _ptr(cw.arranged), _ptr(cw.bias),
+        rc = _lib.lib().tpspp_conv2d_bf16_fwd(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(cw.arranged), _ptr(cw.bias),
                                               residual.data_ptr() if residual is not None else None, res_code,
                                               _ptr(cw.post_scale), _ptr(cw.post_shift), int(res_mode), int(relu),
                                               N, Cout, kernel, kernel, sh, sw, out.data_ptr(),
@@ -895,10 +841,7 @@ def _bf16_slab(w, chain, x3=False):
     if chain:
         idx = idx[:, torch.tensor(_PERM16, device=w.device)]
     a = w[:, idx.reshape(-1)].view(cout, cin // 16, 2, 8).permute(1, 2, 0, 3).contiguous()
-    if not x3:
-        return a.to(torch.bfloat16)
-    hi = a.to(torch.bfloat16)
-    return torch.stack([hi, (a - hi.float()).to(torch.bfloat16)]).contiguous()
+    return torch.stack(_hi_lo(a)).contiguous() if x3 else a.to(torch.bfloat16)
 
 
 class DgabWeightsBf16:
@@ -1052,7 +995,7 @@ def front_bf16(o0, o1, x, fw, feat_grid_dtype=torch.bfloat16, blocked=False, sto
     """`front` on the bf16 matrix cores: bf16 in, bf16 feat0 / feat1 / feat2, feat_grid bf16 or fp32; with x3 weights
     (`FrontWeightsBf16(m, x3=True)`) fp32 in and out, three-term split.  `store01=False` (blocked bf16 only): feat0 / feat1
     stay operands of feat_grid and are returned as None -- `down_fused_bf16` recomputes them where they are consumed."""
-    o0, o1, x = _chk16("outs[0]", o0, 4), _chk16("outs[1]", o1, 4), _chk16("x", x, 4)
+    o0, o1, x = (_chk(nm, t, 4, _F32_BF16) for nm, t in (("outs[0]", o0), ("outs[1]", o1), ("x", x)))
     N, c0, H, W = o0.shape
     if c0 != 32 or tuple(o1.shape) != (N, 32, H, W) or tuple(x.shape) != (N, 64, H // 2, W // 2):
         raise ValueError("front_bf16: needs outs (N,32,H,W) x2 and x (N,64,H/2,W/2)")
@@ -1124,7 +1067,7 @@ def down_fused_bf16(o, w0_slab, b0, cw, relu=True):
     """`down0_1(down0(outs[0]))` / `down1_1(down1(outs[1]))` of TPS_PP.forward (tps_pp.py:560-563) in one kernel
     (`tpspp_down_fused_bf16_fwd`): the 1x1 result never exists in HBM.  `w0_slab`, `b0`: the 1x1 layer as
     `FrontWeightsBf16` holds it; `cw`: the 3x3 stride-2 layer (`prep_conv_weight_bf16`).  Returns a `Blocked` map."""
-    o = _chk16("outs", o, 4)
+    o = _chk("outs", o, 4, _F32_BF16)
     if not down_fused_bf16_applicable(o, cw):
         raise ValueError("down_fused_bf16: needs a (N, 32, H, 128) map with an even H -- bfloat16 with a 64 -> 64 3x3 bf16 weight, "
                          "float32 with an x3 weight -- and a bias")
@@ -1315,9 +1258,7 @@ def arrange_x3(w_kmajor):
     Cop = (Co + 31) // 32 * 32
     if Cop != Co:
         w = torch.cat([w, w.new_zeros((K, Cop - Co))], dim=1)
-    hi = w.to(torch.bfloat16)
-    lo = (w - hi.float()).to(torch.bfloat16)
-    st = torch.stack([hi, lo])                                         # (s, K, Cop)
+    st = torch.stack(_hi_lo(w))                                        # (s, K, Cop)
     st = st.reshape(2, K // 16, 2, 8, Cop // 32, 32)                   # (s, ks, h, e, ct, r)
     return st.permute(4, 1, 0, 2, 5, 3).contiguous()                   # (ct, ks, s, h, r, e)
 
@@ -1339,10 +1280,9 @@ class PtrTable:
     """Host array of device pointers (`const float* const*`) + the tensors it points at (kept alive)."""
 
     def __init__(self, tensors):
-        import ctypes
         self.keep = list(tensors)
-        self.arr = (ctypes.c_void_p * len(self.keep))(*[None if t is None else t.data_ptr() for t in self.keep])
-        self.ptr = ctypes.cast(self.arr, ctypes.c_void_p)
+        self.arr = _ptr_array(self.keep)
+        self.ptr = _vp(self.arr)
 
     def __len__(self):
         return len(self.keep)
@@ -1503,13 +1443,8 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
     flags = (BWD_FIXED_POINT if fixed_point else 0) | (BWD_TWO_KERNELS if two_kernels else 0)
     g_score = None
     if score is not None:
-        if tuple(score.shape) != (N, n, F):
-            raise ValueError("warp_backward: score must be (N, n, F)")
-        if score.stride() == (F * n, 1, n) and n > 1 and F > 1:
-            flags |= SCORE_TRANSPOSED
-            score = _chk("score", score.transpose(1, 2), 3)
-        else:
-            score = _chk("score", score, 3)
+        score, transposed = _chk_score("warp_backward", score, N, n, F)
+        flags |= transposed
         if need_score:
             g_score = torch.empty_like(score)
     if P_xy is not None:
@@ -1586,13 +1521,7 @@ def warp_autograd(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, 
 # are (1, M, 0, K, 1), the tokens of an NCHW map (b c h w -> b (h w) c) are (N, H*W, C*H*W, 1, H*W).
 
 def _i64(*v):
-    import ctypes
-    return (ctypes.c_longlong * len(v))(*v)
-
-
-def _vp(arr):
-    import ctypes
-    return ctypes.cast(arr, ctypes.c_void_p)
+    return _int_array(v, ctypes.c_longlong)
 
 
 def _dense(M, K):
@@ -2181,13 +2110,6 @@ def _conv_spec(conv, name, bias_ok=False):
         raise ValueError(f"{name}: the HIP training path takes 1x1 / 3x3 convolutions with 'same' zero padding, stride 1 or 2"
                          f"{', a bias' if bias_ok else ', no bias'}, no dilation and no groups")
     return k, st
-
-
-def _chk_gpu(who, x):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{who}: expected a torch.Tensor")
-    if not x.is_cuda:
-        raise _lib.TpsppError(f"{who}: tensor is on {x.device}; the HIP path needs a GPU tensor (no CPU fallback)")
 
 
 class _BnStemFunction(torch.autograd.Function):

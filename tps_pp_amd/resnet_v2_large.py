@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from .precision import default_compute_dtype
 from . import ops
+from ._prepared import invalidate_prepared, prepared
 from .registry import BACKBONES
 
 
@@ -59,42 +60,24 @@ class BasicBlock(nn.Module):
             residual = self.downsample(x)
         return self.relu(out + residual)
 
-    def _weights(self):
-        mods = [self.conv1, self.bn1, self.conv2, self.bn2] + \
-            ([self.downsample[0], self.downsample[1]] if self.downsample is not None else [])
-        key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-        cache = getattr(self, "_cw_cache", None)
-        if cache is None or cache[0] != key:
-            def fold(conv, bn):
-                return ops.prep_conv_weight(conv.weight, bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var),
-                                            eps=bn.eps)
-            cw = [fold(self.conv1, self.bn1), fold(self.conv2, self.bn2),
-                  fold(self.downsample[0], self.downsample[1]) if self.downsample is not None else None]
-            self._cw_cache = cache = (key, cw)
-        return cache[1]
+    def _weights(self, prep=ops.prep_conv_weight, **kw):
+        """[conv1, conv2, downsample conv | None] with their BatchNorms folded in, by `ops.prep_conv_weight` (fp32
+        kernels) or `ops.prep_conv_weight_bf16` (kw: x3)."""
+        pairs = [(self.conv1, self.bn1), (self.conv2, self.bn2)] + \
+            ([(self.downsample[0], self.downsample[1])] if self.downsample is not None else [])
 
-    def _weights_bf16(self, x3=False):
-        mods = [self.conv1, self.bn1, self.conv2, self.bn2] + \
-            ([self.downsample[0], self.downsample[1]] if self.downsample is not None else [])
-        key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-        name = "_cw16x3_cache" if x3 else "_cw16_cache"
-        cache = getattr(self, name, None)
-        if cache is None or cache[0] != key:
-            def fold(conv, bn):
-                return ops.prep_conv_weight_bf16(conv.weight, eps=bn.eps, x3=x3,
-                                                 bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var))
-            cw = [fold(self.conv1, self.bn1), fold(self.conv2, self.bn2),
-                  fold(self.downsample[0], self.downsample[1]) if self.downsample is not None else None]
-            cache = (key, cw)
-            setattr(self, name, cache)
-        return cache[1]
+        def build():
+            cw = [prep(conv.weight, bn=ops.bn_tensors(bn), eps=bn.eps, **kw) for conv, bn in pairs]
+            return cw if len(cw) == 3 else cw + [None]
+
+        return prepared(self, prep.__name__, [m for pair in pairs for m in pair], build, tuple(kw.items()))
 
     def _forward_hip_bf16(self, x, out_dtype=torch.bfloat16, x3=False, out_blocked=False):
         """The block on the bf16 matrix cores (BatchNorm folded in fp32, then rounded): activations bf16 in
         HBM, accumulation / bias / residual add / ReLU in fp32.  x3: fp32 activations, three-term bf16 split.
         The map between the block's two convolutions, and with `out_blocked` the block's result, are in the blocked layout
         (`ops.Blocked` / `ops.Blocked32`: 16-byte loads per patch position in the 3x3 convolution); `x` may be blocked."""
-        c1, c2, cd = self._weights_bf16(x3)
+        c1, c2, cd = self._weights(ops.prep_conv_weight_bf16, x3=x3)
         mid = torch.float32 if x3 else torch.bfloat16
         out = ops.conv2d_bf16([x], c1, self.conv1.stride, True, out_dtype=mid, out_blocked=True)
         if cd is None:
@@ -167,17 +150,13 @@ class ResNetABI_v2_large(nn.Module):
             layers.append(BasicBlock(planes, planes, use_conv1x1=True))
         return nn.Sequential(*layers)
 
+    def _stem_weight(self, prep=ops.prep_conv_weight, **kw):
+        bn = self.bn1
+        return prepared(self, prep.__name__, [self.conv1, bn], lambda: prep(
+            self.conv1.weight, conv_bias=self.conv1.bias, bn=ops.bn_tensors(bn), eps=bn.eps, **kw), tuple(kw.items()))
+
     def _stem(self, x):
-        if True:
-            mods = [self.conv1, self.bn1]
-            key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-            cache = getattr(self, "_cw_cache", None)
-            if cache is None or cache[0] != key:
-                bn = self.bn1
-                cw = ops.prep_conv_weight(self.conv1.weight, conv_bias=self.conv1.bias, eps=bn.eps,
-                                          bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var))
-                self._cw_cache = cache = (key, cw)
-            return ops.conv2d([x.float().contiguous()], cache[1], 1, True)
+        return ops.conv2d([x.float().contiguous()], self._stem_weight(), 1, True)
 
     # ---- training graph on the HIP kernels (tpspp_bn_train.hip + the convolution kernels) ------------------------------
     TRAIN_BACKENDS = ("torch", "hip")
@@ -198,20 +177,13 @@ class ResNetABI_v2_large(nn.Module):
 
     def _train_cw(self, name, conv):
         """The forward's weight layouts of one convolution, cached and rebuilt on the device when its parameters change
-        (data_ptr / _version: an optimiser step, an in-place op, load_state_dict).  An edit through `param.data` is NOT
-        seen: call `invalidate_train_cache()` after one."""
+        (`_prepared`, which also names the blind spot `invalidate_train_cache()` is for)."""
         w, b = conv.weight, conv.bias
-        key = (w.data_ptr(), w._version) + ((b.data_ptr(), b._version) if b is not None else ())
-        cache = self.__dict__.setdefault("_train_cw_cache", {})
-        ent = cache.get(name)
-        if ent is None or ent[0] != key:
-            ent = cache[name] = (key, ops.prep_conv_weight_device(w, b))
-        return ent[1]
+        return prepared(self, ("train", name), [w, b], lambda: ops.prep_conv_weight_device(w, b))
 
     def invalidate_train_cache(self):
-        """Drop the HIP training path's cached forward weight layouts (needed only after edits through `param.data`)."""
-        self.__dict__.pop("_train_cw_cache", None)
-        return self
+        """Drop the cached weight layouts of this module's HIP paths (needed only after edits through `param.data`)."""
+        return invalidate_prepared(self)
 
     def _forward_train_hip(self, x, tpsnet=None, **kwargs):
         """`_forward_torch` on the HIP kernels: the same `_run` (stage order, hand-off to `tpsnet`), the stem and each
@@ -264,19 +236,10 @@ class ResNetABI_v2_large(nn.Module):
         return self._run(x, tpsnet, self._stem, lambda blk, t, inner: blk(t), **kwargs)
 
     def _stem_bf16(self, x, x3=False, out_blocked=False):
-        mods = [self.conv1, self.bn1]
-        key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-        name = "_cw16x3_cache" if x3 else "_cw16_cache"
-        cache = getattr(self, name, None)
-        if cache is None or cache[0] != key:
-            bn = self.bn1
-            cw = ops.prep_conv_weight_bf16(self.conv1.weight, conv_bias=self.conv1.bias, eps=bn.eps, x3=x3,
-                                           bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var))
-            cache = (key, cw)
-            setattr(self, name, cache)
+        cw = self._stem_weight(ops.prep_conv_weight_bf16, x3=x3)
         if out_blocked and not x3:
-            return ops.conv2d_bf16([x], cache[1], 1, True, out_blocked=True)
-        return ops.conv2d_bf16([x], cache[1], 1, True, out_dtype=torch.float32 if x3 else torch.bfloat16)
+            return ops.conv2d_bf16([x], cw, 1, True, out_blocked=True)
+        return ops.conv2d_bf16([x], cw, 1, True, out_dtype=torch.float32 if x3 else torch.bfloat16)
 
     def _run(self, x, tpsnet, stem, apply_block, blocked_stage0=False, **kwargs):
         x = stem(x)

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 
 from .precision import default_compute_dtype
 from . import constants, ops
+from ._prepared import invalidate_prepared, prepared
 from .registry import BACKBONES, PREPROCESSOR
 
 
@@ -271,16 +272,13 @@ class Attention_Enhanced_TPS(nn.Module):
         self.register_buffer("hat_C", torch.from_numpy(k["hat_C"]))
         self.register_buffer("P_hat", torch.from_numpy(k["P_hat"]))
         self._P_xy_host = k["P_xy"]
-        self._prep = None
 
     def device_constants(self, device):
         """(P_xy, P_hat_t) on `device`; P is not a registered buffer in the reference (it does a
         per-call `torch.tensor(self.P).float().to(device)`, tps_pp.py:472): cached here instead."""
         p = self.P_hat
-        key = (p.data_ptr(), p._version, str(device))
-        if self._prep is None or self._prep[0] != key:
-            self._prep = (key, torch.from_numpy(self._P_xy_host).to(device), ops.transpose_p_hat(p))
-        return self._prep[1], self._prep[2]
+        return prepared(self, "constants", [p],
+                        lambda: (torch.from_numpy(self._P_xy_host).to(device), ops.transpose_p_hat(p)), str(device))
 
     def build_P_prime(self, batch_C_prime, pc_score, device="cuda"):
         """(N,F,2), (N,n,F) -> (N,n,2) sampling grid (`tps_pp.py:481-496`), HIP kernels."""
@@ -366,9 +364,7 @@ class TPS_PP(nn.Module):
         for k in head + rest + tail:
             self._modules[k] = self._modules.pop(k)           # re-insert: dicts keep insertion order
         self.type = variant
-        for c in ("_cw_cache", "_cw16_cache", "_front_cache", "_front16_cache", "_train_cw_cache"):
-            if hasattr(self, c):
-                delattr(self, c)
+        invalidate_prepared(self)
 
     def set_variant(self, variant, explicit=True):
         """Switch the wiring ('ResNet45v2' / 'ResNet45'); the layers the two do not share are re-created with a fresh
@@ -429,23 +425,24 @@ class TPS_PP(nn.Module):
             tap[name] = (t.nchw() if isinstance(t, ops.Blocked) else t).float().clone()
 
     # ---- hand-written conv path (fp32 MFMA kernels, tps_pp_amd/csrc/tpspp_conv.hip) -------------
-    def _conv_weights(self):
-        """ConvWeight per conv layer, rebuilt when a parameter changes (version counters)."""
+    def _conv_weights(self, prep=ops.prep_conv_weight, **kw):
+        """{layer name: prep(weight, conv_bias=bias, **kw)} of every conv layer: `ops.prep_conv_weight` (fp32 kernels) or
+        `ops.prep_conv_weight_bf16` (kw: x3)."""
         convs = {"down0": self.down0, "down1": self.down1, "down2": self.down2}
         if self.type == "ResNet45v2":
             convs.update(down0_1=self.down0_1, down1_1=self.down1_1, down_feat=self.down_feat)
         for i in range(4):
             convs[f"enc{i}"] = self.MSFA.conv.k_encoder[i]
             convs[f"dec{i}"] = self.MSFA.conv.k_decoder[i][1]
-        key = tuple((n, m.conv.weight._version, m.conv.bias._version, m.conv.weight.data_ptr())
-                    for n, m in convs.items())
-        cache = getattr(self, "_cw_cache", None)
-        if cache is None or cache[0] != key:
-            srcs = {"down_feat": [64, 64, 64], "enc0": [64, 64, 64]}
-            cw = {n: ops.prep_conv_weight(m.conv.weight, conv_bias=m.conv.bias, src_channels=srcs.get(n))
-                  for n, m in convs.items()}
-            self._cw_cache = cache = (key, cw)
-        return cache[1]
+        # (the fp32 kernel's tiled form needs to know where the concatenated sources meet)
+        cat = {"src_channels": [64, 64, 64]} if prep is ops.prep_conv_weight else {}
+        extra = {"down_feat": cat, "enc0": cat}
+
+        def build():
+            return {n: prep(m.conv.weight, conv_bias=m.conv.bias, **kw, **extra.get(n, {})) for n, m in convs.items()}
+
+        return prepared(self, prep.__name__, [t for m in convs.values() for t in (m.conv.weight, m.conv.bias)], build,
+                        tuple(kw.items()))
 
     def _msfa_hip(self, feat_srcs, cw):
         """Encoder_Decoder_Feature_Extractor.forward (`tps_pp.py:156-169`) on the fused conv kernel:
@@ -466,29 +463,12 @@ class TPS_PP(nn.Module):
         return e3, k
 
     # ---- bf16 path (BASELINE.json configs[2]): bf16 MFMA convolutions, tpspp_conv_bf16.hip ------------
-    def _conv_weights_bf16(self, x3=False):
-        convs = {"down0": self.down0, "down1": self.down1, "down2": self.down2}
-        if self.type == "ResNet45v2":
-            convs.update(down0_1=self.down0_1, down1_1=self.down1_1, down_feat=self.down_feat)
-        for i in range(4):
-            convs[f"enc{i}"] = self.MSFA.conv.k_encoder[i]
-            convs[f"dec{i}"] = self.MSFA.conv.k_decoder[i][1]
-        key = tuple((n, m.conv.weight._version, m.conv.bias._version, m.conv.weight.data_ptr())
-                    for n, m in convs.items())
-        name = "_cw16x3_cache" if x3 else "_cw16_cache"
-        cache = getattr(self, name, None)
-        if cache is None or cache[0] != key:
-            cw = {n: ops.prep_conv_weight_bf16(m.conv.weight, conv_bias=m.conv.bias, x3=x3) for n, m in convs.items()}
-            cache = (key, cw)
-            setattr(self, name, cache)
-        return cache[1]
-
     def _regress_hip_bf16(self, batch_img, outs, x3=False):
         """The regressor with every convolution on the bf16 matrix cores.  Activations between convolutions
         are bf16 in HBM; the three tensors that feed fp32 arithmetic -- `en_feat` (CBAM, control points:
         amplified ~223x by the TPS solve), `de_feat` (DGAB, score) and `feat_grid` (sampled by the warp) --
         leave their convolution in fp32 (fp32 accumulators, never rounded).  Inputs may be bf16 or fp32."""
-        cw = self._conv_weights_bf16(x3)
+        cw = self._conv_weights(ops.prep_conv_weight_bf16, x3=x3)
         f32 = torch.float32
         # x3 ("bf16x3", `compute_dtype = "bf16x3"`): every tensor stays fp32 in HBM and every product is the
         # three-term bf16 split (~5e-6 per layer): the convolutions of the parity-bound (1e-4) path at a third of
@@ -506,18 +486,14 @@ class TPS_PP(nn.Module):
             fg_dtype = bf if x.dtype == bf else f32
             if ops.front_bf16_applicable(o0, o1, x, x3):
                 # the four pointwise convolutions fused, register-chained (tpspp_front_bf16.hip)
-                fkey = (tuple((t.data_ptr(), t._version) for mdl in (self.down0, self.down1, self.down2, self.down_feat)
-                              for t in mdl.parameters()), x3)
-                fc = getattr(self, "_front16_cache", None)
-                if fc is None or fc[0] != fkey:
-                    self._front16_cache = fc = (fkey, ops.FrontWeightsBf16(self, x3))
+                fw = prepared(self, "front_bf16", [self.down0, self.down1, self.down2, self.down_feat],
+                              lambda: ops.FrontWeightsBf16(self, x3), x3)
                 # round 4: feat0 / feat1 are not stored where the stride-2 layers can recompute them from outs[0] / outs[1]
                 # (tpspp_down_fused.hip)
                 fused = (ops.down_fused_bf16_applicable(o0, cw["down0_1"])
                          and ops.down_fused_bf16_applicable(o1, cw["down1_1"]))
-                feat0, feat1, feat2, feat_grid = ops.front_bf16(o0, o1, x, fc[1], fg_dtype, blocked=True, store01=not fused)
+                feat0, feat1, feat2, feat_grid = ops.front_bf16(o0, o1, x, fw, fg_dtype, blocked=True, store01=not fused)
                 if fused:
-                    fw = fc[1]
                     cat_srcs = [ops.down_fused_bf16(o0, fw.w0, fw.b0, cw["down0_1"]),
                                 ops.down_fused_bf16(o1, fw.w1, fw.b1, cw["down1_1"]), feat2]
             else:
@@ -628,12 +604,8 @@ class TPS_PP(nn.Module):
         if self.type == "ResNet45v2":
             # down0 / down1 / down2 and grid() (cat + Upsample + down_feat) are pointwise: one fused,
             # register-chained MFMA kernel (tpspp_front.hip)
-            fkey = tuple((t.data_ptr(), t._version) for mdl in (self.down0, self.down1, self.down2, self.down_feat)
-                         for t in mdl.parameters())
-            fc = getattr(self, "_front_cache", None)
-            if fc is None or fc[0] != fkey:
-                self._front_cache = fc = (fkey, ops.FrontWeights(self))
-            fw = fc[1]
+            fw = prepared(self, "front", [self.down0, self.down1, self.down2, self.down_feat],
+                          lambda: ops.FrontWeights(self))
             fused = (ops.down_fused_f32_applicable(o0, cw["down0_1"])
                      and ops.down_fused_f32_applicable(o1, cw["down1_1"]))
             feat0, feat1, feat2, feat_grid = ops.front(o0, o1, x, fw, store01=not fused)
@@ -658,25 +630,20 @@ class TPS_PP(nn.Module):
         tpspp_score.hip: no library kernel is left on the GPU path of the regressor."""
         T = self.TPE
         blk = T.atten[0]
-        key = tuple((t.data_ptr(), t._version) for t in blk.parameters())
-        cache = getattr(self, "_dgab_cache", None)
-        key = key + tuple((t.data_ptr(), t._version) for t in T.feat_linear.parameters())
-        if cache is None or cache[0] != key:
-            self._dgab_cache = cache = (key, ops.DgabWeights(blk), ops.ScoreWeights(T.feat_linear))
         n = en_feat.size(0)
         if bf16:          # the three Linear layers of the DGAB chain on the bf16 matrix cores
-            c16 = getattr(self, "_dgab16_cache", None)
-            if c16 is None or c16[0] != (key, x3):
-                self._dgab16_cache = c16 = ((key, x3), ops.DgabWeightsBf16(blk, x3))
-            de = ops.dgab_bf16(de_feat, en_feat.reshape(n, en_feat.size(1), -1), c16[1])
+            dw = prepared(self, "dgab_bf16", blk.parameters(), lambda: ops.DgabWeightsBf16(blk, x3), x3)
+            de = ops.dgab_bf16(de_feat, en_feat.reshape(n, en_feat.size(1), -1), dw)
         else:
-            de = ops.dgab(de_feat, en_feat.reshape(n, en_feat.size(1), -1), cache[1])
+            dw = prepared(self, "dgab", blk.parameters(), lambda: ops.DgabWeights(blk))
+            de = ops.dgab(de_feat, en_feat.reshape(n, en_feat.size(1), -1), dw)
         self._tap("dgab", de)
         control_point, p1 = ops.tpe_points(en_feat, T)
         if T.without_as:
             return control_point, torch.zeros((n, de.shape[2] * de.shape[3], T.num_fiducial), device=de.device)
         # (in the bf16 and bf16x3 configurations the score's three products take the three-term split as well: ~5e-6)
-        return control_point, ops.score(de, p1, cache[2], T.scale, x3=bf16)
+        sw = prepared(self, "score", T.feat_linear.parameters(), lambda: ops.ScoreWeights(T.feat_linear))
+        return control_point, ops.score(de, p1, sw, T.scale, x3=bf16)
 
     def rectify(self, feat_grid, batch_img, control_point, atten_score, want_grid=False):
         """The transformation stage alone (`tps_pp.py:597-615`): one fused HIP kernel."""
@@ -709,28 +676,19 @@ class TPS_PP(nn.Module):
 
     def _train_conv(self, name, mod, srcs, stride):
         """One ConvModule (conv + in-place ReLU) on `ops.conv2d_autograd`; the forward's weight layouts are cached
-        per layer and rebuilt on the device when the parameters change (data_ptr / _version: an optimiser step, an
-        in-place op on the parameter, load_state_dict).  An edit through `param.data` bumps the version counter of a
-        different tensor and is NOT seen: after one, call `invalidate_train_cache()` (otherwise the forward would use the
-        stale layout while the backward reads the current weight)."""
+        per layer and rebuilt on the device when the parameters change (`_prepared`, which also names the blind spot
+        `invalidate_train_cache()` is for)."""
         conv = mod.conv
         if tuple(conv.padding) != ((conv.kernel_size[0] - 1) // 2, (conv.kernel_size[1] - 1) // 2):
             raise ValueError(f"TPS_PP.{name}: the HIP training path needs 'same' padding")
         w, b = conv.weight, conv.bias
-        key = (w.data_ptr(), w._version, b.data_ptr(), b._version, tuple(t.shape[1] for t in
-                                                                          (e if isinstance(e, torch.Tensor) else e[0]
-                                                                           for e in srcs)))
-        cache = self.__dict__.setdefault("_train_cw_cache", {})
-        ent = cache.get(name)
-        if ent is None or ent[0] != key:
-            chans = list(key[-1])
-            ent = cache[name] = (key, ops.prep_conv_weight_device(w, b, chans))
-        return ops.conv2d_autograd(srcs, w, b, stride, relu=True, cw=ent[1])
+        chans = tuple((e if isinstance(e, torch.Tensor) else e[0]).shape[1] for e in srcs)
+        cw = prepared(self, ("train", name), [w, b], lambda: ops.prep_conv_weight_device(w, b, list(chans)), chans)
+        return ops.conv2d_autograd(srcs, w, b, stride, relu=True, cw=cw)
 
     def invalidate_train_cache(self):
-        """Drop the HIP training path's cached forward weight layouts (needed only after edits through `param.data`)."""
-        self.__dict__.pop("_train_cw_cache", None)
-        return self
+        """Drop the cached weight layouts of this module's HIP paths (needed only after edits through `param.data`)."""
+        return invalidate_prepared(self)
 
     def _regress_train_hip(self, batch_img, outs, all_hip=False):
         """`_regress_torch` with every ConvModule on the HIP forward / backward kernels: the concatenations, the

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import constants, ops
+from ._prepared import prepared
 from .precision import default_compute_dtype
 from .registry import PREPROCESSOR
 
@@ -58,43 +59,25 @@ class LocalizationNetwork(nn.Module):
         self.localization_fc2.bias.data = torch.from_numpy(
             constants.classic_initial_ctrl(num_fiducial)).float().view(-1)
 
-    def _hip_weights(self):
-        """ConvWeights (eval-mode BatchNorm folded into the convolutions) per layer, rebuilt when a
-        parameter or running statistic changes."""
-        mods = [self.conv[i] for i in (0, 1, 4, 5, 8, 9, 12, 13)] + [self.localization_fc1[0], self.localization_fc2]
-        key = tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
-        cache = getattr(self, "_cw_cache", None)
-        if cache is None or cache[0] != key:
-            cw = []
-            for ci, bi in ((0, 1), (4, 5), (8, 9), (12, 13)):
-                bn = self.conv[bi]
-                cw.append(ops.prep_conv_weight(self.conv[ci].weight, bn=(bn.weight, bn.bias, bn.running_mean,
-                                                                       bn.running_var), eps=bn.eps))
-            fc1, fc2 = self.localization_fc1[0], self.localization_fc2
-            cw.append(ops.prep_conv_weight(fc1.weight.view(fc1.out_features, fc1.in_features, 1, 1), conv_bias=fc1.bias))
-            cw.append(ops.prep_conv_weight(fc2.weight.view(fc2.out_features, fc2.in_features, 1, 1), conv_bias=fc2.bias))
-            self._cw_cache = cache = (key, cw)
-        return cache[1]
+    def _hip_weights(self, prep=ops.prep_conv_weight, **kw):
+        """The four convolutions with their eval-mode BatchNorms folded in, by `ops.prep_conv_weight` (fp32 kernels) or
+        `ops.prep_conv_weight_bf16` (kw: x3), rebuilt when a parameter or running statistic changes."""
+        pairs = [(self.conv[i], self.conv[i + 1]) for i in (0, 4, 8, 12)]
+        return prepared(self, prep.__name__, [m for pair in pairs for m in pair],
+                        lambda: [prep(conv.weight, bn=ops.bn_tensors(bn), eps=bn.eps, **kw) for conv, bn in pairs],
+                        tuple(kw.items()))
 
-    def _hip_weights_bf16(self, x3=False):
-        mods = [self.conv[i] for i in (0, 1, 4, 5, 8, 9, 12, 13)]
-        key = (tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers())), x3)
-        cache = getattr(self, "_cw16_cache", None)
-        if cache is None or cache[0] != key:
-            cw = []
-            for ci, bi in ((0, 1), (4, 5), (8, 9), (12, 13)):
-                bn = self.conv[bi]
-                cw.append(ops.prep_conv_weight_bf16(self.conv[ci].weight, eps=bn.eps, x3=x3,
-                                                    bn=(bn.weight, bn.bias, bn.running_mean, bn.running_var)))
-            self._cw16_cache = cache = (key, cw)
-        return cache[1]
+    def _fc_weights(self):
+        """The two fully connected layers as 1x1 ConvWeights (`ops.linear`)."""
+        fcs = [self.localization_fc1[0], self.localization_fc2]
+        return prepared(self, "fc", fcs, lambda: [ops.prep_conv_weight(
+            fc.weight.view(fc.out_features, fc.in_features, 1, 1), conv_bias=fc.bias) for fc in fcs])
 
     def forward(self, batch_img):
         """fp32 MFMA convolutions with BatchNorm folded in, HIP pooling kernels, the two FCs as 1x1
         convolutions over the batch.  No CPU / library-kernel path."""
         ops.require_gpu(batch_img, "LocalizationNetwork", self.training)
         n = batch_img.size(0)
-        cw = self._hip_weights()
         x = batch_img.float().contiguous()
         mode = getattr(self, "compute_dtype", None)
         if mode is None and not hasattr(self, "compute_dtype"):
@@ -103,17 +86,17 @@ class LocalizationNetwork(nn.Module):
             # bf16 configuration: the four convolutions on the bf16 matrix cores (fp32 maps in and out: operands are
             # rounded as they are staged, accumulation / bias / ReLU fp32); pooling and the two FCs stay fp32.
             # "bf16x3": the three-term split of the fp32 operands instead of a plain rounding (within the 1e-4 bar).
-            c16 = self._hip_weights_bf16(mode == "bf16x3")
-            for i in range(3):
-                x = ops.maxpool2x2(ops.conv2d_bf16([x], c16[i], 1, True, out_dtype=torch.float32))
-            x = ops.global_avgpool(ops.conv2d_bf16([x], c16[3], 1, True, out_dtype=torch.float32))
-            x = ops.linear(x, cw[4], relu=True)
-            return ops.linear(x, cw[5], relu=False).view(n, self.num_fiducial, 2)
+            cw = self._hip_weights(ops.prep_conv_weight_bf16, x3=mode == "bf16x3")
+            conv = lambda t, w: ops.conv2d_bf16([t], w, 1, True, out_dtype=torch.float32)      # noqa: E731
+        else:
+            cw = self._hip_weights()
+            conv = lambda t, w: ops.conv2d([t], w, 1, True)                                    # noqa: E731
+        fc1, fc2 = self._fc_weights()
         for i in range(3):
-            x = ops.maxpool2x2(ops.conv2d([x], cw[i], 1, True))
-        x = ops.global_avgpool(ops.conv2d([x], cw[3], 1, True))
-        x = ops.linear(x, cw[4], relu=True)
-        return ops.linear(x, cw[5], relu=False).view(n, self.num_fiducial, 2)
+            x = ops.maxpool2x2(conv(x, cw[i]))
+        x = ops.global_avgpool(conv(x, cw[3]))
+        x = ops.linear(x, fc1, relu=True)
+        return ops.linear(x, fc2, relu=False).view(n, self.num_fiducial, 2)
 
     def _forward_torch(self, batch_img):
         """TEST HOOK, never called by forward(): plain PyTorch composition of the same layers."""
@@ -135,7 +118,6 @@ class GridGenerator(nn.Module):
         self.C, self.P = k["C"], k["P"]
         self.register_buffer("inv_delta_C", torch.from_numpy(k["inv_delta_C"]))
         self.register_buffer("P_hat", torch.from_numpy(k["P_hat"]))
-        self._prep = None        # (key, P_hat_t, table_flags): device-side view of P_hat for the kernels
 
     def prepared_table(self):
         """(P_hat_t, table_flags) for the current P_hat buffer: the transposed copy the coalesced
@@ -143,16 +125,15 @@ class GridGenerator(nn.Module):
         `ops.prepare_mirror_table`), and whether the table has the reference's mirror symmetry (checked
         bitwise, once per buffer version; a checkpoint that loads a different table simply gets 0)."""
         p = self.P_hat
-        key = (p.data_ptr(), p._version, str(p.device))
-        if self._prep is None or self._prep[0] != key:
+
+        def build():
             hw = (self.rectified_img_height, self.rectified_img_width)
             if ops.table_mirror_symmetry(p, hw, self.num_fiducial):
                 P_hat_t, flags = ops.prepare_mirror_table(p, hw)
-                flags |= ops.TABLE_MIRROR4
-            else:
-                P_hat_t, flags = ops.transpose_p_hat(p), 0
-            self._prep = (key, P_hat_t, flags)
-        return self._prep[1], self._prep[2]
+                return P_hat_t, flags | ops.TABLE_MIRROR4
+            return ops.transpose_p_hat(p), 0
+
+        return prepared(self, "table", [p], build)
 
     def build_P_prime(self, batch_C_prime, device="cuda"):
         """(N, F, 2) -> (N, n, 2): `bmm(P_hat, bmm(inv_delta_C, [C'; 0]))` as two HIP kernels with the
