@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 8   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 9   /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
                                5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
@@ -41,7 +41,9 @@ extern "C" {
                                   tpspp_dgab_gate_fwd / _bwd, tpspp_cbam_train_fwd, tpspp_cbam_bwd (+ _workspace_floats);
                                8: the backbone's BatchNorm training kernels: tpspp_bn_train_stats (+ _workspace_floats as
                                   tpspp_bn_stats_workspace_floats), tpspp_bn_eval_stats, tpspp_bn_apply_fwd, tpspp_bn_bwd_reduce
-                                  (+ _workspace_floats), tpspp_bn_bwd_data */
+                                  (+ _workspace_floats), tpspp_bn_bwd_data;
+                               9: the encoder's attention training kernels, declared in tpspp_train_attn.h: tpspp_attn_train_fwd,
+                                  tpspp_attn_train_bwd, tpspp_attn_dropout_mask */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */

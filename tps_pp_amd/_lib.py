@@ -1,4 +1,4 @@
-"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h).
+"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h).
 
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
@@ -100,6 +100,16 @@ _SIGNATURES = {
     "tpspp_attn_tensor2idx_fwd": ([_f, _i, _i, _i, _i, _i, _f, _f, _f], _i),
 }
 
+# include/tpspp_train_attn.h: the encoder's attention training kernels.  A table of its own: `exported_symbols()` is the
+# list of include/tpspp.h alone.
+_u64 = ctypes.c_ulonglong
+_TRAIN_SIGNATURES = {
+    "tpspp_attn_train_fwd": ([_f, _f, _f, _l, _i, _i, _i, _i, _i, _f, ctypes.c_float, _u64, _u64, _f, _f, _f], _i),
+    "tpspp_attn_train_bwd": ([_f, _f, _f, _f, _l, _f, _f, _i, _i, _i, _i, _i, _f, ctypes.c_float, _u64, _u64, _f, _f, _f, _l,
+                              _f], _i),
+    "tpspp_attn_dropout_mask": ([_i, _i, _i, _i, ctypes.c_float, _u64, _u64, _f, _f], _i),
+}
+
 _lib = None
 
 
@@ -112,6 +122,11 @@ def exported_symbols():
     return sorted(_SIGNATURES)
 
 
+def train_symbols():
+    """Names include/tpspp_train_attn.h declares (kept in sync by tests/test_attn_train_host.py)."""
+    return sorted(_TRAIN_SIGNATURES)
+
+
 def lib():
     """The loaded library; raises if it is absent (build it: `python -m tps_pp_amd.build`)."""
     global _lib
@@ -121,7 +136,7 @@ def lib():
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in _SIGNATURES.items():
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
             fn.argtypes = argtypes
             fn.restype = restype

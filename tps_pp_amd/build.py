@@ -30,12 +30,17 @@ def sources():
     return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
 
 
+def _public_headers():
+    inc = os.path.join(ROOT, "include")
+    return sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+
+
 def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
     deps = sources() + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-        [os.path.join(ROOT, "include", "tpspp.h"), os.path.abspath(__file__)]
+        _public_headers() + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -64,7 +69,7 @@ def _build_locked(force, verbose):
     objdir = os.path.join(CSRC, ".build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
-        [os.path.join(ROOT, "include", "tpspp.h"), os.path.abspath(__file__)]
+        _public_headers() + [os.path.abspath(__file__)]
     hdr_t = max(os.path.getmtime(h) for h in headers)
     cflags = [f for f in FLAGS if f != "-shared"] + ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
 

@@ -12,7 +12,9 @@ The sub-modules below only HOLD parameters (so `state_dict` matches); the arithm
 encoder / decoder call is one C-ABI call (`tpspp_nrtr_encoder_fwd` / `tpspp_nrtr_decoder_fwd`) that
 enqueues hand-written HIP kernels: there is no CPU or library-kernel path for inference, and the modules raise on
 CPU tensors.  Under `.train()` (round 5) encoder and decoder run as PyTorch compositions of the same layers so that
-autograd reaches their parameters (`_forward_graph`, `_forward_train_graph`).  The decoder is incremental (one position per step against cached
+autograd reaches their parameters (`_forward_graph`, `_forward_train_graph`); `NRTREncoder.set_train_backend("hip")` moves
+the encoder's training graph onto HIP kernels as well (masked attention with dropout forward and backward:
+tpspp_attn_train.hip).  The decoder is incremental (one position per step against cached
 keys/values) where the reference re-runs the padded sequence every step; results agree to fp32
 rounding (see tests/test_gpu_head.py).
 """
@@ -110,14 +112,19 @@ def _f32(t):
     return t.detach().float().contiguous()
 
 
+def _valid_counts(img_metas, n, t):
+    """The mask lengths of `_get_mask` as host integers: min(T, ceil(T * valid_ratio)) per image."""
+    ratios = [m.get("valid_ratio", 1.0) for m in img_metas]
+    if len(ratios) != n:
+        raise ValueError("img_metas must hold one dict per image")
+    return [min(t, math.ceil(t * r)) for r in ratios]
+
+
 def _valid_len(img_metas, n, t, device):
     """`_get_mask` of encoder and decoder: the first min(T, ceil(T * valid_ratio)) tokens are valid."""
     if img_metas is None:
         return None
-    ratios = [m.get("valid_ratio", 1.0) for m in img_metas]
-    if len(ratios) != n:
-        raise ValueError("img_metas must hold one dict per image")
-    vals = [min(t, math.ceil(t * r)) for r in ratios]
+    vals = _valid_counts(img_metas, n, t)
     if torch.device(device).type != "cuda":
         return torch.tensor(vals, dtype=torch.int32, device=device)
     # pinned staging + asynchronous copy: `torch.tensor(..., device=cuda)` copies from pageable memory, which blocks the HOST until
@@ -236,9 +243,49 @@ class NRTREncoder(nn.Module):
             x = x + _ffn_graph(lyr.mlp, Fn.layer_norm(x, (c,), lyr.norm2.weight, lyr.norm2.bias, lyr.norm2.eps), p, tr)
         return Fn.layer_norm(x, (c,), self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
 
+    def set_train_backend(self, mode):
+        """Which kernels the encoder's training graph (`.train()`, or eval mode with an input that carries gradients) runs
+        on: "torch" (default) -- the PyTorch composition of its layers (`_forward_graph`); "hip" -- every matrix product,
+        the masked attention with its dropout, every LayerNorm and the GELU on HIP kernels forward and backward
+        (`ops.encoder_layer_autograd`: tpspp_attn_train.hip around the regressor's Linear / LayerNorm kernels; the
+        residual additions and the two element-wise dropouts of a layer stay PyTorch ops).  No effect on the eval path."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")
+
+    def _forward_train_hip(self, feat, img_metas=None):
+        """`_forward_graph` on the HIP training kernels, always fp32.  The seed of the attention dropout is drawn once per
+        call from PyTorch's default CPU generator (torch.manual_seed reproduces a run); layer l uses offset l."""
+        n, c, h, w = feat.shape
+        t = h * w
+        if c != self.d_model:
+            raise ValueError(f"NRTREncoder: feature width {c} != d_model {self.d_model}")
+        if t > 256:
+            raise ValueError(f"NRTREncoder: at most 256 tokens on the HIP training path, got {t}")
+        vl = None
+        if img_metas is not None:
+            counts = _valid_counts(img_metas, n, t)
+            if min(counts) <= 0:
+                raise ValueError("NRTREncoder: a valid_ratio that masks every token of an image (mask length 0): the "
+                                 "softmax over no key is undefined (PyTorch's composition gives NaN)")
+            vl = _valid_len(img_metas, n, t, feat.device)
+        p = self.dropout_p if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if p > 0 else 0
+        x = feat.reshape(n, c, t).permute(0, 2, 1).contiguous()
+        for i, lyr in enumerate(self.layer_stack):
+            x = ops.encoder_layer_autograd(x, lyr, vl, p, seed, i)
+        return ops.token_ln_autograd(x, self.layer_norm)
+
     def forward(self, feat, img_metas=None):
         if self.training or (torch.is_grad_enabled() and feat.requires_grad):
             ops.require_gpu(feat, "NRTREncoder")
+            if self.train_backend == "hip":
+                return self._forward_train_hip(feat.float(), img_metas)
             return self._forward_graph(feat.float(), img_metas)
         ops.require_gpu(feat, "NRTREncoder")
         ops.warn_detached_once(self, "NRTREncoder")
@@ -598,11 +645,12 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
-    def set_train_backend(self, mode, backbone=None):
+    def set_train_backend(self, mode, backbone=None, encoder=None):
         """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
         "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).
         backbone: None leaves the backbone's train backend as it is; "torch" or "hip" sets it as well
-        (ResNetABI_v2_large.set_train_backend).  No effect on the eval path."""
+        (ResNetABI_v2_large.set_train_backend).  encoder: the same for the encoder (NRTREncoder.set_train_backend).
+        No effect on the eval path."""
         if mode not in ("torch", "hip", "hip_all"):
             raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
         if backbone is not None:
@@ -610,10 +658,17 @@ class EncodeDecodeRecognizer(nn.Module):
                 raise ValueError(f'set_train_backend: backbone must be None, "torch" or "hip", got {backbone!r}')
             if not hasattr(self.backbone, "set_train_backend"):
                 raise ValueError(f"set_train_backend: {type(self.backbone).__name__} has no HIP training path")
+        if encoder is not None:
+            if encoder not in ("torch", "hip"):
+                raise ValueError(f'set_train_backend: encoder must be None, "torch" or "hip", got {encoder!r}')
+            if not hasattr(self.encoder, "set_train_backend"):
+                raise ValueError(f"set_train_backend: {type(self.encoder).__name__} has no HIP training path")
         if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
             self.tpsnet.set_train_backend(mode)
         if backbone is not None:
             self.backbone.set_train_backend(backbone)
+        if encoder is not None:
+            self.encoder.set_train_backend(encoder)
         return self
 
     def extract_feat(self, img, test=False, **kwargs):

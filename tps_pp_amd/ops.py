@@ -2258,3 +2258,297 @@ def bn_block_autograd(x, blk, cws=None, name="block"):
                None if ds is None else prep_conv_weight_device(wd))
     return _BnBlockFunction.apply(x, blk.conv1.weight, blk.bn1.weight, blk.bn1.bias, blk.conv2.weight, blk.bn2.weight,
                                   blk.bn2.bias, wd, gd, bd, (tuple(cws), (kst1, kst2, kstd), (s1, s2, sd)))
+
+
+# ---- training graph of the NRTR encoder (NRTREncoder.set_train_backend("hip"), tpspp_attn_train.hip) -------------------
+# Scaled-dot-product attention with the valid_ratio key mask and dropout on the probabilities, forward and backward
+# (include/tpspp_train_attn.h), and around it an encoder layer composed of the kernels above: `tpspp_plane_ln_*`,
+# `tpspp_mm_f32` (q / k / v as one product, GELU as w_1's epilogue), `tpspp_linear_bwd_weight`, `tpspp_act_bwd`.  Each
+# layer is two once-differentiable functions (norm1 - attention - fc, norm2 - w_1 - GELU - w_2); the two element-wise
+# dropouts and the residual additions between them stay PyTorch element-wise ops.
+
+_U64 = (1 << 64) - 1
+
+
+def _row_stride(t):
+    """Row stride of an (N, T, C) operand whose tokens lie one row stride apart with contiguous columns, else None."""
+    N, T, C = t.shape
+    if C > 1 and t.stride(2) != 1:
+        return None
+    if T > 1:
+        ld = t.stride(1)
+        if N > 1 and t.stride(0) != T * ld:
+            return None
+    else:
+        ld = t.stride(0) if N > 1 else C
+    return ld if ld >= C else None
+
+
+def _attn_operands(who, q, k, v):
+    """q (N, Tq, C), k / v (N, Tk, C) as the kernels take them: one row stride for the three (views of one fused
+    (N, T, 3C) projection pass as they are), dense copies otherwise."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _chk_gpu(f"{who} {name}", t)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who} {name}: expected float32, got {t.dtype}")
+        if t.dim() != 3:
+            raise ValueError(f"{who} {name}: expected (N, T, C), got {tuple(t.shape)}")
+    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise ValueError(f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit together")
+    lds = {_row_stride(t) for t in (q, k, v)}
+    if len(lds) != 1 or None in lds:
+        q, k, v = (t.contiguous() for t in (q, k, v))
+        return q, k, v, q.shape[2]
+    return q, k, v, lds.pop()
+
+
+def _attn_valid_len(who, valid_len, N, dev):
+    if valid_len is None:
+        return None
+    valid_len = _chk(f"{who} valid_len", valid_len, 1, (torch.int32,))
+    if valid_len.shape[0] != N or valid_len.device != dev:
+        raise ValueError(f"{who}: valid_len must be {N} int32 lengths on {dev}")
+    return valid_len
+
+
+def attn_train_fwd(q, k, v, ld, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset):
+    """`tpspp_attn_train_fwd` on raw operands (rows `ld` elements apart): (out (N*Tq, C), lse (N, heads, Tq))."""
+    out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
+    lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_attn_train_fwd(_ptr(q), _ptr(k), _ptr(v), ld, N, C, heads, Tq, Tk, _ptr(valid_len),
+                                               float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(out), _ptr(lse),
+                                               _stream(q)), "tpspp_attn_train_fwd")
+    return out, lse
+
+
+def attn_train_bwd(d_out, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset, dq, dk, dv, ld_grad):
+    """`tpspp_attn_train_bwd`: writes dq (N*Tq rows), dk, dv (N*Tk rows), rows `ld_grad` elements apart."""
+    _lib.check(_lib.lib().tpspp_attn_train_bwd(_ptr(d_out), _ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), N, C, heads,
+                                               Tq, Tk, _ptr(valid_len), float(drop_p), int(seed) & _U64, int(offset) & _U64,
+                                               _ptr(dq), _ptr(dk), _ptr(dv), ld_grad, _stream(d_out)),
+               "tpspp_attn_train_bwd")
+
+
+def attn_dropout_mask(N, heads, Tq, Tk, drop_p, seed, offset, device):
+    """`tpspp_attn_dropout_mask`: the (N, heads, Tq, Tk) uint8 keep mask the attention kernels apply for
+    (seed, offset, drop_p).  For tests and debugging."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.TpsppError(f"attn_dropout_mask: device is {device}; the HIP path needs a GPU (no CPU fallback)")
+    mask = torch.empty((N, heads, Tq, Tk), device=device, dtype=torch.uint8)
+    _lib.check(_lib.lib().tpspp_attn_dropout_mask(N, heads, Tq, Tk, float(drop_p), int(seed) & _U64, int(offset) & _U64,
+                                                  _ptr(mask), torch.cuda.current_stream(device).cuda_stream),
+               "tpspp_attn_dropout_mask")
+    return mask
+
+
+class _AttnTrainFunction(torch.autograd.Function):
+    """Attention of `transformer_module.py:24-33` per head.  Saves q, k, v, out and the log-sum-exp; the backward
+    recomputes the probabilities and regenerates the dropout mask from (seed, offset)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, valid_len, cfg):
+        drop_p, seed, offset = cfg
+        q, k, v, ld = _attn_operands("attn_train_autograd", q, k, v)
+        N, Tq, C = q.shape
+        Tk, heads = k.shape[1], C // 64
+        out, lse = attn_train_fwd(q, k, v, ld, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset)
+        ctx.save_for_backward(q, k, v, out, lse, valid_len)
+        ctx.cfg = (ld, drop_p, seed, offset)
+        return out.view(N, Tq, C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        q, k, v, out, lse, valid_len = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * 5
+        ld, drop_p, seed, offset = ctx.cfg
+        N, Tq, C = q.shape
+        Tk, heads = k.shape[1], C // 64
+        gout = gout.float().contiguous()
+        dq = torch.empty((N, Tq, C), device=q.device, dtype=torch.float32)
+        dk = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
+        dv = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
+        attn_train_bwd(gout, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset, dq, dk, dv, C)
+        return dq, dk, dv, None, None
+
+
+def attn_train_autograd(q, k, v, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """Differentiable multi-head attention on projected q (N, Tq, C), k, v (N, Tk, C), head h = columns [64h, 64h + 64):
+    dropout(softmax(mask(q k^T / 8))) v -> (N, Tq, C) (`tpspp_attn_train_fwd` / `_bwd`).  Keys j >= valid_len[b] (int32,
+    on the device) are masked; the dropout keep decision of element (b, h, i, j) is a pure function of (seed, offset,
+    b, h, i, j) (`attn_dropout_mask` materialises it).  Views of one fused (N, T, 3C) projection are read in place."""
+    if not 0.0 <= float(drop_p) < 1.0:
+        raise ValueError(f"attn_train_autograd: drop_p must lie in [0, 1), got {drop_p!r}")
+    _chk_gpu("attn_train_autograd q", q)
+    if q.dim() != 3 or q.shape[2] % 64:
+        raise ValueError(f"attn_train_autograd: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
+    valid_len = _attn_valid_len("attn_train_autograd", valid_len, q.shape[0], q.device)
+    return _AttnTrainFunction.apply(q, k, v, valid_len, (float(drop_p), int(seed), int(offset)))
+
+
+class _AttnBlockFunction(torch.autograd.Function):
+    """norm1 - q / k / v projections (one product) - attention - fc of a TFEncoderLayer on x (N, T, C).  Saves x, the
+    LayerNorm statistics, the fused projection, the attention output and its log-sum-exp; the LayerNorm output is
+    recomputed in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg):
+        eps, drop_p, seed, offset = cfg
+        N, T, C = x.shape
+        M, heads = N * T, C // 64
+        y, m1, r1 = plane_ln_fwd(x, n1w, n1b, eps)
+        wqkv = torch.cat([wq, wk, wv], dim=0)
+        bqkv = None if bq is None else torch.cat([bq, bk, bv])
+        qkv = linear_fwd(y, _dense(M, C), wqkv, bqkv)
+        out, lse = attn_train_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], 3 * C, N, C, heads, T, T, valid_len, drop_p, seed, offset)
+        a = linear_fwd(out, _dense(M, C), fcw, fcb)
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len)
+        return a.view(N, T, C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ga):
+        x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:11]):
+            return (None,) * 13
+        eps, drop_p, seed, offset = ctx.cfg
+        N, T, C = x.shape
+        M, heads = N * T, C // 64
+        dev = x.device
+        ga = ga.float().contiguous()
+        dw_fc, db_fc = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[9], need[10])
+        dout = linear_bwd_data(ga, fcw, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
+        dqkv = torch.empty((M, 3 * C), device=dev, dtype=torch.float32)
+        attn_train_bwd(dout, qkv, qkv[:, C:], qkv[:, 2 * C:], 3 * C, out, lse, N, C, heads, T, T, valid_len, drop_p, seed,
+                       offset, dqkv, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C)
+        del dout
+        y, _, _ = plane_ln_fwd(x, n1w, n1b, eps)
+        dw = db = None
+        if any(need[3:9]):
+            dw, db = linear_bwd_weight(dqkv, y, _dense(M, C), 3 * C, C, any(need[3:6]), any(need[6:9]))
+        del y
+        res = [None] * 13
+        if any(need[:3]):
+            dy = linear_bwd_data(dqkv, wqkv, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
+            dx = torch.empty_like(x) if need[0] else None
+            dw_ln, db_ln = plane_ln_bwd(dy, x, n1w, m1, r1, dx=dx, want_params=need[1] or need[2])
+            res[0], res[1], res[2] = dx, dw_ln if need[1] else None, db_ln if need[2] else None
+        for i in range(3):
+            if dw is not None and need[3 + i]:
+                res[3 + i] = dw[i * C:(i + 1) * C]
+            if db is not None and need[6 + i]:
+                res[6 + i] = db[i * C:(i + 1) * C]
+        res[9], res[10] = dw_fc, db_fc
+        return tuple(res)
+
+
+def attn_block_autograd(x, attn, norm, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """fc(attention(norm(x))) of a TFEncoderLayer (`transformer_layers.py:57-75` up to the first dropout) on tokens x
+    (N, T, C), differentiable, on HIP kernels only.  attn: the MultiHeadAttention parameter holder, norm: its LayerNorm."""
+    x = _chk("attn_block_autograd x", x, 3)
+    N, T, C = x.shape
+    if C != attn.dim_k or attn.d_k != 64 or attn.d_v != 64:
+        raise ValueError(f"attn_block_autograd: token width {C} against {attn.n_head} heads of {attn.d_k}")
+    if T > 256:
+        raise ValueError(f"attn_block_autograd: at most 256 tokens, got {T}")
+    if not 0.0 <= float(drop_p) < 1.0:
+        raise ValueError(f"attn_block_autograd: drop_p must lie in [0, 1), got {drop_p!r}")
+    biases = (attn.linear_q.bias, attn.linear_k.bias, attn.linear_v.bias)
+    if any(b is None for b in biases) and not all(b is None for b in biases):
+        raise ValueError("attn_block_autograd: linear_q / _k / _v must all have a bias or none")
+    valid_len = _attn_valid_len("attn_block_autograd", valid_len, N, x.device)
+    return _AttnBlockFunction.apply(x, norm.weight, norm.bias, attn.linear_q.weight, attn.linear_k.weight,
+                                    attn.linear_v.weight, *biases, attn.fc.weight, attn.fc.bias, valid_len,
+                                    (float(norm.eps), float(drop_p), int(seed), int(offset)))
+
+
+class _FfnBlockFunction(torch.autograd.Function):
+    """norm2 - w_1 - GELU - w_2 of a TFEncoderLayer.  Saves x and the LayerNorm statistics; the LayerNorm output and w_1's
+    pre-activation are recomputed in the backward (GELU of it inside w_2's weight-gradient staging)."""
+
+    @staticmethod
+    def forward(ctx, x, nw, nb, w1, b1, w2, b2, eps):
+        N, T, C = x.shape
+        M = N * T
+        xn, m, r = plane_ln_fwd(x, nw, nb, eps)
+        g = linear_fwd(xn, _dense(M, C), w1, b1, epi=2)
+        f = linear_fwd(g, _dense(M, w1.shape[0]), w2, b2)
+        ctx.eps = eps
+        ctx.save_for_backward(x, m, r, nw, nb, w1, b1, w2)
+        return f.view(N, T, C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gf):
+        x, m, r, nw, nb, w1, b1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:7]):
+            return (None,) * 8
+        N, T, C = x.shape
+        M, hid = N * T, w1.shape[0]
+        dev = x.device
+        gf = gf.float().contiguous()
+        xn, _, _ = plane_ln_fwd(x, nw, nb, ctx.eps)
+        u = linear_fwd(xn, _dense(M, C), w1, b1)
+        dw2, db2 = linear_bwd_weight(gf, u, _dense(M, hid), C, hid, need[5], need[6], x_gelu=True)
+        du = linear_bwd_data(gf, w2, torch.empty((M, hid), device=dev, dtype=torch.float32), _dense(M, hid))
+        act_bwd(ACT_GELU, du, u, out=du)
+        del u
+        dw1, db1 = linear_bwd_weight(du, xn, _dense(M, C), hid, C, need[3], need[4])
+        del xn
+        dx = dw_ln = db_ln = None
+        if any(need[:3]):
+            dxn = linear_bwd_data(du, w1, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
+            dx = torch.empty_like(x) if need[0] else None
+            dw_ln, db_ln = plane_ln_bwd(dxn, x, nw, m, r, dx=dx, want_params=need[1] or need[2])
+        return dx, dw_ln if need[1] else None, db_ln if need[2] else None, dw1, db1, dw2, db2, None
+
+
+def ffn_block_autograd(x, mlp, norm):
+    """w_2(GELU(w_1(norm(x)))) of a TFEncoderLayer (`transformer_module.py:119-128` up to its dropout) on tokens x
+    (N, T, C), differentiable, on HIP kernels only."""
+    x = _chk("ffn_block_autograd x", x, 3)
+    if mlp.w_1.bias is None or mlp.w_2.bias is None:
+        raise ValueError("ffn_block_autograd: w_1 and w_2 carry a bias in every NRTR config")
+    return _FfnBlockFunction.apply(x, norm.weight, norm.bias, *_lin(mlp.w_1), *_lin(mlp.w_2), float(norm.eps))
+
+
+class _TokenLnFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, eps):
+        y, m, r = plane_ln_fwd(x, w, b, eps)
+        ctx.save_for_backward(x, w, m, r)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w, m, r = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:3]):
+            return (None,) * 4
+        dx = torch.empty_like(x) if need[0] else None
+        dw, db = plane_ln_bwd(gy.float().contiguous(), x, w, m, r, dx=dx, want_params=need[1] or need[2])
+        return dx, dw if need[1] else None, db if need[2] else None, None
+
+
+def token_ln_autograd(x, ln):
+    """nn.LayerNorm `ln` over the last dimension of x, differentiable (`tpspp_plane_ln_fwd` / `_bwd`)."""
+    x = _chk("token_ln_autograd x", x)
+    return _TokenLnFunction.apply(x, ln.weight, ln.bias, float(ln.eps))
+
+
+def encoder_layer_autograd(x, lyr, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """One pre-norm TFEncoderLayer (`transformer_layers.py:57-75`) on tokens x (N, T, C) in the training graph: every
+    matrix product, softmax, LayerNorm and GELU on HIP kernels; the residual additions and the two element-wise dropouts
+    (after fc and after w_2, rate drop_p, PyTorch's generator) are PyTorch element-wise ops.  drop_p also drives the
+    dropout on the attention probabilities, seeded by (seed, offset)."""
+    import torch.nn.functional as Fn
+    a = attn_block_autograd(x, lyr.attn, lyr.norm1, valid_len, drop_p, seed, offset)
+    x = x + Fn.dropout(a, drop_p, drop_p > 0)
+    f = ffn_block_autograd(x, lyr.mlp, lyr.norm2)
+    return x + Fn.dropout(f, drop_p, drop_p > 0)
