@@ -323,7 +323,9 @@ int tpspp_conv2d_prep_weight(const float* weight, int Cout, int Cin, int KH, int
  * for b < batch, i < M, j < N.  Element (b, i, k) of A is A[b*a_strides[0] + i*a_strides[1] + k*a_strides[2]] (B and C / R
  * likewise with b_strides, c_strides), in elements: tokens can be read from and written to NCHW maps in place.
  * epilogue: 0 none, 1 ReLU, 2 GELU (erf form), 3 tanh.  bias (N) or NULL.  k_total > 0 splits one long reduction over the
- * batch (K_b = min(K, k_total - b*K)), <= 0: K_b = K.  C must not alias A, B or R.
+ * batch (K_b = min(K, k_total - b*K); k_total <= batch * K), <= 0: K_b = K.  A trailing entry with K_b <= 0 is an empty
+ * sum, C[b] = epi(bias) (+ R[b]), and reads neither A nor B; no entry reads k >= K_b.  batch, M or N of 0: success, nothing
+ * written.  Only the addressed elements of C are written.  C must not alias A, B or R.
  * replaces: nn.Linear (+ ReLU / GELU) and the score's einsum + tanh in the autograd graph of backbones/tps_pp/DGAB.py:7-23,55,
  *           backbones/tps_pp/tps_pp.py:293-323
  */
