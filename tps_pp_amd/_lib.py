@@ -1,4 +1,4 @@
-"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h).
+"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h, include/tpspp_train_dec.h).
 
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
@@ -110,6 +110,19 @@ _TRAIN_SIGNATURES = {
     "tpspp_attn_dropout_mask": ([_i, _i, _i, _i, ctypes.c_float, _u64, _u64, _f, _f], _i),
 }
 
+# include/tpspp_train_dec.h: the decoder's attention, its embedding and the sequence cross-entropy.  A table of its own
+# again: tests pin the exact name sets of the other two.
+_DEC_TRAIN_SIGNATURES = {
+    "tpspp_attn_train_fwd_ex": ([_f, _l, _f, _f, _l, _i, _i, _i, _i, _i, _f, _f, _i, ctypes.c_float, _u64, _u64, _f, _f, _f], _i),
+    "tpspp_attn_train_bwd_ex": ([_f, _f, _l, _f, _f, _l, _f, _f, _i, _i, _i, _i, _i, _f, _f, _i, ctypes.c_float, _u64, _u64,
+                                 _f, _l, _f, _f, _l, _f], _i),
+    "tpspp_embed_pos_fwd": ([_f, _f, _f, _i, _i, _i, _i, _f, _f], _i),
+    "tpspp_embed_bwd_workspace_floats": ([_l, _i, _i], ctypes.c_size_t),
+    "tpspp_embed_bwd": ([_f, _f, _l, _i, _i, _i, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_seq_ce_fwd": ([_f, _l, _l, _l, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f], _i),
+    "tpspp_seq_ce_bwd": ([_f, _f, _l, _l, _l, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f], _i),
+}
+
 _lib = None
 
 
@@ -127,6 +140,11 @@ def train_symbols():
     return sorted(_TRAIN_SIGNATURES)
 
 
+def dec_train_symbols():
+    """Names include/tpspp_train_dec.h declares (kept in sync by tests/test_dec_train_host.py)."""
+    return sorted(_DEC_TRAIN_SIGNATURES)
+
+
 def lib():
     """The loaded library; raises if it is absent (build it: `python -m tps_pp_amd.build`)."""
     global _lib
@@ -136,7 +154,8 @@ def lib():
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()):
+        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + \
+                list(_DEC_TRAIN_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
             fn.argtypes = argtypes
             fn.restype = restype

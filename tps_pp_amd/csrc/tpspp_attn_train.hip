@@ -1,5 +1,6 @@
-// Training kernels of the NRTR encoder's attention (include/tpspp_train_attn.h): scaled-dot-product attention with the
-// valid_ratio key mask and dropout on the probabilities, forward and backward, exact fp32.
+// Training kernels of the NRTR encoder's and decoder's attention (include/tpspp_train_attn.h, and its generalisation
+// tpspp_attn_train_fwd_ex / _bwd_ex of include/tpspp_train_dec.h): scaled-dot-product attention with a key mask
+// (valid_ratio prefix, per-key mask, causal) and dropout on the probabilities, forward and backward, exact fp32.
 //
 // replaces: the autograd of common/modules/transformer_module.py:24-33,71-96 (reference, mmocr/models/) in the
 // training graph; tps_pp_amd/ops.py composes it with tpspp_mm_f32 / tpspp_plane_ln_* / tpspp_linear_bwd_weight /
@@ -13,7 +14,8 @@
 // take without bank conflicts.
 //   * attn_train_fwd_kernel, one workgroup per (image, head, block of 64 queries), q in registers.  Pass A walks the
 //     key blocks and keeps a running row maximum and sum (lse = max + log(sum)); pass B recomputes each S block, forms
-//     P = exp(S - lse), applies the dropout and accumulates out += P v.  Key blocks past valid_len are never read.
+//     P = exp(S - lse), applies the dropout and accumulates out += P v.  Key blocks past valid_len, or (causal) wholly
+//     above the diagonal of the query block, are never read.
 //   * attn_train_bwd_dq_kernel, the same ownership: dS = P * (dropout'(d_out v^T) - rowsum(d_out * out)) per key
 //     block, dq += dS k.
 //   * attn_train_bwd_dkv_kernel, one workgroup per (image, head, block of 64 keys), k and v in registers: it walks the
@@ -24,6 +26,7 @@
 // holds, so a lane makes 4 Philox calls for its 16 elements of a block.  Bitwise reproducible: no atomics, fixed orders.
 #include "tpspp_common.h"
 #include "tpspp_train_attn.h"
+#include "tpspp_train_dec.h"
 
 #include <math.h>
 
@@ -51,7 +54,9 @@ struct AttnParams {
     float* dk;
     float* dv;
     const int* valid_len;
-    long long ld, ldg;
+    const unsigned char* key_mask;   // (N, Tk), 0 = masked, or NULL
+    long long ld_q, ld_kv, ld_dq, ld_dkv;
+    int causal;
     int N, C, heads, Tq, Tk;
     unsigned drop_thr;        // floor(drop_p * 2^32); 0: no dropout
     float inv_keep;           // 1 / (1 - drop_p)
@@ -158,6 +163,18 @@ __device__ __forceinline__ int valid_keys(const AttnParams& P, int b)
     return vl;
 }
 
+// is key j0 + jl of image b (one of the `ncols` keys of its block below valid_len) visible to any query at all
+__device__ __forceinline__ bool key_visible(const AttnParams& P, int b, int j0, int jl, int ncols)
+{
+    return jl < ncols && (!P.key_mask || P.key_mask[(long long)b * P.Tk + j0 + jl] != 0);
+}
+
+// the keys a block of queries that ends before row `iend` walks: those below valid_len, causal: and not past its last row
+__device__ __forceinline__ int walked_keys(const AttnParams& P, int vl, int iend)
+{
+    return (P.causal && iend < vl) ? iend : vl;
+}
+
 // sD[row] = sum_d a[row][d] * b[row][d] for the 64 rows of a block (0 for row >= nrows): one thread per row, one fmaf
 // chain over d ascending from 0 -- the order of the MFMA's own k chain, so that for a row with a single valid key and no
 // dropout (out == v) this is bit for bit the d_out . v the kernels form on the matrix cores, and dS is an exact zero as
@@ -189,61 +206,68 @@ attn_train_fwd_kernel(const AttnParams P)
     const int b = blockIdx.x / nqb, i0 = (blockIdx.x % nqb) * BT, h = blockIdx.y;
     const int vl = valid_keys(P, b);
     const int nrows = P.Tq - i0 < BT ? P.Tq - i0 : BT;
-    const float* kb = P.k + (long long)b * P.Tk * P.ld + h * BT;
-    const float* vb = P.v + (long long)b * P.Tk * P.ld + h * BT;
+    const int kend = walked_keys(P, vl, i0 + nrows);
+    const float* kb = P.k + (long long)b * P.Tk * P.ld_kv + h * BT;
+    const float* vb = P.v + (long long)b * P.Tk * P.ld_kv + h * BT;
     const int im = wm * 32 + l31, jn = wn * 32 + l31;
 
     float qr[32];
-    load_rows(qr, P.q + ((long long)b * P.Tq + i0) * P.ld + h * BT, P.ld, im, nrows, half);
+    load_rows(qr, P.q + ((long long)b * P.Tq + i0) * P.ld_q + h * BT, P.ld_q, im, nrows, half);
     if (tid < BT) {
         sM[tid] = -INFINITY;
         sL[tid] = 0.0f;
     }
 
-    // pass A: running maximum and sum of every row over the valid keys
-    for (int j0 = 0; j0 < vl; j0 += BT) {
+    // pass A: running maximum and sum of every row over its visible keys (a masked logit is staged as -inf)
+    for (int j0 = 0; j0 < kend; j0 += BT) {
         const int ncols = vl - j0 < BT ? vl - j0 : BT;
+        const bool kvis = key_visible(P, b, j0, jn, ncols);
         __syncthreads();
-        load_tile(sK, kb + (long long)j0 * P.ld, P.ld, ncols, tid);
+        load_tile(sK, kb + (long long)j0 * P.ld_kv, P.ld_kv, ncols, tid);
         __syncthreads();
         const f32x16 s = mm_reg_lds<ROW>(qr, sK, jn, half, zero16());
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sS[wm * 32 + acc_row(r, half)][jn] = kScale * s[r];
+        for (int r = 0; r < 16; ++r) {
+            const int il = wm * 32 + acc_row(r, half);
+            sS[il][jn] = (kvis && (!P.causal || j0 + jn <= i0 + il)) ? kScale * s[r] : -INFINITY;
+        }
         __syncthreads();
         const int row = tid >> 2, c0 = (tid & 3) * 16;
         float mx = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c0 + c < ncols) mx = fmaxf(mx, sS[row][c0 + c]);
+        for (int c = 0; c < 16; ++c) mx = fmaxf(mx, sS[row][c0 + c]);
         mx = fmaxf(mx, __shfl_xor(mx, 1));
         mx = fmaxf(mx, __shfl_xor(mx, 2));
+        // a row with no visible key in this block (mx == -inf) keeps its maximum and sum: its terms below are
+        // exp(-inf - 0) = 0 and the update is skipped, so -inf - -inf never arises
+        const bool any = mx > -INFINITY;
         const float m_old = sM[row];
-        const float m_new = fmaxf(m_old, mx);       // finite: column 0 of every block walked here is a valid key
+        const float m_new = any ? fmaxf(m_old, mx) : 0.0f;
         float sum = 0.0f;
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c0 + c < ncols) sum = sum + expf(sS[row][c0 + c] - m_new);
+        for (int c = 0; c < 16; ++c) sum = sum + expf(sS[row][c0 + c] - m_new);
         sum = sum + __shfl_xor(sum, 1);
         sum = sum + __shfl_xor(sum, 2);
-        if ((tid & 3) == 0) {
+        if ((tid & 3) == 0 && any) {
             sL[row] = sL[row] * expf(m_old - m_new) + sum;
             sM[row] = m_new;
         }
     }
     __syncthreads();
     if (tid < BT) {
-        const float lse = vl > 0 ? sM[tid] + logf(sL[tid]) : -INFINITY;
+        const float lse = sM[tid] > -INFINITY ? sM[tid] + logf(sL[tid]) : -INFINITY;     // -inf: no visible key at all
         sM[tid] = lse;
         if (tid < nrows) P.lse[((long long)b * P.heads + h) * P.Tq + i0 + tid] = lse;
     }
 
     // pass B: P = exp(S - lse), dropout, out += P v
     f32x16 o = zero16();
-    for (int j0 = 0; j0 < vl; j0 += BT) {
+    for (int j0 = 0; j0 < kend; j0 += BT) {
         const int ncols = vl - j0 < BT ? vl - j0 : BT;
+        const bool kvis = key_visible(P, b, j0, jn, ncols);
         __syncthreads();
-        load_tile(sK, kb + (long long)j0 * P.ld, P.ld, ncols, tid);
-        load_tile(sV, vb + (long long)j0 * P.ld, P.ld, ncols, tid);
+        load_tile(sK, kb + (long long)j0 * P.ld_kv, P.ld_kv, ncols, tid);
+        load_tile(sV, vb + (long long)j0 * P.ld_kv, P.ld_kv, ncols, tid);
         __syncthreads();
         const f32x16 s = mm_reg_lds<ROW>(qr, sK, jn, half, zero16());
 #pragma unroll
@@ -254,7 +278,7 @@ attn_train_fwd_kernel(const AttnParams P)
             for (int e = 0; e < 4; ++e) {
                 const int r = 4 * g + e;
                 const int il = wm * 32 + acc_row(r, half);
-                float p = jn < ncols ? expf(kScale * s[r] - sM[il]) : 0.0f;
+                float p = (kvis && (!P.causal || j0 + jn <= i0 + il)) ? expf(kScale * s[r] - sM[il]) : 0.0f;
                 if (P.drop_thr) p = w[e] >= P.drop_thr ? p * P.inv_keep : 0.0f;
                 sS[il][jn] = p;
             }
@@ -283,23 +307,25 @@ attn_train_bwd_dq_kernel(const AttnParams P)
     const int b = blockIdx.x / nqb, i0 = (blockIdx.x % nqb) * BT, h = blockIdx.y;
     const int vl = valid_keys(P, b);
     const int nrows = P.Tq - i0 < BT ? P.Tq - i0 : BT;
-    const float* kb = P.k + (long long)b * P.Tk * P.ld + h * BT;
-    const float* vb = P.v + (long long)b * P.Tk * P.ld + h * BT;
+    const int kend = walked_keys(P, vl, i0 + nrows);
+    const float* kb = P.k + (long long)b * P.Tk * P.ld_kv + h * BT;
+    const float* vb = P.v + (long long)b * P.Tk * P.ld_kv + h * BT;
     const long long orow = ((long long)b * P.Tq + i0) * P.C + h * BT;     // d_out and out are dense (N*Tq, C)
     const int im = wm * 32 + l31, jn = wn * 32 + l31;
 
     float qr[32], gr[32];
-    load_rows(qr, P.q + ((long long)b * P.Tq + i0) * P.ld + h * BT, P.ld, im, nrows, half);
+    load_rows(qr, P.q + ((long long)b * P.Tq + i0) * P.ld_q + h * BT, P.ld_q, im, nrows, half);
     load_rows(gr, P.d_out + orow, P.C, im, nrows, half);
     row_dots(sD, P.d_out + orow, P.out_in + orow, P.C, nrows, tid);
     if (tid < BT) sLse[tid] = tid < nrows ? P.lse_in[((long long)b * P.heads + h) * P.Tq + i0 + tid] : 0.0f;
 
     f32x16 dq = zero16();
-    for (int j0 = 0; j0 < vl; j0 += BT) {
+    for (int j0 = 0; j0 < kend; j0 += BT) {
         const int ncols = vl - j0 < BT ? vl - j0 : BT;
+        const bool kvis = key_visible(P, b, j0, jn, ncols);
         __syncthreads();
-        load_tile(sK, kb + (long long)j0 * P.ld, P.ld, ncols, tid);
-        load_tile(sV, vb + (long long)j0 * P.ld, P.ld, ncols, tid);
+        load_tile(sK, kb + (long long)j0 * P.ld_kv, P.ld_kv, ncols, tid);
+        load_tile(sV, vb + (long long)j0 * P.ld_kv, P.ld_kv, ncols, tid);
         __syncthreads();
         const f32x16 s = mm_reg_lds<ROW>(qr, sK, jn, half, zero16());
         const f32x16 dp = mm_reg_lds<ROW>(gr, sV, jn, half, zero16());
@@ -311,7 +337,8 @@ attn_train_bwd_dq_kernel(const AttnParams P)
             for (int e = 0; e < 4; ++e) {
                 const int r = 4 * g + e;
                 const int il = wm * 32 + acc_row(r, half);
-                const float p = (jn < ncols && il < nrows) ? expf(kScale * s[r] - sLse[il]) : 0.0f;
+                const bool vis = kvis && il < nrows && (!P.causal || j0 + jn <= i0 + il);
+                const float p = vis ? expf(kScale * s[r] - sLse[il]) : 0.0f;
                 float d = dp[r];
                 if (P.drop_thr) d = w[e] >= P.drop_thr ? d * P.inv_keep : 0.0f;
                 sS[il][jn] = p * (d - sD[il]);
@@ -323,7 +350,7 @@ attn_train_bwd_dq_kernel(const AttnParams P)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int il = wm * 32 + acc_row(r, half);
-        if (il < nrows) P.dq[((long long)b * P.Tq + i0 + il) * P.ldg + h * BT + jn] = kScale * dq[r];
+        if (il < nrows) P.dq[((long long)b * P.Tq + i0 + il) * P.ld_dq + h * BT + jn] = kScale * dq[r];
     }
 }
 
@@ -342,12 +369,12 @@ attn_train_bwd_dkv_kernel(const AttnParams P)
     const int vl = valid_keys(P, b);
     const int nkeys = P.Tk - j0 < BT ? P.Tk - j0 : BT;                       // rows of dk / dv this workgroup owns
     const int ncols = vl - j0 < 0 ? 0 : (vl - j0 < BT ? vl - j0 : BT);       // ... of which valid keys
-    const long long grow = ((long long)b * P.Tk + j0) * P.ldg + h * BT;
+    const long long grow = ((long long)b * P.Tk + j0) * P.ld_dkv + h * BT;
     const int im = wm * 32 + l31, jn = wn * 32 + l31;
 
     if (ncols == 0) {                  // a block of masked keys: exact zeros, nothing read
         for (int e = tid; e < nkeys * BT; e += kThreads) {
-            const long long o = grow + (long long)(e >> 6) * P.ldg + (e & (BT - 1));
+            const long long o = grow + (long long)(e >> 6) * P.ld_dkv + (e & (BT - 1));
             P.dk[o] = 0.0f;
             P.dv[o] = 0.0f;
         }
@@ -355,15 +382,17 @@ attn_train_bwd_dkv_kernel(const AttnParams P)
     }
 
     float kr[32], vr[32];
-    load_rows(kr, P.k + ((long long)b * P.Tk + j0) * P.ld + h * BT, P.ld, jn, ncols, half);
-    load_rows(vr, P.v + ((long long)b * P.Tk + j0) * P.ld + h * BT, P.ld, jn, ncols, half);
+    load_rows(kr, P.k + ((long long)b * P.Tk + j0) * P.ld_kv + h * BT, P.ld_kv, jn, ncols, half);
+    load_rows(vr, P.v + ((long long)b * P.Tk + j0) * P.ld_kv + h * BT, P.ld_kv, jn, ncols, half);
+    const bool kvis = key_visible(P, b, j0, jn, ncols);
 
+    // causal: the query blocks before this key block see none of its keys (j0 is a multiple of the block size)
     f32x16 dk = zero16(), dv = zero16();
-    for (int i0 = 0; i0 < P.Tq; i0 += BT) {
+    for (int i0 = P.causal ? j0 : 0; i0 < P.Tq; i0 += BT) {
         const int nrows = P.Tq - i0 < BT ? P.Tq - i0 : BT;
         const long long orow = ((long long)b * P.Tq + i0) * P.C + h * BT;
         __syncthreads();
-        load_tile(sQ, P.q + ((long long)b * P.Tq + i0) * P.ld + h * BT, P.ld, nrows, tid);
+        load_tile(sQ, P.q + ((long long)b * P.Tq + i0) * P.ld_q + h * BT, P.ld_q, nrows, tid);
         load_tile(sG, P.d_out + orow, P.C, nrows, tid);
         row_dots(sD, P.d_out + orow, P.out_in + orow, P.C, nrows, tid);
         if (tid < BT) sLse[tid] = tid < nrows ? P.lse_in[((long long)b * P.heads + h) * P.Tq + i0 + tid] : 0.0f;
@@ -379,7 +408,8 @@ attn_train_bwd_dkv_kernel(const AttnParams P)
             for (int e = 0; e < 4; ++e) {
                 const int r = 4 * g + e;
                 const int il = wm * 32 + acc_row(r, half);
-                const float p = (jn < ncols && il < nrows) ? expf(kScale * s[r] - sLse[il]) : 0.0f;
+                const bool vis = kvis && il < nrows && (!P.causal || j0 + jn <= i0 + il);
+                const float p = vis ? expf(kScale * s[r] - sLse[il]) : 0.0f;
                 float pd = p, d = dp[r];
                 if (P.drop_thr) {
                     const bool keep = w[e] >= P.drop_thr;
@@ -402,9 +432,10 @@ attn_train_bwd_dkv_kernel(const AttnParams P)
     for (int r = 0; r < 16; ++r) {
         const int jl = wm * 32 + acc_row(r, half);
         if (jl < nkeys) {
-            const long long o = grow + (long long)jl * P.ldg + jn;
-            P.dk[o] = jl < ncols ? kScale * dk[r] : 0.0f;
-            P.dv[o] = jl < ncols ? dv[r] : 0.0f;
+            const long long o = grow + (long long)jl * P.ld_dkv + jn;
+            const bool seen = key_visible(P, b, j0, jl, ncols);       // a masked key: exact zeros
+            P.dk[o] = seen ? kScale * dk[r] : 0.0f;
+            P.dv[o] = seen ? dv[r] : 0.0f;
         }
     }
 }
@@ -441,10 +472,11 @@ int check_sizes(const char* who, int N, int heads, int Tq, int Tk, float drop_p)
     return TPSPP_OK;
 }
 
-int check_operands(const char* who, long long ld, int C, int heads)
+int check_operands(const char* who, long long ld_q, long long ld_kv, int C, int heads, int causal)
 {
     TPSPP_REQUIRE(C == BT * heads, "%s: C must be 64 * heads (d_k = d_v = 64), got C = %d, heads = %d", who, C, heads);
-    TPSPP_REQUIRE(ld >= C, "%s: row stride %lld < C = %d", who, ld, C);
+    TPSPP_REQUIRE(ld_q >= C && ld_kv >= C, "%s: row stride %lld < C = %d", who, ld_q < ld_kv ? ld_q : ld_kv, C);
+    TPSPP_REQUIRE(causal == 0 || causal == 1, "%s: causal must be 0 or 1, got %d", who, causal);
     return TPSPP_OK;
 }
 
@@ -457,27 +489,80 @@ void set_dropout(AttnParams& P, float drop_p, unsigned long long seed, unsigned 
     P.off_lo = (unsigned)offset; P.off_hi = (unsigned)(offset >> 32);
 }
 
+// the one forward and the one backward behind both pairs of entry points: P carries the operands, everything is checked here
+int attn_fwd(const char* who, AttnParams& P, float drop_p, unsigned long long seed, unsigned long long offset,
+             tpspp_stream_t stream)
+{
+    TPSPP_REQUIRE(P.q && P.k && P.v && P.out && P.lse, "%s: null pointer", who);
+    int rc = check_sizes(who, P.N, P.heads, P.Tq, P.Tk, drop_p);
+    if (rc != TPSPP_OK) return rc;
+    rc = check_operands(who, P.ld_q, P.ld_kv, P.C, P.heads, P.causal);
+    if (rc != TPSPP_OK) return rc;
+    if (P.N == 0) return TPSPP_OK;
+    set_dropout(P, drop_p, seed, offset);
+    const dim3 grid((unsigned)(P.N * ((P.Tq + BT - 1) / BT)), (unsigned)P.heads);
+    hipLaunchKernelGGL(attn_train_fwd_kernel, grid, dim3(kThreads), 0, tpspp::as_stream(stream), P);
+    return tpspp::check_launch(who);
+}
+
+int attn_bwd(const char* who, AttnParams& P, float drop_p, unsigned long long seed, unsigned long long offset,
+             tpspp_stream_t stream)
+{
+    TPSPP_REQUIRE(P.d_out && P.q && P.k && P.v && P.out_in && P.lse_in && P.dq && P.dk && P.dv, "%s: null pointer", who);
+    int rc = check_sizes(who, P.N, P.heads, P.Tq, P.Tk, drop_p);
+    if (rc != TPSPP_OK) return rc;
+    rc = check_operands(who, P.ld_q, P.ld_kv, P.C, P.heads, P.causal);
+    if (rc != TPSPP_OK) return rc;
+    TPSPP_REQUIRE(P.ld_dq >= P.C && P.ld_dkv >= P.C, "%s: gradient row stride %lld < C = %d", who,
+                  P.ld_dq < P.ld_dkv ? P.ld_dq : P.ld_dkv, P.C);
+    if (P.N == 0) return TPSPP_OK;
+    set_dropout(P, drop_p, seed, offset);
+    hipStream_t st = tpspp::as_stream(stream);
+    hipLaunchKernelGGL(attn_train_bwd_dq_kernel, dim3((unsigned)(P.N * ((P.Tq + BT - 1) / BT)), (unsigned)P.heads),
+                       dim3(kThreads), 0, st, P);
+    rc = tpspp::check_launch(who);
+    if (rc != TPSPP_OK) return rc;
+    hipLaunchKernelGGL(attn_train_bwd_dkv_kernel, dim3((unsigned)(P.N * ((P.Tk + BT - 1) / BT)), (unsigned)P.heads),
+                       dim3(kThreads), 0, st, P);
+    return tpspp::check_launch(who);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------------
+TPSPP_EXPORT int tpspp_attn_train_fwd_ex(const float* q, long long ld_q, const float* k, const float* v, long long ld_kv, int N,
+                                         int C, int heads, int Tq, int Tk, const int* valid_len,
+                                         const unsigned char* key_mask, int causal, float drop_p, unsigned long long seed,
+                                         unsigned long long offset, float* out, float* lse, tpspp_stream_t stream)
+{
+    AttnParams P = {};
+    P.q = q; P.k = k; P.v = v; P.out = out; P.lse = lse; P.valid_len = valid_len; P.key_mask = key_mask; P.causal = causal;
+    P.ld_q = ld_q; P.ld_kv = ld_kv; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
+    return attn_fwd("tpspp_attn_train_fwd_ex", P, drop_p, seed, offset, stream);
+}
+
+TPSPP_EXPORT int tpspp_attn_train_bwd_ex(const float* d_out, const float* q, long long ld_q, const float* k, const float* v,
+                                         long long ld_kv, const float* out, const float* lse, int N, int C, int heads, int Tq,
+                                         int Tk, const int* valid_len, const unsigned char* key_mask, int causal,
+                                         float drop_p, unsigned long long seed, unsigned long long offset, float* dq,
+                                         long long ld_dq, float* dk, float* dv, long long ld_dkv, tpspp_stream_t stream)
+{
+    AttnParams P = {};
+    P.q = q; P.k = k; P.v = v; P.d_out = d_out; P.out_in = out; P.lse_in = lse; P.valid_len = valid_len;
+    P.key_mask = key_mask; P.causal = causal; P.dq = dq; P.dk = dk; P.dv = dv;
+    P.ld_q = ld_q; P.ld_kv = ld_kv; P.ld_dq = ld_dq; P.ld_dkv = ld_dkv; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
+    return attn_bwd("tpspp_attn_train_bwd_ex", P, drop_p, seed, offset, stream);
+}
+
+// the encoder's entry points: a prefix mask alone, one row stride for q, k and v
 TPSPP_EXPORT int tpspp_attn_train_fwd(const float* q, const float* k, const float* v, long long ld, int N, int C, int heads,
                                       int Tq, int Tk, const int* valid_len, float drop_p, unsigned long long seed,
                                       unsigned long long offset, float* out, float* lse, tpspp_stream_t stream)
 {
-    const char* who = "tpspp_attn_train_fwd";
-    TPSPP_REQUIRE(q && k && v && out && lse, "%s: null pointer", who);
-    int rc = check_sizes(who, N, heads, Tq, Tk, drop_p);
-    if (rc != TPSPP_OK) return rc;
-    rc = check_operands(who, ld, C, heads);
-    if (rc != TPSPP_OK) return rc;
-    if (N == 0) return TPSPP_OK;
     AttnParams P = {};
     P.q = q; P.k = k; P.v = v; P.out = out; P.lse = lse; P.valid_len = valid_len;
-    P.ld = ld; P.ldg = 0; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
-    set_dropout(P, drop_p, seed, offset);
-    const dim3 grid((unsigned)(N * ((Tq + BT - 1) / BT)), (unsigned)heads);
-    hipLaunchKernelGGL(attn_train_fwd_kernel, grid, dim3(kThreads), 0, tpspp::as_stream(stream), P);
-    return tpspp::check_launch(who);
+    P.ld_q = P.ld_kv = ld; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
+    return attn_fwd("tpspp_attn_train_fwd", P, drop_p, seed, offset, stream);
 }
 
 TPSPP_EXPORT int tpspp_attn_train_bwd(const float* d_out, const float* q, const float* k, const float* v, long long ld,
@@ -486,29 +571,12 @@ TPSPP_EXPORT int tpspp_attn_train_bwd(const float* d_out, const float* q, const 
                                       unsigned long long offset, float* dq, float* dk, float* dv, long long ld_grad,
                                       tpspp_stream_t stream)
 {
-    const char* who = "tpspp_attn_train_bwd";
-    TPSPP_REQUIRE(d_out && q && k && v && out && lse && dq && dk && dv, "%s: null pointer", who);
-    int rc = check_sizes(who, N, heads, Tq, Tk, drop_p);
-    if (rc != TPSPP_OK) return rc;
-    rc = check_operands(who, ld, C, heads);
-    if (rc != TPSPP_OK) return rc;
-    TPSPP_REQUIRE(ld_grad >= C, "%s: gradient row stride %lld < C = %d", who, ld_grad, C);
-    if (N == 0) return TPSPP_OK;
     AttnParams P = {};
     P.q = q; P.k = k; P.v = v; P.d_out = d_out; P.out_in = out; P.lse_in = lse; P.valid_len = valid_len;
     P.dq = dq; P.dk = dk; P.dv = dv;
-    P.ld = ld; P.ldg = ld_grad; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
-    set_dropout(P, drop_p, seed, offset);
-    hipStream_t st = tpspp::as_stream(stream);
-    hipLaunchKernelGGL(attn_train_bwd_dq_kernel, dim3((unsigned)(N * ((Tq + BT - 1) / BT)), (unsigned)heads), dim3(kThreads), 0,
-                       st, P);
-    rc = tpspp::check_launch(who);
-    if (rc != TPSPP_OK) return rc;
-    hipLaunchKernelGGL(attn_train_bwd_dkv_kernel, dim3((unsigned)(N * ((Tk + BT - 1) / BT)), (unsigned)heads), dim3(kThreads), 0,
-                       st, P);
-    return tpspp::check_launch(who);
+    P.ld_q = P.ld_kv = ld; P.ld_dq = P.ld_dkv = ld_grad; P.N = N; P.C = C; P.heads = heads; P.Tq = Tq; P.Tk = Tk;
+    return attn_bwd("tpspp_attn_train_bwd", P, drop_p, seed, offset, stream);
 }
-
 TPSPP_EXPORT int tpspp_attn_dropout_mask(int N, int heads, int Tq, int Tk, float drop_p, unsigned long long seed,
                                          unsigned long long offset, unsigned char* mask, tpspp_stream_t stream)
 {

@@ -3,7 +3,8 @@ buildable from the same config dicts (reference: `mmocr/models/textrecog/losses/
 `encode_decode_recognizer.py:68-70` with `ignore_index = label_convertor.padding_idx`).
 
 Only `EncodeDecodeRecognizer.forward_train` -- the training graph of round 5 -- needs them; the cross-entropy itself is
-`torch.nn.functional.cross_entropy`.  One function does the work; the two registered classes only fix how outputs and
+`torch.nn.functional.cross_entropy`, or with `set_train_backend("hip")` the kernels of include/tpspp_train_dec.h
+(`ops.seq_cross_entropy_autograd`).  One function does the work; the two registered classes only fix how outputs and
 targets are aligned.  Everything else under the reference's `losses/` stays out of scope.
 """
 import torch.nn as nn
@@ -40,8 +41,24 @@ class _SequenceLoss(nn.Module):
             raise AssertionError("ignore_index must be an int, reduction one of " + ", ".join(_REDUCTIONS))
         self.ignore_index, self.reduction, self.shift, self.flatten = ignore_index, reduction, bool(shift), bool(flatten)
 
+    def set_train_backend(self, mode):
+        """ "torch" (default): `F.cross_entropy`; "hip": `tpspp_seq_ce_fwd` / `_bwd` for logits on the GPU (logits on the
+        host keep PyTorch's)."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")
+
     def forward(self, outputs, targets_dict, img_metas=None):
         """-> {'loss_ce': tensor}; `targets_dict['padded_targets']` (N, T) as `AttnConvertor.str2tensor` builds it."""
+        if self.train_backend == "hip" and outputs.is_cuda:
+            from . import ops
+            return {"loss_ce": ops.seq_cross_entropy_autograd(outputs.float(), targets_dict["padded_targets"],
+                                                              self.ignore_index, self.reduction, self.shift, self.flatten)}
         return {"loss_ce": sequence_cross_entropy(outputs, targets_dict["padded_targets"], self.ignore_index,
                                                   self.reduction, self.shift, self.flatten)}
 

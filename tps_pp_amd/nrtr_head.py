@@ -12,9 +12,9 @@ The sub-modules below only HOLD parameters (so `state_dict` matches); the arithm
 encoder / decoder call is one C-ABI call (`tpspp_nrtr_encoder_fwd` / `tpspp_nrtr_decoder_fwd`) that
 enqueues hand-written HIP kernels: there is no CPU or library-kernel path for inference, and the modules raise on
 CPU tensors.  Under `.train()` (round 5) encoder and decoder run as PyTorch compositions of the same layers so that
-autograd reaches their parameters (`_forward_graph`, `_forward_train_graph`); `NRTREncoder.set_train_backend("hip")` moves
-the encoder's training graph onto HIP kernels as well (masked attention with dropout forward and backward:
-tpspp_attn_train.hip).  The decoder is incremental (one position per step against cached
+autograd reaches their parameters (`_forward_graph`, `_forward_train_graph`); `NRTREncoder.set_train_backend("hip")` and
+`NRTRDecoder.set_train_backend("hip")` move their training graphs onto HIP kernels as well (masked attention with dropout
+forward and backward: tpspp_attn_train.hip; embedding: tpspp_dec_train.hip).  The decoder is incremental (one position per step against cached
 keys/values) where the reference re-runs the padded sequence every step; results agree to fp32
 rounding (see tests/test_gpu_head.py).
 """
@@ -412,8 +412,73 @@ class NRTRDecoder(nn.Module):
         x = Fn.layer_norm(x, (c,), self.layer_norm.weight, self.layer_norm.bias, self.layer_norm.eps)
         return Fn.linear(x, self.classifier.weight, self.classifier.bias)
 
+    def set_train_backend(self, mode):
+        """Which kernels the decoder's training graph (`forward_train` under `.train()`, or in eval mode with an encoder
+        output that carries gradients) runs on: "torch" (default) -- the PyTorch composition of its layers
+        (`_forward_train_graph`); "hip" -- the embedding, every matrix product, the causal self-attention and the
+        cross-attention with their dropout, every LayerNorm, the GELU and the classifier on HIP kernels forward and backward
+        (`_forward_train_hip`).  No effect on the eval and inference paths."""
+        if mode not in ("torch", "hip"):
+            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")
+
+    def _check_train_targets(self, targets, img_metas, n, t):
+        """What the HIP training path refuses, on the host (`targets`: the (N, L) padded targets as they come from the
+        label convertor, on the host).  Returns the mask lengths of the encoder tokens, or None."""
+        num_classes = self.trg_word_emb.weight.shape[0]
+        if targets.dim() != 2 or targets.shape[0] != n or targets.is_floating_point():
+            raise ValueError(f"NRTRDecoder: padded_targets must be ({n}, L) integers, got {tuple(targets.shape)}")
+        L = targets.shape[1]
+        if not 1 <= L <= 256 or t > 256:
+            raise ValueError(f"NRTRDecoder: 1 to 256 target positions and at most 256 encoder tokens on the HIP training "
+                             f"path, got L = {L}, T = {t}")
+        host = targets.detach().cpu()
+        if int(host.min()) < 0 or int(host.max()) >= num_classes:
+            raise ValueError(f"NRTRDecoder: target tokens must lie in [0, {num_classes}), got "
+                             f"[{int(host.min())}, {int(host.max())}]")
+        if bool((host[:, 0] == self.padding_idx).any()):
+            raise ValueError("NRTRDecoder: a target row whose first token is the padding: its first query sees no key, an "
+                             "empty softmax row (PyTorch's composition gives NaN)")
+        if img_metas is None:
+            return None
+        counts = _valid_counts(img_metas, n, t)
+        if min(counts) <= 0:
+            raise ValueError("NRTRDecoder: a valid_ratio that masks every encoder token of an image (mask length 0): the "
+                             "softmax over no key is undefined (PyTorch's composition gives NaN)")
+        return counts
+
+    def _forward_train_hip(self, out_enc, targets, img_metas):
+        """`_forward_train_graph` on the HIP training kernels, always fp32.  The seed of the attention dropouts is drawn
+        once per call from PyTorch's default CPU generator (torch.manual_seed reproduces a run); layer l uses the offsets
+        2 l (self-attention) and 2 l + 1 (cross-attention)."""
+        import torch.nn.functional as Fn
+        n, t, c = out_enc.shape
+        if c != self.d_model:
+            raise ValueError(f"NRTRDecoder: encoder width {c} != d_model {self.d_model}")
+        counts = self._check_train_targets(targets, img_metas, n, t)
+        ops.require_gpu(out_enc, "NRTRDecoder")
+        dev = out_enc.device
+        vl = None if counts is None else _valid_len(img_metas, n, t, dev)
+        p = self.dropout_p if self.training else 0.0
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if p > 0 else 0
+        tok = targets.to(device=dev, dtype=torch.int32).contiguous()
+        key_mask = tok != self.padding_idx
+        x = ops.embed_pos_autograd(tok, self.trg_word_emb.weight, self.position_enc.position_table, self.padding_idx)
+        x = Fn.dropout(x, p, p > 0)
+        out_enc = out_enc.contiguous()
+        for i, lyr in enumerate(self.layer_stack):
+            x = ops.decoder_layer_autograd(x, out_enc, lyr, key_mask, vl, p, seed, i)
+        return ops.linear_autograd(ops.token_ln_autograd(x, self.layer_norm), self.classifier)
+
     def forward_train(self, feat, out_enc, targets_dict, img_metas):
         if self.training or (torch.is_grad_enabled() and out_enc.requires_grad):
+            if self.train_backend == "hip":
+                return self._forward_train_hip(out_enc.float(), targets_dict["padded_targets"], img_metas)
             ops.require_gpu(out_enc, "NRTRDecoder")
             return self._forward_train_graph(out_enc.float(), targets_dict["padded_targets"].to(out_enc.device).long(),
                                              img_metas)
@@ -645,12 +710,13 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
-    def set_train_backend(self, mode, backbone=None, encoder=None):
+    def set_train_backend(self, mode, backbone=None, encoder=None, decoder=None, loss=None):
         """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
         "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).
         backbone: None leaves the backbone's train backend as it is; "torch" or "hip" sets it as well
-        (ResNetABI_v2_large.set_train_backend).  encoder: the same for the encoder (NRTREncoder.set_train_backend).
-        No effect on the eval path."""
+        (ResNetABI_v2_large.set_train_backend).  encoder, decoder, loss: the same for the encoder
+        (NRTREncoder.set_train_backend), the decoder (NRTRDecoder.set_train_backend) and the loss
+        (losses._SequenceLoss.set_train_backend).  No effect on the eval path."""
         if mode not in ("torch", "hip", "hip_all"):
             raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
         if backbone is not None:
@@ -663,12 +729,22 @@ class EncodeDecodeRecognizer(nn.Module):
                 raise ValueError(f'set_train_backend: encoder must be None, "torch" or "hip", got {encoder!r}')
             if not hasattr(self.encoder, "set_train_backend"):
                 raise ValueError(f"set_train_backend: {type(self.encoder).__name__} has no HIP training path")
+        for name, val, part in (("decoder", decoder, self.decoder), ("loss", loss, self.loss)):
+            if val is not None:
+                if val not in ("torch", "hip"):
+                    raise ValueError(f'set_train_backend: {name} must be None, "torch" or "hip", got {val!r}')
+                if not hasattr(part, "set_train_backend"):
+                    raise ValueError(f"set_train_backend: {type(part).__name__} has no HIP training path")
         if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
             self.tpsnet.set_train_backend(mode)
         if backbone is not None:
             self.backbone.set_train_backend(backbone)
         if encoder is not None:
             self.encoder.set_train_backend(encoder)
+        if decoder is not None:
+            self.decoder.set_train_backend(decoder)
+        if loss is not None:
+            self.loss.set_train_backend(loss)
         return self
 
     def extract_feat(self, img, test=False, **kwargs):

@@ -2389,12 +2389,14 @@ def attn_train_autograd(q, k, v, valid_len=None, drop_p=0.0, seed=0, offset=0):
 
 
 class _AttnBlockFunction(torch.autograd.Function):
-    """norm1 - q / k / v projections (one product) - attention - fc of a TFEncoderLayer on x (N, T, C).  Saves x, the
+    """norm1 - q / k / v projections (one product) - attention - fc of a TFEncoderLayer on x (N, T, C), and with key_mask /
+    causal of a TFDecoderLayer's self-attention (the same kernels: `tpspp_attn_train_fwd_ex` without the two masks is
+    `tpspp_attn_train_fwd` bit for bit).  Saves x, the
     LayerNorm statistics, the fused projection, the attention output and its log-sum-exp; the LayerNorm output is
     recomputed in the backward."""
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg):
+    def forward(ctx, x, n1w, n1b, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg, key_mask=None, causal=False):
         eps, drop_p, seed, offset = cfg
         N, T, C = x.shape
         M, heads = N * T, C // 64
@@ -2402,20 +2404,21 @@ class _AttnBlockFunction(torch.autograd.Function):
         wqkv = torch.cat([wq, wk, wv], dim=0)
         bqkv = None if bq is None else torch.cat([bq, bk, bv])
         qkv = linear_fwd(y, _dense(M, C), wqkv, bqkv)
-        out, lse = attn_train_fwd(qkv, qkv[:, C:], qkv[:, 2 * C:], 3 * C, N, C, heads, T, T, valid_len, drop_p, seed, offset)
+        out, lse = attn_train_fwd_ex(qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, N, C, heads, T, T, valid_len, key_mask,
+                                     causal, drop_p, seed, offset)
         a = linear_fwd(out, _dense(M, C), fcw, fcb)
-        ctx.cfg = cfg
-        ctx.save_for_backward(x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len)
+        ctx.cfg = cfg + (causal,)
+        ctx.save_for_backward(x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len, key_mask)
         return a.view(N, T, C)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, ga):
-        x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len = ctx.saved_tensors
+        x, m1, r1, qkv, out, lse, n1w, n1b, wqkv, bqkv, fcw, valid_len, key_mask = ctx.saved_tensors
         need = ctx.needs_input_grad
         if not any(need[:11]):
-            return (None,) * 13
-        eps, drop_p, seed, offset = ctx.cfg
+            return (None,) * 15
+        eps, drop_p, seed, offset, causal = ctx.cfg
         N, T, C = x.shape
         M, heads = N * T, C // 64
         dev = x.device
@@ -2423,15 +2426,15 @@ class _AttnBlockFunction(torch.autograd.Function):
         dw_fc, db_fc = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[9], need[10])
         dout = linear_bwd_data(ga, fcw, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
         dqkv = torch.empty((M, 3 * C), device=dev, dtype=torch.float32)
-        attn_train_bwd(dout, qkv, qkv[:, C:], qkv[:, 2 * C:], 3 * C, out, lse, N, C, heads, T, T, valid_len, drop_p, seed,
-                       offset, dqkv, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C)
+        attn_train_bwd_ex(dout, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, out, lse, N, C, heads, T, T, valid_len, key_mask,
+                          causal, drop_p, seed, offset, dqkv, 3 * C, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C)
         del dout
         y, _, _ = plane_ln_fwd(x, n1w, n1b, eps)
         dw = db = None
         if any(need[3:9]):
             dw, db = linear_bwd_weight(dqkv, y, _dense(M, C), 3 * C, C, any(need[3:6]), any(need[6:9]))
         del y
-        res = [None] * 13
+        res = [None] * 15
         if any(need[:3]):
             dy = linear_bwd_data(dqkv, wqkv, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
             dx = torch.empty_like(x) if need[0] else None
@@ -2551,4 +2554,425 @@ def encoder_layer_autograd(x, lyr, valid_len=None, drop_p=0.0, seed=0, offset=0)
     a = attn_block_autograd(x, lyr.attn, lyr.norm1, valid_len, drop_p, seed, offset)
     x = x + Fn.dropout(a, drop_p, drop_p > 0)
     f = ffn_block_autograd(x, lyr.mlp, lyr.norm2)
+    return x + Fn.dropout(f, drop_p, drop_p > 0)
+
+
+# ---- the decoder's training graph and the loss on HIP kernels ---------------------------------------------------------------
+# include/tpspp_train_dec.h: the attention above with a per-key mask, a causal mask and separate row strides for q and
+# k / v (the decoder's self- and cross-attention), the target embedding and the sequence cross-entropy.  A decoder layer is
+# three once-differentiable functions (norm1 - qkv - causal attention - fc, norm2 - q / fused k|v - attention - fc, norm3 -
+# w_1 - GELU - w_2); residual additions and element-wise dropouts stay PyTorch ops as in the encoder.
+
+def _attn_operands_ex(who, q, k, v):
+    """q (N, Tq, C), k / v (N, Tk, C) as `tpspp_attn_train_fwd_ex` takes them: q with a row stride of its own, one row
+    stride for k and v (views of a fused (N, T, 2C) or (N, T, 3C) projection pass as they are), dense copies otherwise."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        _chk_gpu(f"{who} {name}", t)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who} {name}: expected float32, got {t.dtype}")
+        if t.dim() != 3:
+            raise ValueError(f"{who} {name}: expected (N, T, C), got {tuple(t.shape)}")
+    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise ValueError(f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit together")
+    if q.shape[2] % 64 or q.shape[2] == 0:
+        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
+    ld_q = _row_stride(q)
+    if ld_q is None:
+        q, ld_q = q.contiguous(), q.shape[2]
+    ld_kv = _row_stride(k)
+    if ld_kv is None or ld_kv != _row_stride(v):
+        k, v, ld_kv = k.contiguous(), v.contiguous(), k.shape[2]
+    return q, k, v, ld_q, ld_kv
+
+
+def _attn_key_mask(who, key_mask, N, Tk, dev):
+    """(N, Tk) bool or uint8 on the device, 0 = masked -> contiguous uint8, or None."""
+    if key_mask is None:
+        return None
+    if not isinstance(key_mask, torch.Tensor) or key_mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{who}: key_mask must be a bool or uint8 tensor")
+    if tuple(key_mask.shape) != (N, Tk) or key_mask.device != dev:
+        raise ValueError(f"{who}: key_mask must be ({N}, {Tk}) on {dev}, got {tuple(key_mask.shape)} on {key_mask.device}")
+    key_mask = key_mask.contiguous()
+    return key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
+
+
+def _attn_rate(who, drop_p):
+    if not 0.0 <= float(drop_p) < 1.0:
+        raise ValueError(f"{who}: drop_p must lie in [0, 1), got {drop_p!r}")
+    return float(drop_p)
+
+
+def attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed, offset):
+    """`tpspp_attn_train_fwd_ex` on raw operands: (out (N*Tq, C), lse (N, heads, Tq))."""
+    out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
+    lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_attn_train_fwd_ex(_ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, N, C, heads, Tq, Tk, _ptr(valid_len),
+                                                  _ptr(key_mask), int(bool(causal)), float(drop_p), int(seed) & _U64,
+                                                  int(offset) & _U64, _ptr(out), _ptr(lse), _stream(q)),
+               "tpspp_attn_train_fwd_ex")
+    return out, lse
+
+
+def attn_train_bwd_ex(d_out, q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
+                      offset, dq, ld_dq, dk, dv, ld_dkv):
+    """`tpspp_attn_train_bwd_ex`: writes dq (N*Tq rows, `ld_dq` apart), dk, dv (N*Tk rows, `ld_dkv` apart)."""
+    _lib.check(_lib.lib().tpspp_attn_train_bwd_ex(_ptr(d_out), _ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, _ptr(out), _ptr(lse), N,
+                                                  C, heads, Tq, Tk, _ptr(valid_len), _ptr(key_mask), int(bool(causal)),
+                                                  float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(dq), ld_dq,
+                                                  _ptr(dk), _ptr(dv), ld_dkv, _stream(d_out)), "tpspp_attn_train_bwd_ex")
+
+
+class _AttnTrainExFunction(torch.autograd.Function):
+    """`_AttnTrainFunction` with a per-key mask, a causal mask and separate row strides."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, valid_len, key_mask, cfg):
+        causal, drop_p, seed, offset = cfg
+        q, k, v, ld_q, ld_kv = _attn_operands_ex("attn_train_autograd_ex", q, k, v)
+        N, Tq, C = q.shape
+        Tk, heads = k.shape[1], C // 64
+        out, lse = attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
+                                     offset)
+        ctx.save_for_backward(q, k, v, out, lse, valid_len, key_mask)
+        ctx.cfg = (ld_q, ld_kv) + cfg
+        return out.view(N, Tq, C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        q, k, v, out, lse, valid_len, key_mask = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * 6
+        ld_q, ld_kv, causal, drop_p, seed, offset = ctx.cfg
+        N, Tq, C = q.shape
+        Tk, heads = k.shape[1], C // 64
+        dq = torch.empty((N, Tq, C), device=q.device, dtype=torch.float32)
+        dk = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
+        dv = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
+        attn_train_bwd_ex(gout.float().contiguous(), q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask,
+                          causal, drop_p, seed, offset, dq, C, dk, dv, C)
+        return dq, dk, dv, None, None, None
+
+
+def attn_train_autograd_ex(q, k, v, valid_len=None, key_mask=None, causal=False, drop_p=0.0, seed=0, offset=0):
+    """`attn_train_autograd` with the decoder's masks (`tpspp_attn_train_fwd_ex` / `_bwd_ex`): key j is visible to query i
+    iff j < valid_len[b], key_mask[b, j] != 0 ((N, Tk) bool / uint8 on the device) and, with causal, j <= i -- whichever
+    are given.  q may have a row stride of its own (a (N, L, C) projection next to k, v = the halves of a fused (N, T, 2C)
+    one).  A query with no visible key gives an output row of zeros and no gradient."""
+    who = "attn_train_autograd_ex"
+    drop_p = _attn_rate(who, drop_p)
+    _chk_gpu(f"{who} q", q)
+    if q.dim() != 3 or k.dim() != 3:
+        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
+    if max(q.shape[1], k.shape[1]) > 256:
+        raise ValueError(f"{who}: at most 256 tokens, got Tq = {q.shape[1]}, Tk = {k.shape[1]}")
+    valid_len = _attn_valid_len(who, valid_len, q.shape[0], q.device)
+    key_mask = _attn_key_mask(who, key_mask, q.shape[0], k.shape[1], q.device)
+    return _AttnTrainExFunction.apply(q, k, v, valid_len, key_mask, (bool(causal), drop_p, int(seed), int(offset)))
+
+
+def _attn_block_args(who, x, attn, drop_p):
+    x = _chk(f"{who} x", x, 3)
+    N, T, C = x.shape
+    if C != attn.dim_k or attn.d_k != 64 or attn.d_v != 64:
+        raise ValueError(f"{who}: token width {C} against {attn.n_head} heads of {attn.d_k}")
+    if T > 256:
+        raise ValueError(f"{who}: at most 256 tokens, got {T}")
+    biases = (attn.linear_q.bias, attn.linear_k.bias, attn.linear_v.bias)
+    if any(b is None for b in biases) and not all(b is None for b in biases):
+        raise ValueError(f"{who}: linear_q / _k / _v must all have a bias or none")
+    return x, biases, _attn_rate(who, drop_p)
+
+
+def self_attn_block_autograd(x, attn, norm, key_mask=None, causal=True, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """fc(attention(norm(x))) of a TFDecoderLayer's self-attention (`transformer_layers.py:133-147` up to the dropout) on
+    tokens x (N, L, C): `attn_block_autograd` -- the same function -- with the pad mask of the targets as `key_mask`
+    ((N, L) bool / uint8, 0 = <PAD>) and the causal mask."""
+    who = "self_attn_block_autograd"
+    x, biases, drop_p = _attn_block_args(who, x, attn, drop_p)
+    valid_len = _attn_valid_len(who, valid_len, x.shape[0], x.device)
+    key_mask = _attn_key_mask(who, key_mask, x.shape[0], x.shape[1], x.device)
+    return _AttnBlockFunction.apply(x, norm.weight, norm.bias, attn.linear_q.weight, attn.linear_k.weight,
+                                    attn.linear_v.weight, *biases, attn.fc.weight, attn.fc.bias, valid_len,
+                                    (float(norm.eps), drop_p, int(seed), int(offset)), key_mask, bool(causal))
+
+
+class _CrossAttnBlockFunction(torch.autograd.Function):
+    """norm2 - q projection on x (N, L, C); one fused k | v projection (N*T, 2C) on the encoder output; attention with
+    ld_q = C, ld_kv = 2C; fc.  Saves x, out_enc, the LayerNorm statistics, both projections, the attention output and its
+    log-sum-exp; the LayerNorm output is recomputed in the backward."""
+
+    @staticmethod
+    def forward(ctx, x, enc, nw, nb, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg):
+        eps, drop_p, seed, offset = cfg
+        N, L, C = x.shape
+        T, heads = enc.shape[1], C // 64
+        y, m, r = plane_ln_fwd(x, nw, nb, eps)
+        qp = linear_fwd(y, _dense(N * L, C), wq, bq)
+        wkv = torch.cat([wk, wv], dim=0)
+        bkv = None if bk is None else torch.cat([bk, bv])
+        kv = linear_fwd(enc, _dense(N * T, C), wkv, bkv)
+        out, lse = attn_train_fwd_ex(qp, C, kv, kv[:, C:], 2 * C, N, C, heads, L, T, valid_len, None, False, drop_p, seed,
+                                     offset)
+        a = linear_fwd(out, _dense(N * L, C), fcw, fcb)
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, enc, m, r, qp, kv, out, lse, nw, nb, wq, bq, wkv, fcw, valid_len)
+        return a.view(N, L, C)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, ga):
+        x, enc, m, r, qp, kv, out, lse, nw, nb, wq, bq, wkv, fcw, valid_len = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:12]):
+            return (None,) * 14
+        eps, drop_p, seed, offset = ctx.cfg
+        N, L, C = x.shape
+        T, heads = enc.shape[1], C // 64
+        M, MT = N * L, N * T
+        dev = x.device
+        ga = ga.float().contiguous()
+        res = [None] * 14
+        res[10], res[11] = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[10], need[11])
+        dout = linear_bwd_data(ga, fcw, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
+        dqp = torch.empty((M, C), device=dev, dtype=torch.float32)
+        dkv = torch.empty((MT, 2 * C), device=dev, dtype=torch.float32)
+        attn_train_bwd_ex(dout, qp, C, kv, kv[:, C:], 2 * C, out, lse, N, C, heads, L, T, valid_len, None, False, drop_p, seed,
+                          offset, dqp, C, dkv, dkv[:, C:], 2 * C)
+        del dout
+        if need[4] or need[7]:
+            y, _, _ = plane_ln_fwd(x, nw, nb, eps)
+            dwq, dbq = linear_bwd_weight(dqp, y, _dense(M, C), C, C, need[4], need[7])
+            del y
+            res[4], res[7] = dwq, dbq
+        if any(need[5:7]) or any(need[8:10]):
+            dw, db = linear_bwd_weight(dkv, enc, _dense(MT, C), 2 * C, C, any(need[5:7]), any(need[8:10]))
+            for i in range(2):
+                if dw is not None and need[5 + i]:
+                    res[5 + i] = dw[i * C:(i + 1) * C]
+                if db is not None and need[8 + i]:
+                    res[8 + i] = db[i * C:(i + 1) * C]
+        if any((need[0], need[2], need[3])):
+            dy = linear_bwd_data(dqp, wq, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
+            dx = torch.empty_like(x) if need[0] else None
+            dw_ln, db_ln = plane_ln_bwd(dy, x, nw, m, r, dx=dx, want_params=need[2] or need[3])
+            res[0], res[2], res[3] = dx, dw_ln if need[2] else None, db_ln if need[3] else None
+        if need[1]:
+            res[1] = linear_bwd_data(dkv, wkv, torch.empty((MT, C), device=dev, dtype=torch.float32),
+                                     _dense(MT, C)).view(enc.shape)
+        return tuple(res)
+
+
+def cross_attn_block_autograd(x, out_enc, attn, norm, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """fc(attention(norm(x), out_enc)) of a TFDecoderLayer's encoder-decoder attention (`transformer_layers.py:149-156` up
+    to the dropout): queries from the decoder tokens x (N, L, C), keys and values from the encoder output (N, T, C) through
+    ONE (N*T, 2C) product, keys j >= valid_len[b] masked.  Differentiable in x, out_enc and every parameter."""
+    who = "cross_attn_block_autograd"
+    x, biases, drop_p = _attn_block_args(who, x, attn, drop_p)
+    out_enc = _chk(f"{who} out_enc", out_enc, 3)
+    if out_enc.shape[0] != x.shape[0] or out_enc.shape[2] != x.shape[2]:
+        raise ValueError(f"{who}: x {tuple(x.shape)} against out_enc {tuple(out_enc.shape)}")
+    if out_enc.shape[1] > 256:
+        raise ValueError(f"{who}: at most 256 encoder tokens, got {out_enc.shape[1]}")
+    valid_len = _attn_valid_len(who, valid_len, x.shape[0], x.device)
+    return _CrossAttnBlockFunction.apply(x, out_enc, norm.weight, norm.bias, attn.linear_q.weight, attn.linear_k.weight,
+                                         attn.linear_v.weight, *biases, attn.fc.weight, attn.fc.bias, valid_len,
+                                         (float(norm.eps), drop_p, int(seed), int(offset)))
+
+
+def _embed_tokens(who, tokens, num_classes, dev):
+    """(N, L) integer tokens -> int32 on `dev`.  Tokens that live on the host -- where the targets originate -- are
+    refused when they lie outside [0, num_classes); tokens already on the device are taken as they are (the kernels
+    ignore such a token)."""
+    if not isinstance(tokens, torch.Tensor) or tokens.dim() != 2 or tokens.is_floating_point():
+        raise ValueError(f"{who}: tokens must be an (N, L) integer tensor")
+    if tokens.device.type == "cpu" and tokens.numel():
+        lo, hi = int(tokens.min()), int(tokens.max())
+        if lo < 0 or hi >= num_classes:
+            raise ValueError(f"{who}: tokens must lie in [0, {num_classes}), got [{lo}, {hi}]")
+    return tokens.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def embed_pos_fwd(tok, weight, pos):
+    """`tpspp_embed_pos_fwd`: weight[tok] + pos[:L] -> (N, L, C); tok (N, L) int32 on the device."""
+    N, L = tok.shape
+    out = torch.empty((N, L, weight.shape[1]), device=weight.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_embed_pos_fwd(_ptr(tok), _ptr(weight), _ptr(pos), N, L, weight.shape[1], weight.shape[0],
+                                              _ptr(out), _stream(weight)), "tpspp_embed_pos_fwd")
+    return out
+
+
+def embed_bwd_workspace_floats(M, num_classes, C):
+    return int(_lib.lib().tpspp_embed_bwd_workspace_floats(int(M), int(num_classes), int(C)))
+
+
+def embed_bwd(dx, tok, num_classes, padding_idx):
+    """`tpspp_embed_bwd`: d_weight (num_classes, C) from dx (M, C) dense and tok (M) int32, every row written."""
+    M, C = tok.numel(), dx.shape[-1]
+    if M == 0:
+        return torch.zeros((num_classes, C), device=dx.device, dtype=torch.float32)
+    dw = torch.empty((num_classes, C), device=dx.device, dtype=torch.float32)
+    n = embed_bwd_workspace_floats(M, num_classes, C)
+    ws = torch.empty((n,), device=dx.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_embed_bwd(_ptr(dx), _ptr(tok), M, C, num_classes, -1 if padding_idx is None else padding_idx,
+                                          _ptr(dw), _ptr(ws), n, _stream(dx)), "tpspp_embed_bwd")
+    return dw
+
+
+class _EmbedPosFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, weight, tok, pos, padding_idx):
+        ctx.save_for_backward(tok)
+        ctx.cfg = (weight.shape[0], padding_idx)
+        return embed_pos_fwd(tok, weight, pos)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gx):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 4
+        (tok,) = ctx.saved_tensors
+        return embed_bwd(gx.float().contiguous(), tok, *ctx.cfg), None, None, None
+
+
+def embed_pos_autograd(tokens, emb_weight, pos_table, padding_idx=None):
+    """nn.Embedding(tokens) + the first L rows of the position table (`nrtr_decoder.py:95-99` before the dropout) ->
+    (N, L, C), differentiable in emb_weight (`tpspp_embed_pos_fwd` / `tpspp_embed_bwd`: the row of padding_idx gets a zero
+    gradient, in a fixed summation order)."""
+    who = "embed_pos_autograd"
+    emb_weight = _chk(f"{who} emb_weight", emb_weight, 2)
+    tok = _embed_tokens(who, tokens, emb_weight.shape[0], emb_weight.device)
+    pos = _chk(f"{who} pos_table", pos_table.detach())
+    pos = pos.reshape(-1, pos.shape[-1])
+    if pos.shape[1] != emb_weight.shape[1] or pos.shape[0] < tok.shape[1] or pos.device != emb_weight.device:
+        raise ValueError(f"{who}: position table {tuple(pos.shape)} against {tok.shape[1]} tokens of width "
+                         f"{emb_weight.shape[1]}")
+    return _EmbedPosFunction.apply(emb_weight, tok, pos, padding_idx)
+
+
+_CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+
+
+def _ce_operands(who, logits, targets, shift):
+    """logits (N, L, K) float32 on the device with any strides, targets (N, L) integers -> int32 on that device."""
+    _chk_gpu(f"{who} logits", logits)
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise TypeError(f"{who}: logits must be (N, L, K) float32, got {tuple(logits.shape)} {logits.dtype}")
+    N, L, K = logits.shape
+    if not 1 <= K <= 1024:
+        raise ValueError(f"{who}: 1 to 1024 classes, got {K}")
+    if not isinstance(targets, torch.Tensor) or targets.is_floating_point() or tuple(targets.shape) != (N, L):
+        raise ValueError(f"{who}: targets must be ({N}, {L}) integers")
+    if L - int(bool(shift)) < 0 or L == 0:
+        raise ValueError(f"{who}: no position to score")
+    return targets.to(device=logits.device, dtype=torch.int32).contiguous()
+
+
+def seq_ce_fwd(logits, tgt, shift, ignore_index, reduction):
+    """`tpspp_seq_ce_fwd`: (loss (N, Lp), lse (N, Lp), reduced (1) | None, count (1) | None), Lp = L - shift."""
+    N, L, K = logits.shape
+    Lp = L - int(shift)
+    dev = logits.device
+    loss = torch.empty((N, Lp), device=dev, dtype=torch.float32)
+    lse = torch.empty((N, Lp), device=dev, dtype=torch.float32)
+    red = cnt = None
+    if reduction:
+        red = torch.empty((1,), device=dev, dtype=torch.float32)
+        cnt = torch.empty((1,), device=dev, dtype=torch.float32)
+    if N == 0 and reduction:                   # the library returns before any launch
+        red.fill_(float("nan") if reduction == 1 else 0.0)
+        cnt.zero_()
+    _lib.check(_lib.lib().tpspp_seq_ce_fwd(_ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), _ptr(tgt), N, L,
+                                           K, int(shift), int(ignore_index), reduction, _ptr(loss), _ptr(lse), _ptr(red),
+                                           _ptr(cnt), _stream(logits)), "tpspp_seq_ce_fwd")
+    return loss, lse, red, cnt
+
+
+def seq_ce_bwd(g, logits, tgt, lse, cnt, shift, ignore_index, reduction):
+    """`tpspp_seq_ce_bwd`: d_logits (N, L, K) dense."""
+    N, L, K = logits.shape
+    d = torch.empty((N, L, K), device=logits.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_seq_ce_bwd(_ptr(g), _ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2),
+                                           _ptr(tgt), _ptr(lse), _ptr(cnt), N, L, K, int(shift), int(ignore_index), reduction,
+                                           _ptr(d), _stream(logits)), "tpspp_seq_ce_bwd")
+    return d
+
+
+class _SeqCeFunction(torch.autograd.Function):
+    """Saves the logits, the targets, the per-position log-sum-exp and the count; the softmax is recomputed."""
+
+    @staticmethod
+    def forward(ctx, logits, tgt, cfg):
+        shift, ignore_index, reduction, flatten = cfg
+        loss, lse, red, cnt = seq_ce_fwd(logits, tgt, shift, ignore_index, reduction)
+        ctx.save_for_backward(logits, tgt, lse, cnt)
+        ctx.cfg = cfg
+        if reduction:
+            return red.view(())
+        return loss.view(-1) if flatten else loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        logits, tgt, lse, cnt = ctx.saved_tensors
+        shift, ignore_index, reduction, _ = ctx.cfg
+        if logits.shape[0] == 0:
+            return torch.zeros_like(logits), None, None
+        return seq_ce_bwd(g.float().contiguous(), logits, tgt, lse, cnt, shift, ignore_index, reduction), None, None
+
+
+def seq_cross_entropy_autograd(logits, targets, ignore_index=-100, reduction="none", shift=False, flatten=True):
+    """`losses.sequence_cross_entropy` on HIP kernels (`tpspp_seq_ce_fwd` / `_bwd`), with its result shapes: a scalar for
+    "mean" / "sum", (N * L',) for "none" with flatten, else (N, L'), L' = L - shift.  The logits are read through their
+    strides (no copy for a view such as logits[:, :-1]); targets on the host or on the device, any integer type."""
+    who = "seq_cross_entropy_autograd"
+    if reduction not in _CE_REDUCTIONS:
+        raise ValueError(f'{who}: reduction must be "none", "mean" or "sum", got {reduction!r}')
+    tgt = _ce_operands(who, logits, targets, shift)
+    return _SeqCeFunction.apply(logits, tgt, (bool(shift), int(ignore_index), _CE_REDUCTIONS[reduction], bool(flatten)))
+
+
+class _LinearFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        return linear_fwd(x, _dense(x.numel() // w.shape[1], w.shape[1]), w, b).view(*x.shape[:-1], w.shape[0])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        O, K = w.shape
+        M = x.numel() // K
+        gy = gy.float().contiguous().view(M, O)
+        dw, db = linear_bwd_weight(gy, x, _dense(M, K), O, K, need[1], need[2])
+        dx = linear_bwd_data(gy, w, torch.empty_like(x), _dense(M, K)) if need[0] else None
+        return dx, dw, db
+
+
+def linear_autograd(x, lin):
+    """nn.Linear `lin` on the last dimension of x, differentiable (`tpspp_mm_f32` / `tpspp_linear_bwd_weight`)."""
+    x = _chk("linear_autograd x", x)
+    if x.shape[-1] != lin.weight.shape[1]:
+        raise ValueError(f"linear_autograd: input width {x.shape[-1]} against weight {tuple(lin.weight.shape)}")
+    return _LinearFunction.apply(x, lin.weight, lin.bias)
+
+
+def decoder_layer_autograd(x, out_enc, lyr, key_mask=None, valid_len=None, drop_p=0.0, seed=0, offset=0):
+    """One pre-norm TFDecoderLayer (`transformer_layers.py:133-163`) on tokens x (N, L, C) and the encoder output
+    (N, T, C) in the training graph: causal self-attention under the targets' pad mask `key_mask`, attention over the
+    encoder tokens below valid_len, feed-forward -- every matrix product, softmax, LayerNorm and GELU on HIP kernels; the
+    three residual additions and the three element-wise dropouts (rate drop_p, PyTorch's generator) are PyTorch ops.
+    `offset` is the layer's index: the dropout on the attention probabilities uses (seed, 2 * offset) in the
+    self-attention and (seed, 2 * offset + 1) in the cross-attention."""
+    import torch.nn.functional as Fn
+    a = self_attn_block_autograd(x, lyr.self_attn, lyr.norm1, key_mask, True, None, drop_p, seed, 2 * offset)
+    x = x + Fn.dropout(a, drop_p, drop_p > 0)
+    a = cross_attn_block_autograd(x, out_enc, lyr.enc_attn, lyr.norm2, valid_len, drop_p, seed, 2 * offset + 1)
+    x = x + Fn.dropout(a, drop_p, drop_p > 0)
+    f = ffn_block_autograd(x, lyr.mlp, lyr.norm3)
     return x + Fn.dropout(f, drop_p, drop_p > 0)
