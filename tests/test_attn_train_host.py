@@ -106,6 +106,55 @@ def test_ops_refuse_cpu_tensors_and_bad_rates():
         ops.attn_dropout_mask(1, 1, 4, 4, 0.5, 1, 0, "cpu")
 
 
+def test_both_autograd_names_raise_the_same_rate_error():
+    from tps_pp_amd import ops
+    q = torch.zeros(1, 4, 64)
+    with pytest.raises(ValueError) as old:
+        ops.attn_train_autograd(q, q, q, drop_p=1.0)
+    with pytest.raises(ValueError) as new:
+        ops.attn_train_autograd_ex(q, q, q, drop_p=1.0)
+    assert type(old.value) is type(new.value) is ValueError and str(old.value) == str(new.value)
+    assert "drop_p must lie in [0, 1), got 1.0" in str(old.value)
+
+
+def _switchable(name):
+    import tps_pp_amd as P
+    from tps_pp_amd import losses
+    return {"TPS_PP": lambda: P.TPS_PP(),
+            "ResNetABI_v2_large": lambda: P.ResNetABI_v2_large(arch_settings=[1, 1, 1, 1, 1], strides=[2, 1, 2, 1, 2]),
+            "NRTREncoder": lambda: P.NRTREncoder(n_layers=1, n_head=2, d_model=128, d_inner=64),
+            "NRTRDecoder": lambda: P.NRTRDecoder(n_layers=1, n_head=2, d_model=128, d_embedding=128, d_inner=64),
+            "_SequenceLoss": lambda: losses._SequenceLoss(92, "none", shift=True, flatten=True)}[name]()
+
+
+@pytest.mark.parametrize("name", ["TPS_PP", "ResNetABI_v2_large", "NRTREncoder", "NRTRDecoder", "_SequenceLoss"])
+def test_the_five_train_backend_switches_are_one(name):
+    from tps_pp_amd.registry import TrainBackendMixin
+    m = _switchable(name)
+    modes = ("torch", "hip", "hip_all") if name == "TPS_PP" else ("torch", "hip")
+    text = '"torch", "hip" or "hip_all"' if name == "TPS_PP" else '"torch" or "hip"'
+    assert isinstance(m, TrainBackendMixin) and type(m).TRAIN_BACKENDS == modes
+    assert "train_backend" not in vars(type(m))                # the property is the mixin's
+    assert m.train_backend == "torch"
+    for mode in modes[::-1]:
+        assert m.set_train_backend(mode) is m and m.train_backend == mode
+    for bad in ("x", "HIP", "hip_some", None, 1) + (() if name == "TPS_PP" else ("hip_all",)):
+        with pytest.raises(ValueError) as e:
+            m.set_train_backend(bad)
+        assert str(e.value) == f"set_train_backend: {text}, got {bad!r}"
+        assert m.train_backend == "torch"                      # modes[::-1] ended on "torch": the old value stays
+    m.set_train_backend("hip")
+    with pytest.raises(ValueError):
+        m.set_train_backend("x")
+    assert m.train_backend == "hip"
+    # an object built before the attribute existed reads as "torch"
+    del m._train_backend
+    assert m.train_backend == "torch"
+    # what each mode means for this class is still written down
+    doc = (type(m).set_train_backend.__doc__ or "") + (type(m).__doc__ or "")
+    assert '"hip"' in doc and '"torch"' in doc
+
+
 def small_recogniser(**kw):
     import tps_pp_amd as P
     return P.build_detector(dict(type="NRTR", backbone=dict(type="ResNetABI_v2_large", arch_settings=[1, 1, 1, 1, 1],

@@ -122,6 +122,39 @@ def test_views_of_one_fused_projection_buffer(cuda):
     check_against_float64(cuda, "fused p=0.1", N, heads, T, [20, 12, 7], p=0.1, seed=5, offset=1, fused=True)
 
 
+def test_encoder_signature_is_the_general_path_and_reads_strided_operands_in_place(cuda):
+    """`attn_train_autograd` is `attn_train_autograd_ex` without the two masks: q as a view of a wider buffer next to k, v
+    as the halves of a fused (N, T, 2C) one are read where they lie, and output and gradients have the bits of the dense
+    operands and of the raw `tpspp_attn_train_fwd` / `_bwd` entry points.  T = 65 crosses one 64-key block."""
+    N, heads, T, p, seed, offset = 2, 2, 65, 0.5, 20240229, 3
+    C = 64 * heads
+    q, k, v, gout = (t.to(cuda) for t in make_case(N, heads, T, seed=7))
+    vl = torch.tensor([65, 40], dtype=torch.int32, device=cuda)
+    out, lse = ops.attn_train_fwd(q, k, v, C, N, C, heads, T, T, vl, p, seed, offset)
+    raw = [out.view(N, T, C)] + [torch.empty_like(q) for _ in range(3)]
+    ops.attn_train_bwd(gout, q, k, v, C, out, lse, N, C, heads, T, T, vl, p, seed, offset, *raw[1:], C)
+
+    xs = [t.clone().requires_grad_(True) for t in (q, k, v)]
+    out = ops.attn_train_autograd(*xs, vl, p, seed, offset)
+    out.backward(gout)
+    ok, why = GA.same_bits(raw, [out.detach()] + [t.grad for t in xs])
+    assert ok, f"dense: {why}"
+
+    qb = torch.full((N, T, C + 32), float("nan"), device=cuda)             # the spare columns are never read
+    qb[..., :C] = q
+    qb.requires_grad_(True)
+    kvb = torch.cat([k, v], dim=2).requires_grad_(True)
+    views = (qb[..., :C], kvb[..., :C], kvb[..., C:])
+    taken = ops._attn_operands("t", *views)
+    assert taken[3:] == (C + 32, 2 * C) and [t.data_ptr() for t in taken[:3]] == [t.data_ptr() for t in views]
+    out = ops.attn_train_autograd(*views, vl, p, seed, offset)
+    out.backward(gout)
+    assert kvb.grad.shape == kvb.shape and qb.grad.shape == qb.shape
+    ok, why = GA.same_bits(raw, [out.detach(), qb.grad[..., :C], kvb.grad[..., :C], kvb.grad[..., C:]])
+    assert ok, f"strided: {why}"
+    assert (qb.grad[..., C:] == 0).all()
+
+
 # ---- 2. masked keys ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,heads,T,valid_len", [SHAPES[0], SHAPES[2], SHAPES[4]], ids=["T20", "T64", "T255"])
 def test_masked_keys_get_exact_zeros_and_are_never_read(cuda, N, heads, T, valid_len):

@@ -286,7 +286,7 @@ def test_autograd_wrapper_takes_the_strided_operands_without_copies(cuda):
     qb = q.to(cuda).requires_grad_(True)
     kvb = torch.cat([k, v], dim=2).to(cuda).requires_grad_(True)
     vl = torch.tensor(case["valid_len"], dtype=torch.int32, device=cuda)
-    assert ops._attn_operands_ex("t", qb, kvb[..., :C], kvb[..., C:])[3:] == (C, 2 * C)
+    assert ops._attn_operands("t", qb, kvb[..., :C], kvb[..., C:])[3:] == (C, 2 * C)
     out = ops.attn_train_autograd_ex(qb, kvb[..., :C], kvb[..., C:], vl, None, False, 0.1, 5, 3)
     out.backward(gout.to(cuda))
     ok, why = GA.same_bits([want[0], want[2], want[3], want[4]], [out.detach(), qb.grad, kvb.grad[..., :C], kvb.grad[..., C:]])

@@ -10,7 +10,7 @@ targets are aligned.  Everything else under the reference's `losses/` stays out 
 import torch.nn as nn
 import torch.nn.functional as Fn
 
-from .registry import Registry
+from .registry import Registry, TrainBackendMixin
 
 LOSSES = Registry("loss")
 _REDUCTIONS = ("none", "mean", "sum")
@@ -32,7 +32,7 @@ def sequence_cross_entropy(logits, targets, ignore_index, reduction, shift, flat
                             reduction=reduction)
 
 
-class _SequenceLoss(nn.Module):
+class _SequenceLoss(TrainBackendMixin, nn.Module):
     shift_default = False
 
     def __init__(self, ignore_index, reduction, shift, flatten):
@@ -44,14 +44,7 @@ class _SequenceLoss(nn.Module):
     def set_train_backend(self, mode):
         """ "torch" (default): `F.cross_entropy`; "hip": `tpspp_seq_ce_fwd` / `_bwd` for logits on the GPU (logits on the
         host keep PyTorch's)."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
-        self._train_backend = mode
-        return self
-
-    @property
-    def train_backend(self):
-        return getattr(self, "_train_backend", "torch")
+        return super().set_train_backend(mode)
 
     def forward(self, outputs, targets_dict, img_metas=None):
         """-> {'loss_ce': tensor}; `targets_dict['padded_targets']` (N, T) as `AttnConvertor.str2tensor` builds it."""

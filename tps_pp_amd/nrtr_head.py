@@ -27,7 +27,7 @@ import torch.nn as nn
 from .precision import default_compute_dtype
 from . import ops
 from ._prepared import prepared
-from .registry import (CONVERTORS, DECODERS, DETECTORS, ENCODERS, build_backbone, build_convertor,
+from .registry import (CONVERTORS, DECODERS, DETECTORS, ENCODERS, TrainBackendMixin, build_backbone, build_convertor,
                        build_decoder, build_encoder, build_preprocessor)
 
 
@@ -186,7 +186,7 @@ def _head_flags(compute_dtype):
 
 
 @ENCODERS.register_module()
-class NRTREncoder(nn.Module):
+class NRTREncoder(TrainBackendMixin, nn.Module):
     """Transformer encoder; `forward(feat (N, C, H, W), img_metas=None) -> (N, H*W, C)`."""
 
     def __init__(self, n_layers=6, n_head=8, d_k=64, d_v=64, d_model=512, d_inner=256, dropout=0.1,
@@ -249,14 +249,7 @@ class NRTREncoder(nn.Module):
         the masked attention with its dropout, every LayerNorm and the GELU on HIP kernels forward and backward
         (`ops.encoder_layer_autograd`: tpspp_attn_train.hip around the regressor's Linear / LayerNorm kernels; the
         residual additions and the two element-wise dropouts of a layer stay PyTorch ops).  No effect on the eval path."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
-        self._train_backend = mode
-        return self
-
-    @property
-    def train_backend(self):
-        return getattr(self, "_train_backend", "torch")
+        return super().set_train_backend(mode)
 
     def _forward_train_hip(self, feat, img_metas=None):
         """`_forward_graph` on the HIP training kernels, always fp32.  The seed of the attention dropout is drawn once per
@@ -301,7 +294,7 @@ class NRTREncoder(nn.Module):
 
 
 @DECODERS.register_module()
-class NRTRDecoder(nn.Module):
+class NRTRDecoder(TrainBackendMixin, nn.Module):
     """Transformer decoder; `forward(feat, out_enc, targets_dict=None, img_metas=None, train_mode=True)`.
     `train_mode=False`: greedy decoding -> per-step softmax scores (N, max_seq_len, num_classes - 1).
     `train_mode=True`: teacher-forced raw logits of `targets_dict['padded_targets']` (inference of the
@@ -418,14 +411,7 @@ class NRTRDecoder(nn.Module):
         (`_forward_train_graph`); "hip" -- the embedding, every matrix product, the causal self-attention and the
         cross-attention with their dropout, every LayerNorm, the GELU and the classifier on HIP kernels forward and backward
         (`_forward_train_hip`).  No effect on the eval and inference paths."""
-        if mode not in ("torch", "hip"):
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
-        self._train_backend = mode
-        return self
-
-    @property
-    def train_backend(self):
-        return getattr(self, "_train_backend", "torch")
+        return super().set_train_backend(mode)
 
     def _check_train_targets(self, targets, img_metas, n, t):
         """What the HIP training path refuses, on the host (`targets`: the (N, L) padded targets as they come from the
@@ -719,17 +705,9 @@ class EncodeDecodeRecognizer(nn.Module):
         (losses._SequenceLoss.set_train_backend).  No effect on the eval path."""
         if mode not in ("torch", "hip", "hip_all"):
             raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
-        if backbone is not None:
-            if backbone not in ("torch", "hip"):
-                raise ValueError(f'set_train_backend: backbone must be None, "torch" or "hip", got {backbone!r}')
-            if not hasattr(self.backbone, "set_train_backend"):
-                raise ValueError(f"set_train_backend: {type(self.backbone).__name__} has no HIP training path")
-        if encoder is not None:
-            if encoder not in ("torch", "hip"):
-                raise ValueError(f'set_train_backend: encoder must be None, "torch" or "hip", got {encoder!r}')
-            if not hasattr(self.encoder, "set_train_backend"):
-                raise ValueError(f"set_train_backend: {type(self.encoder).__name__} has no HIP training path")
-        for name, val, part in (("decoder", decoder, self.decoder), ("loss", loss, self.loss)):
+        parts = (("backbone", backbone, self.backbone), ("encoder", encoder, self.encoder),
+                 ("decoder", decoder, self.decoder), ("loss", loss, self.loss))
+        for name, val, part in parts:                        # a call that fails changes nothing: every check comes first
             if val is not None:
                 if val not in ("torch", "hip"):
                     raise ValueError(f'set_train_backend: {name} must be None, "torch" or "hip", got {val!r}')
@@ -737,14 +715,9 @@ class EncodeDecodeRecognizer(nn.Module):
                     raise ValueError(f"set_train_backend: {type(part).__name__} has no HIP training path")
         if self.tpsnet is not None and hasattr(self.tpsnet, "set_train_backend"):
             self.tpsnet.set_train_backend(mode)
-        if backbone is not None:
-            self.backbone.set_train_backend(backbone)
-        if encoder is not None:
-            self.encoder.set_train_backend(encoder)
-        if decoder is not None:
-            self.decoder.set_train_backend(decoder)
-        if loss is not None:
-            self.loss.set_train_backend(loss)
+        for _, val, part in parts:
+            if val is not None:
+                part.set_train_backend(val)
         return self
 
     def extract_feat(self, img, test=False, **kwargs):

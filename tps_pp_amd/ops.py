@@ -2262,10 +2262,12 @@ def bn_block_autograd(x, blk, cws=None, name="block"):
 
 # ---- training graph of the NRTR encoder (NRTREncoder.set_train_backend("hip"), tpspp_attn_train.hip) -------------------
 # Scaled-dot-product attention with the valid_ratio key mask and dropout on the probabilities, forward and backward
-# (include/tpspp_train_attn.h), and around it an encoder layer composed of the kernels above: `tpspp_plane_ln_*`,
-# `tpspp_mm_f32` (q / k / v as one product, GELU as w_1's epilogue), `tpspp_linear_bwd_weight`, `tpspp_act_bwd`.  Each
-# layer is two once-differentiable functions (norm1 - attention - fc, norm2 - w_1 - GELU - w_2); the two element-wise
-# dropouts and the residual additions between them stay PyTorch element-wise ops.
+# (include/tpspp_train_attn.h; every autograd path calls the `_ex` entry points of include/tpspp_train_dec.h, which add a
+# per-key mask, a causal mask and separate row strides and without them give the same bits), and around it an encoder
+# layer composed of the kernels above: `tpspp_plane_ln_*`, `tpspp_mm_f32` (q / k / v as one product, GELU as w_1's
+# epilogue), `tpspp_linear_bwd_weight`, `tpspp_act_bwd`.  Each layer is two once-differentiable functions (norm1 -
+# attention - fc, norm2 - w_1 - GELU - w_2); the two element-wise dropouts and the residual additions between them stay
+# PyTorch element-wise ops.
 
 _U64 = (1 << 64) - 1
 
@@ -2285,8 +2287,9 @@ def _row_stride(t):
 
 
 def _attn_operands(who, q, k, v):
-    """q (N, Tq, C), k / v (N, Tk, C) as the kernels take them: one row stride for the three (views of one fused
-    (N, T, 3C) projection pass as they are), dense copies otherwise."""
+    """q (N, Tq, C), k / v (N, Tk, C) as `tpspp_attn_train_fwd_ex` takes them: q with a row stride of its own, one row
+    stride for k and v (views of a fused (N, T, 2C) or (N, T, 3C) projection pass as they are), dense copies otherwise.
+    -> (q, k, v, ld_q, ld_kv)"""
     for name, t in (("q", q), ("k", k), ("v", v)):
         _chk_gpu(f"{who} {name}", t)
         if t.dtype != torch.float32:
@@ -2295,11 +2298,15 @@ def _attn_operands(who, q, k, v):
             raise ValueError(f"{who} {name}: expected (N, T, C), got {tuple(t.shape)}")
     if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
         raise ValueError(f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit together")
-    lds = {_row_stride(t) for t in (q, k, v)}
-    if len(lds) != 1 or None in lds:
-        q, k, v = (t.contiguous() for t in (q, k, v))
-        return q, k, v, q.shape[2]
-    return q, k, v, lds.pop()
+    if q.shape[2] % 64 or q.shape[2] == 0:
+        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
+    ld_q = _row_stride(q)
+    if ld_q is None:
+        q, ld_q = q.contiguous(), q.shape[2]
+    ld_kv = _row_stride(k)
+    if ld_kv is None or ld_kv != _row_stride(v):
+        k, v, ld_kv = k.contiguous(), v.contiguous(), k.shape[2]
+    return q, k, v, ld_q, ld_kv
 
 
 def _attn_valid_len(who, valid_len, N, dev):
@@ -2309,6 +2316,24 @@ def _attn_valid_len(who, valid_len, N, dev):
     if valid_len.shape[0] != N or valid_len.device != dev:
         raise ValueError(f"{who}: valid_len must be {N} int32 lengths on {dev}")
     return valid_len
+
+
+def _attn_key_mask(who, key_mask, N, Tk, dev):
+    """(N, Tk) bool or uint8 on the device, 0 = masked -> contiguous uint8, or None."""
+    if key_mask is None:
+        return None
+    if not isinstance(key_mask, torch.Tensor) or key_mask.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{who}: key_mask must be a bool or uint8 tensor")
+    if tuple(key_mask.shape) != (N, Tk) or key_mask.device != dev:
+        raise ValueError(f"{who}: key_mask must be ({N}, {Tk}) on {dev}, got {tuple(key_mask.shape)} on {key_mask.device}")
+    key_mask = key_mask.contiguous()
+    return key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
+
+
+def _attn_rate(who, drop_p):
+    if not 0.0 <= float(drop_p) < 1.0:
+        raise ValueError(f"{who}: drop_p must lie in [0, 1), got {drop_p!r}")
+    return float(drop_p)
 
 
 def attn_train_fwd(q, k, v, ld, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset):
@@ -2329,6 +2354,26 @@ def attn_train_bwd(d_out, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len,
                "tpspp_attn_train_bwd")
 
 
+def attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed, offset):
+    """`tpspp_attn_train_fwd_ex` on raw operands: (out (N*Tq, C), lse (N, heads, Tq))."""
+    out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
+    lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
+    _lib.check(_lib.lib().tpspp_attn_train_fwd_ex(_ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, N, C, heads, Tq, Tk, _ptr(valid_len),
+                                                  _ptr(key_mask), int(bool(causal)), float(drop_p), int(seed) & _U64,
+                                                  int(offset) & _U64, _ptr(out), _ptr(lse), _stream(q)),
+               "tpspp_attn_train_fwd_ex")
+    return out, lse
+
+
+def attn_train_bwd_ex(d_out, q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
+                      offset, dq, ld_dq, dk, dv, ld_dkv):
+    """`tpspp_attn_train_bwd_ex`: writes dq (N*Tq rows, `ld_dq` apart), dk, dv (N*Tk rows, `ld_dkv` apart)."""
+    _lib.check(_lib.lib().tpspp_attn_train_bwd_ex(_ptr(d_out), _ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, _ptr(out), _ptr(lse), N,
+                                                  C, heads, Tq, Tk, _ptr(valid_len), _ptr(key_mask), int(bool(causal)),
+                                                  float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(dq), ld_dq,
+                                                  _ptr(dk), _ptr(dv), ld_dkv, _stream(d_out)), "tpspp_attn_train_bwd_ex")
+
+
 def attn_dropout_mask(N, heads, Tq, Tk, drop_p, seed, offset, device):
     """`tpspp_attn_dropout_mask`: the (N, heads, Tq, Tk) uint8 keep mask the attention kernels apply for
     (seed, offset, drop_p).  For tests and debugging."""
@@ -2347,56 +2392,85 @@ class _AttnTrainFunction(torch.autograd.Function):
     recomputes the probabilities and regenerates the dropout mask from (seed, offset)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, valid_len, cfg):
-        drop_p, seed, offset = cfg
-        q, k, v, ld = _attn_operands("attn_train_autograd", q, k, v)
+    def forward(ctx, q, k, v, valid_len, key_mask, cfg):
+        causal, drop_p, seed, offset = cfg
+        q, k, v, ld_q, ld_kv = _attn_operands("attn_train_autograd_ex", q, k, v)
         N, Tq, C = q.shape
         Tk, heads = k.shape[1], C // 64
-        out, lse = attn_train_fwd(q, k, v, ld, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset)
-        ctx.save_for_backward(q, k, v, out, lse, valid_len)
-        ctx.cfg = (ld, drop_p, seed, offset)
+        out, lse = attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
+                                     offset)
+        ctx.save_for_backward(q, k, v, out, lse, valid_len, key_mask)
+        ctx.cfg = (ld_q, ld_kv) + cfg
         return out.view(N, Tq, C)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        q, k, v, out, lse, valid_len = ctx.saved_tensors
+        q, k, v, out, lse, valid_len, key_mask = ctx.saved_tensors
         if not any(ctx.needs_input_grad[:3]):
-            return (None,) * 5
-        ld, drop_p, seed, offset = ctx.cfg
+            return (None,) * 6
+        ld_q, ld_kv, causal, drop_p, seed, offset = ctx.cfg
         N, Tq, C = q.shape
         Tk, heads = k.shape[1], C // 64
-        gout = gout.float().contiguous()
         dq = torch.empty((N, Tq, C), device=q.device, dtype=torch.float32)
         dk = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
         dv = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
-        attn_train_bwd(gout, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset, dq, dk, dv, C)
-        return dq, dk, dv, None, None
+        attn_train_bwd_ex(gout.float().contiguous(), q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask,
+                          causal, drop_p, seed, offset, dq, C, dk, dv, C)
+        return dq, dk, dv, None, None, None
+
+
+def attn_train_autograd_ex(q, k, v, valid_len=None, key_mask=None, causal=False, drop_p=0.0, seed=0, offset=0):
+    """Differentiable multi-head attention on projected q (N, Tq, C), k, v (N, Tk, C), head h = columns [64h, 64h + 64):
+    dropout(softmax(mask(q k^T / 8))) v -> (N, Tq, C) (`tpspp_attn_train_fwd_ex` / `_bwd_ex`).  Key j is visible to query i
+    iff j < valid_len[b] (int32, on the device), key_mask[b, j] != 0 ((N, Tk) bool / uint8 on the device) and, with causal,
+    j <= i -- whichever are given.  A query with no visible key gives an output row of zeros and no gradient.  The dropout
+    keep decision of element (b, h, i, j) is a pure function of (seed, offset, b, h, i, j) (`attn_dropout_mask`
+    materialises it).  q may have a row stride of its own and k, v share one: views of one fused (N, T, 3C) projection, or a
+    (N, L, C) projection next to the halves of a fused (N, T, 2C) one, are read in place."""
+    who = "attn_train_autograd_ex"
+    drop_p = _attn_rate(who, drop_p)
+    _chk_gpu(f"{who} q", q)
+    if q.dim() != 3 or k.dim() != 3:
+        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
+    if max(q.shape[1], k.shape[1]) > 256:
+        raise ValueError(f"{who}: at most 256 tokens, got Tq = {q.shape[1]}, Tk = {k.shape[1]}")
+    valid_len = _attn_valid_len(who, valid_len, q.shape[0], q.device)
+    key_mask = _attn_key_mask(who, key_mask, q.shape[0], k.shape[1], q.device)
+    return _AttnTrainFunction.apply(q, k, v, valid_len, key_mask, (bool(causal), drop_p, int(seed), int(offset)))
 
 
 def attn_train_autograd(q, k, v, valid_len=None, drop_p=0.0, seed=0, offset=0):
-    """Differentiable multi-head attention on projected q (N, Tq, C), k, v (N, Tk, C), head h = columns [64h, 64h + 64):
-    dropout(softmax(mask(q k^T / 8))) v -> (N, Tq, C) (`tpspp_attn_train_fwd` / `_bwd`).  Keys j >= valid_len[b] (int32,
-    on the device) are masked; the dropout keep decision of element (b, h, i, j) is a pure function of (seed, offset,
-    b, h, i, j) (`attn_dropout_mask` materialises it).  Views of one fused (N, T, 3C) projection are read in place."""
-    if not 0.0 <= float(drop_p) < 1.0:
-        raise ValueError(f"attn_train_autograd: drop_p must lie in [0, 1), got {drop_p!r}")
-    _chk_gpu("attn_train_autograd q", q)
-    if q.dim() != 3 or q.shape[2] % 64:
-        raise ValueError(f"attn_train_autograd: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
-    valid_len = _attn_valid_len("attn_train_autograd", valid_len, q.shape[0], q.device)
-    return _AttnTrainFunction.apply(q, k, v, valid_len, (float(drop_p), int(seed), int(offset)))
+    """`attn_train_autograd_ex` with the valid_len mask alone: the encoder's attention."""
+    return attn_train_autograd_ex(q, k, v, valid_len, None, False, drop_p, seed, offset)
+
+
+def _unfuse(g, need, C):
+    """The gradient `g` of a fused weight or bias (or None), cut back into its projections' row blocks of C: one per entry
+    of `need`, None where that projection wants none."""
+    return [g[i * C:(i + 1) * C] if g is not None and n else None for i, n in enumerate(need)]
+
+
+def _attn_block_args(who, x, attn, drop_p):
+    x = _chk(f"{who} x", x, 3)
+    N, T, C = x.shape
+    if C != attn.dim_k or attn.d_k != 64 or attn.d_v != 64:
+        raise ValueError(f"{who}: token width {C} against {attn.n_head} heads of {attn.d_k}")
+    if T > 256:
+        raise ValueError(f"{who}: at most 256 tokens, got {T}")
+    biases = (attn.linear_q.bias, attn.linear_k.bias, attn.linear_v.bias)
+    if any(b is None for b in biases) and not all(b is None for b in biases):
+        raise ValueError(f"{who}: linear_q / _k / _v must all have a bias or none")
+    return x, biases, _attn_rate(who, drop_p)
 
 
 class _AttnBlockFunction(torch.autograd.Function):
-    """norm1 - q / k / v projections (one product) - attention - fc of a TFEncoderLayer on x (N, T, C), and with key_mask /
-    causal of a TFDecoderLayer's self-attention (the same kernels: `tpspp_attn_train_fwd_ex` without the two masks is
-    `tpspp_attn_train_fwd` bit for bit).  Saves x, the
-    LayerNorm statistics, the fused projection, the attention output and its log-sum-exp; the LayerNorm output is
-    recomputed in the backward."""
+    """norm1 - q / k / v projections (one product) - attention - fc on x (N, T, C): the attention block of a TFEncoderLayer
+    and, with key_mask and causal, the self-attention block of a TFDecoderLayer.  Saves x, the LayerNorm statistics, the
+    fused projection, the attention output and its log-sum-exp; the LayerNorm output is recomputed in the backward."""
 
     @staticmethod
-    def forward(ctx, x, n1w, n1b, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg, key_mask=None, causal=False):
+    def forward(ctx, x, n1w, n1b, wq, wk, wv, bq, bk, bv, fcw, fcb, valid_len, cfg, key_mask, causal):
         eps, drop_p, seed, offset = cfg
         N, T, C = x.shape
         M, heads = N * T, C // 64
@@ -2440,33 +2514,23 @@ class _AttnBlockFunction(torch.autograd.Function):
             dx = torch.empty_like(x) if need[0] else None
             dw_ln, db_ln = plane_ln_bwd(dy, x, n1w, m1, r1, dx=dx, want_params=need[1] or need[2])
             res[0], res[1], res[2] = dx, dw_ln if need[1] else None, db_ln if need[2] else None
-        for i in range(3):
-            if dw is not None and need[3 + i]:
-                res[3 + i] = dw[i * C:(i + 1) * C]
-            if db is not None and need[6 + i]:
-                res[6 + i] = db[i * C:(i + 1) * C]
+        res[3:6], res[6:9] = _unfuse(dw, need[3:6], C), _unfuse(db, need[6:9], C)
         res[9], res[10] = dw_fc, db_fc
         return tuple(res)
 
 
-def attn_block_autograd(x, attn, norm, valid_len=None, drop_p=0.0, seed=0, offset=0):
-    """fc(attention(norm(x))) of a TFEncoderLayer (`transformer_layers.py:57-75` up to the first dropout) on tokens x
-    (N, T, C), differentiable, on HIP kernels only.  attn: the MultiHeadAttention parameter holder, norm: its LayerNorm."""
-    x = _chk("attn_block_autograd x", x, 3)
-    N, T, C = x.shape
-    if C != attn.dim_k or attn.d_k != 64 or attn.d_v != 64:
-        raise ValueError(f"attn_block_autograd: token width {C} against {attn.n_head} heads of {attn.d_k}")
-    if T > 256:
-        raise ValueError(f"attn_block_autograd: at most 256 tokens, got {T}")
-    if not 0.0 <= float(drop_p) < 1.0:
-        raise ValueError(f"attn_block_autograd: drop_p must lie in [0, 1), got {drop_p!r}")
-    biases = (attn.linear_q.bias, attn.linear_k.bias, attn.linear_v.bias)
-    if any(b is None for b in biases) and not all(b is None for b in biases):
-        raise ValueError("attn_block_autograd: linear_q / _k / _v must all have a bias or none")
-    valid_len = _attn_valid_len("attn_block_autograd", valid_len, N, x.device)
+def attn_block_autograd(x, attn, norm, valid_len=None, drop_p=0.0, seed=0, offset=0, key_mask=None, causal=False):
+    """fc(attention(norm(x))) on tokens x (N, T, C), differentiable, on HIP kernels only: of a TFEncoderLayer
+    (`transformer_layers.py:57-75` up to the first dropout) and, with the pad mask of the targets as `key_mask` ((N, T) bool
+    / uint8, 0 = <PAD>) and `causal`, of a TFDecoderLayer's self-attention (`transformer_layers.py:133-147` up to the
+    dropout).  attn: the MultiHeadAttention parameter holder, norm: its LayerNorm."""
+    who = "attn_block_autograd"
+    x, biases, drop_p = _attn_block_args(who, x, attn, drop_p)
+    valid_len = _attn_valid_len(who, valid_len, x.shape[0], x.device)
+    key_mask = _attn_key_mask(who, key_mask, x.shape[0], x.shape[1], x.device)
     return _AttnBlockFunction.apply(x, norm.weight, norm.bias, attn.linear_q.weight, attn.linear_k.weight,
                                     attn.linear_v.weight, *biases, attn.fc.weight, attn.fc.bias, valid_len,
-                                    (float(norm.eps), float(drop_p), int(seed), int(offset)))
+                                    (float(norm.eps), drop_p, int(seed), int(offset)), key_mask, bool(causal))
 
 
 class _FfnBlockFunction(torch.autograd.Function):
@@ -2558,145 +2622,10 @@ def encoder_layer_autograd(x, lyr, valid_len=None, drop_p=0.0, seed=0, offset=0)
 
 
 # ---- the decoder's training graph and the loss on HIP kernels ---------------------------------------------------------------
-# include/tpspp_train_dec.h: the attention above with a per-key mask, a causal mask and separate row strides for q and
+# include/tpspp_train_dec.h: the attention above with its per-key mask, its causal mask and separate row strides for q and
 # k / v (the decoder's self- and cross-attention), the target embedding and the sequence cross-entropy.  A decoder layer is
 # three once-differentiable functions (norm1 - qkv - causal attention - fc, norm2 - q / fused k|v - attention - fc, norm3 -
 # w_1 - GELU - w_2); residual additions and element-wise dropouts stay PyTorch ops as in the encoder.
-
-def _attn_operands_ex(who, q, k, v):
-    """q (N, Tq, C), k / v (N, Tk, C) as `tpspp_attn_train_fwd_ex` takes them: q with a row stride of its own, one row
-    stride for k and v (views of a fused (N, T, 2C) or (N, T, 3C) projection pass as they are), dense copies otherwise."""
-    for name, t in (("q", q), ("k", k), ("v", v)):
-        _chk_gpu(f"{who} {name}", t)
-        if t.dtype != torch.float32:
-            raise TypeError(f"{who} {name}: expected float32, got {t.dtype}")
-        if t.dim() != 3:
-            raise ValueError(f"{who} {name}: expected (N, T, C), got {tuple(t.shape)}")
-    if k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise ValueError(f"{who}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not fit together")
-    if q.shape[2] % 64 or q.shape[2] == 0:
-        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
-    ld_q = _row_stride(q)
-    if ld_q is None:
-        q, ld_q = q.contiguous(), q.shape[2]
-    ld_kv = _row_stride(k)
-    if ld_kv is None or ld_kv != _row_stride(v):
-        k, v, ld_kv = k.contiguous(), v.contiguous(), k.shape[2]
-    return q, k, v, ld_q, ld_kv
-
-
-def _attn_key_mask(who, key_mask, N, Tk, dev):
-    """(N, Tk) bool or uint8 on the device, 0 = masked -> contiguous uint8, or None."""
-    if key_mask is None:
-        return None
-    if not isinstance(key_mask, torch.Tensor) or key_mask.dtype not in (torch.bool, torch.uint8):
-        raise TypeError(f"{who}: key_mask must be a bool or uint8 tensor")
-    if tuple(key_mask.shape) != (N, Tk) or key_mask.device != dev:
-        raise ValueError(f"{who}: key_mask must be ({N}, {Tk}) on {dev}, got {tuple(key_mask.shape)} on {key_mask.device}")
-    key_mask = key_mask.contiguous()
-    return key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
-
-
-def _attn_rate(who, drop_p):
-    if not 0.0 <= float(drop_p) < 1.0:
-        raise ValueError(f"{who}: drop_p must lie in [0, 1), got {drop_p!r}")
-    return float(drop_p)
-
-
-def attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed, offset):
-    """`tpspp_attn_train_fwd_ex` on raw operands: (out (N*Tq, C), lse (N, heads, Tq))."""
-    out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
-    lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
-    _lib.check(_lib.lib().tpspp_attn_train_fwd_ex(_ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, N, C, heads, Tq, Tk, _ptr(valid_len),
-                                                  _ptr(key_mask), int(bool(causal)), float(drop_p), int(seed) & _U64,
-                                                  int(offset) & _U64, _ptr(out), _ptr(lse), _stream(q)),
-               "tpspp_attn_train_fwd_ex")
-    return out, lse
-
-
-def attn_train_bwd_ex(d_out, q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
-                      offset, dq, ld_dq, dk, dv, ld_dkv):
-    """`tpspp_attn_train_bwd_ex`: writes dq (N*Tq rows, `ld_dq` apart), dk, dv (N*Tk rows, `ld_dkv` apart)."""
-    _lib.check(_lib.lib().tpspp_attn_train_bwd_ex(_ptr(d_out), _ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, _ptr(out), _ptr(lse), N,
-                                                  C, heads, Tq, Tk, _ptr(valid_len), _ptr(key_mask), int(bool(causal)),
-                                                  float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(dq), ld_dq,
-                                                  _ptr(dk), _ptr(dv), ld_dkv, _stream(d_out)), "tpspp_attn_train_bwd_ex")
-
-
-class _AttnTrainExFunction(torch.autograd.Function):
-    """`_AttnTrainFunction` with a per-key mask, a causal mask and separate row strides."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, valid_len, key_mask, cfg):
-        causal, drop_p, seed, offset = cfg
-        q, k, v, ld_q, ld_kv = _attn_operands_ex("attn_train_autograd_ex", q, k, v)
-        N, Tq, C = q.shape
-        Tk, heads = k.shape[1], C // 64
-        out, lse = attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
-                                     offset)
-        ctx.save_for_backward(q, k, v, out, lse, valid_len, key_mask)
-        ctx.cfg = (ld_q, ld_kv) + cfg
-        return out.view(N, Tq, C)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        q, k, v, out, lse, valid_len, key_mask = ctx.saved_tensors
-        if not any(ctx.needs_input_grad[:3]):
-            return (None,) * 6
-        ld_q, ld_kv, causal, drop_p, seed, offset = ctx.cfg
-        N, Tq, C = q.shape
-        Tk, heads = k.shape[1], C // 64
-        dq = torch.empty((N, Tq, C), device=q.device, dtype=torch.float32)
-        dk = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
-        dv = torch.empty((N, Tk, C), device=q.device, dtype=torch.float32)
-        attn_train_bwd_ex(gout.float().contiguous(), q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask,
-                          causal, drop_p, seed, offset, dq, C, dk, dv, C)
-        return dq, dk, dv, None, None, None
-
-
-def attn_train_autograd_ex(q, k, v, valid_len=None, key_mask=None, causal=False, drop_p=0.0, seed=0, offset=0):
-    """`attn_train_autograd` with the decoder's masks (`tpspp_attn_train_fwd_ex` / `_bwd_ex`): key j is visible to query i
-    iff j < valid_len[b], key_mask[b, j] != 0 ((N, Tk) bool / uint8 on the device) and, with causal, j <= i -- whichever
-    are given.  q may have a row stride of its own (a (N, L, C) projection next to k, v = the halves of a fused (N, T, 2C)
-    one).  A query with no visible key gives an output row of zeros and no gradient."""
-    who = "attn_train_autograd_ex"
-    drop_p = _attn_rate(who, drop_p)
-    _chk_gpu(f"{who} q", q)
-    if q.dim() != 3 or k.dim() != 3:
-        raise ValueError(f"{who}: expected (N, T, 64 * heads) operands, got q {tuple(q.shape)}")
-    if max(q.shape[1], k.shape[1]) > 256:
-        raise ValueError(f"{who}: at most 256 tokens, got Tq = {q.shape[1]}, Tk = {k.shape[1]}")
-    valid_len = _attn_valid_len(who, valid_len, q.shape[0], q.device)
-    key_mask = _attn_key_mask(who, key_mask, q.shape[0], k.shape[1], q.device)
-    return _AttnTrainExFunction.apply(q, k, v, valid_len, key_mask, (bool(causal), drop_p, int(seed), int(offset)))
-
-
-def _attn_block_args(who, x, attn, drop_p):
-    x = _chk(f"{who} x", x, 3)
-    N, T, C = x.shape
-    if C != attn.dim_k or attn.d_k != 64 or attn.d_v != 64:
-        raise ValueError(f"{who}: token width {C} against {attn.n_head} heads of {attn.d_k}")
-    if T > 256:
-        raise ValueError(f"{who}: at most 256 tokens, got {T}")
-    biases = (attn.linear_q.bias, attn.linear_k.bias, attn.linear_v.bias)
-    if any(b is None for b in biases) and not all(b is None for b in biases):
-        raise ValueError(f"{who}: linear_q / _k / _v must all have a bias or none")
-    return x, biases, _attn_rate(who, drop_p)
-
-
-def self_attn_block_autograd(x, attn, norm, key_mask=None, causal=True, valid_len=None, drop_p=0.0, seed=0, offset=0):
-    """fc(attention(norm(x))) of a TFDecoderLayer's self-attention (`transformer_layers.py:133-147` up to the dropout) on
-    tokens x (N, L, C): `attn_block_autograd` -- the same function -- with the pad mask of the targets as `key_mask`
-    ((N, L) bool / uint8, 0 = <PAD>) and the causal mask."""
-    who = "self_attn_block_autograd"
-    x, biases, drop_p = _attn_block_args(who, x, attn, drop_p)
-    valid_len = _attn_valid_len(who, valid_len, x.shape[0], x.device)
-    key_mask = _attn_key_mask(who, key_mask, x.shape[0], x.shape[1], x.device)
-    return _AttnBlockFunction.apply(x, norm.weight, norm.bias, attn.linear_q.weight, attn.linear_k.weight,
-                                    attn.linear_v.weight, *biases, attn.fc.weight, attn.fc.bias, valid_len,
-                                    (float(norm.eps), drop_p, int(seed), int(offset)), key_mask, bool(causal))
-
 
 class _CrossAttnBlockFunction(torch.autograd.Function):
     """norm2 - q projection on x (N, L, C); one fused k | v projection (N*T, 2C) on the encoder output; attention with
@@ -2748,11 +2677,7 @@ class _CrossAttnBlockFunction(torch.autograd.Function):
             res[4], res[7] = dwq, dbq
         if any(need[5:7]) or any(need[8:10]):
             dw, db = linear_bwd_weight(dkv, enc, _dense(MT, C), 2 * C, C, any(need[5:7]), any(need[8:10]))
-            for i in range(2):
-                if dw is not None and need[5 + i]:
-                    res[5 + i] = dw[i * C:(i + 1) * C]
-                if db is not None and need[8 + i]:
-                    res[8 + i] = db[i * C:(i + 1) * C]
+            res[5:7], res[8:10] = _unfuse(dw, need[5:7], C), _unfuse(db, need[8:10], C)
         if any((need[0], need[2], need[3])):
             dy = linear_bwd_data(dqp, wq, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
             dx = torch.empty_like(x) if need[0] else None
@@ -2970,7 +2895,7 @@ def decoder_layer_autograd(x, out_enc, lyr, key_mask=None, valid_len=None, drop_
     `offset` is the layer's index: the dropout on the attention probabilities uses (seed, 2 * offset) in the
     self-attention and (seed, 2 * offset + 1) in the cross-attention."""
     import torch.nn.functional as Fn
-    a = self_attn_block_autograd(x, lyr.self_attn, lyr.norm1, key_mask, True, None, drop_p, seed, 2 * offset)
+    a = attn_block_autograd(x, lyr.self_attn, lyr.norm1, None, drop_p, seed, 2 * offset, key_mask=key_mask, causal=True)
     x = x + Fn.dropout(a, drop_p, drop_p > 0)
     a = cross_attn_block_autograd(x, out_enc, lyr.enc_attn, lyr.norm2, valid_len, drop_p, seed, 2 * offset + 1)
     x = x + Fn.dropout(a, drop_p, drop_p > 0)

@@ -73,6 +73,23 @@ class Registry:
         return cls(**args)
 
 
+class TrainBackendMixin:
+    """The switch between the kernels a module's training graph runs on: "torch", the PyTorch composition of its layers,
+    or a HIP path.  What each mode means is the inheriting class's to say; it touches neither parameters nor state_dict."""
+    TRAIN_BACKENDS = ("torch", "hip")
+
+    def set_train_backend(self, mode):
+        if mode not in self.TRAIN_BACKENDS:
+            names = [f'"{m}"' for m in self.TRAIN_BACKENDS]
+            raise ValueError(f'set_train_backend: {", ".join(names[:-1])} or {names[-1]}, got {mode!r}')
+        self._train_backend = mode
+        return self
+
+    @property
+    def train_backend(self):
+        return getattr(self, "_train_backend", "torch")       # also on an object built before the attribute existed
+
+
 BACKBONES = Registry("backbone")
 PREPROCESSOR = Registry("preprocessor")
 ENCODERS = Registry("encoder")

@@ -22,7 +22,7 @@ import torch.nn as nn
 from .precision import default_compute_dtype
 from . import ops
 from ._prepared import invalidate_prepared, prepared
-from .registry import BACKBONES
+from .registry import BACKBONES, TrainBackendMixin
 
 
 class BasicBlock(nn.Module):
@@ -101,7 +101,7 @@ class BasicBlock(nn.Module):
 
 
 @BACKBONES.register_module()
-class ResNetABI_v2_large(nn.Module):
+class ResNetABI_v2_large(TrainBackendMixin, nn.Module):
     """`resnet_v2_large.py:25-196`."""
 
     def __init__(self, in_channels=3, stem_channels=32, base_channels=32, arch_settings=[3, 4, 6, 6, 3],
@@ -159,21 +159,12 @@ class ResNetABI_v2_large(nn.Module):
         return ops.conv2d([x.float().contiguous()], self._stem_weight(), 1, True)
 
     # ---- training graph on the HIP kernels (tpspp_bn_train.hip + the convolution kernels) ------------------------------
-    TRAIN_BACKENDS = ("torch", "hip")
-
     def set_train_backend(self, mode):
         """Which kernels the backbone's training graph (`.train()`, or eval mode with an input that carries gradients) runs
         on: "torch" (default) -- the PyTorch composition of its layers, as the reference runs them; "hip" -- the stem and
         every BasicBlock on `ops.bn_stem_autograd` / `ops.bn_block_autograd` (HIP forward and backward; each BatchNorm
         follows its own mode).  Touches neither the parameters, the buffers, the state_dict nor the eval path."""
-        if mode not in self.TRAIN_BACKENDS:
-            raise ValueError(f'set_train_backend: "torch" or "hip", got {mode!r}')
-        self._train_backend = mode
-        return self
-
-    @property
-    def train_backend(self):
-        return getattr(self, "_train_backend", "torch")
+        return super().set_train_backend(mode)
 
     def _train_cw(self, name, conv):
         """The forward's weight layouts of one convolution, cached and rebuilt on the device when its parameters change

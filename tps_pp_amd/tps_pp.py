@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from .precision import default_compute_dtype
 from . import constants, ops
 from ._prepared import invalidate_prepared, prepared
-from .registry import BACKBONES, PREPROCESSOR
+from .registry import BACKBONES, PREPROCESSOR, TrainBackendMixin
 
 
 class ConvModule(nn.Module):
@@ -288,7 +288,7 @@ class Attention_Enhanced_TPS(nn.Module):
 
 
 @BACKBONES.register_module()
-class TPS_PP(nn.Module):
+class TPS_PP(TrainBackendMixin, nn.Module):
     """TPS++ rectifier (`tps_pp.py:499-625`).
 
     Args (as the reference): img_size, rectified_img_size (tuples), num_img_channel, point_size,
@@ -665,14 +665,7 @@ class TPS_PP(nn.Module):
         PyTorch; "hip_all" -- the convolutions as "hip" and every other layer on HIP as well (`ops.cbam_autograd`,
         `ops.dgab_autograd`, `ops.tpe_points_autograd`, `ops.score_autograd`).  The warp is `ops.warp_autograd` in all
         three.  Touches neither the parameters, the state_dict nor the eval path."""
-        if mode not in self.TRAIN_BACKENDS:
-            raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
-        self._train_backend = mode
-        return self
-
-    @property
-    def train_backend(self):
-        return getattr(self, "_train_backend", "torch")
+        return super().set_train_backend(mode)
 
     def _train_conv(self, name, mod, srcs, stride):
         """One ConvModule (conv + in-place ReLU) on `ops.conv2d_autograd`; the forward's weight layouts are cached
