@@ -19,7 +19,8 @@ import torch.nn.functional as F
 
 import cases
 import guarded_alloc as GA
-from tps_pp_amd import NRTRDecoder, losses, ops
+from freeze_patterns import check_freeze_patterns
+from tps_pp_amd import NRTRDecoder, TFDecoderLayer, TFEncoderLayer, losses, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -661,6 +662,47 @@ def test_eval_paths_do_not_depend_on_the_train_backend(cuda):
                          m(None, out_enc, {"padded_targets": targets}, metas, train_mode=True)]
     ok, why = GA.same_bits(res["torch"], res["hip"])
     assert ok, why
+
+
+# ---- 10b. frozen layers --------------------------------------------------------------------------------------------------
+def frozen_blocks(cuda):
+    """{name: (Function, call, inputs, {name: Parameter}, the last Linear, further patterns)} on d_model 128 (2 heads),
+    N = 3, T = 20 encoder tokens, L = 9 target positions, attention dropout 0.1: the attention block of an encoder layer
+    (with q / k / v / fc biases) under valid_len with one short row, and the three blocks of a decoder layer (its
+    self-attention under a pad mask with one padded tail)."""
+    torch.manual_seed(8)
+    enc, dec = TFEncoderLayer(128, 64, 2, qkv_bias=True).to(cuda), TFDecoderLayer(128, 64, 2).to(cuda)
+    g = torch.Generator().manual_seed(9)
+    xt, xl = torch.randn((3, 20, 128), generator=g).to(cuda), torch.randn((3, 9, 128), generator=g).to(cuda)
+    out_enc = torch.randn((3, 20, 128), generator=g).to(cuda)
+    vl = torch.tensor([20, 7, 20], dtype=torch.int32, device=cuda)
+    pad = torch.ones((3, 9), dtype=torch.bool, device=cuda)
+    pad[1, 5:] = False
+
+    def named(attn, norm, first="attn"):
+        return {**dict(attn.named_parameters(prefix=first)), **dict(norm.named_parameters(prefix="norm"))}
+
+    return {
+        "self-valid_len": (ops._AttnBlockFunction, lambda x: ops.attn_block_autograd(x, enc.attn, enc.norm1, vl, 0.1, 3, 1),
+                           [xt], named(enc.attn, enc.norm1), "attn.fc.", None),
+        "self-causal": (ops._AttnBlockFunction,
+                        lambda x: ops.attn_block_autograd(x, dec.self_attn, dec.norm1, None, 0.1, 3, 2, key_mask=pad,
+                                                          causal=True),
+                        [xl], named(dec.self_attn, dec.norm1), "attn.fc.", None),
+        "cross": (ops._CrossAttnBlockFunction,
+                  lambda x, e: ops.cross_attn_block_autograd(x, e, dec.enc_attn, dec.norm2, vl, 0.1, 3, 3),
+                  [xl, out_enc], named(dec.enc_attn, dec.norm2), "attn.fc.",
+                  {"out_enc frozen": {"input0"} | set(named(dec.enc_attn, dec.norm2)),
+                   "only out_enc trainable": {"input1"}}),
+        "ffn": (ops._FfnBlockFunction, lambda x: ops.ffn_block_autograd(x, dec.mlp, dec.norm3), [xl],
+                named(dec.mlp, dec.norm3, "mlp"), "mlp.w_2.", None),
+    }
+
+
+@pytest.mark.parametrize("name", ["self-valid_len", "self-causal", "cross", "ffn"])
+def test_freeze_patterns_return_none_and_keep_the_bits(cuda, name, monkeypatch):
+    fn_cls, call, inputs, params, last, more = frozen_blocks(cuda)[name]
+    check_freeze_patterns(monkeypatch, fn_cls, call, inputs, params, last, more)
 
 
 # ---- 11. recogniser ------------------------------------------------------------------------------------------------------

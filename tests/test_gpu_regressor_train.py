@@ -14,6 +14,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import cases
+from freeze_patterns import check_freeze_patterns
 from tps_pp_amd import TPS_PP, ops
 
 pytestmark = pytest.mark.gpu
@@ -371,6 +372,16 @@ def test_frozen_dgab_gives_input_gradients_only(cuda):
     gi32, _ = reference_grads("dgab", mod, inputs, gout, torch.float32, "cuda")
     for g, w, t in zip(gin, gi64, gi32):
         assert g is not None and rel(g, w) <= max(1e-5, 2 * rel(t, w))
+
+
+@pytest.mark.parametrize("kind", ["dgab", "score", "points"])
+def test_freeze_patterns_return_none_and_keep_the_bits(cuda, kind, monkeypatch):
+    fn_cls, fn, last = {"dgab": (ops._DgabFunction, ops.dgab_autograd, "mlp.fc2."),
+                        "score": (ops._ScoreFunction, ops.score_autograd, "p_linear.1."),
+                        "points": (ops._TpePointsFunction, ops.tpe_points_autograd, "localization_fc2.")}[kind]
+    mod = block_module(kind).to(cuda)
+    inputs = [t.to(cuda) for t in block_inputs(kind, 3, seed=12)]
+    check_freeze_patterns(monkeypatch, fn_cls, lambda *xs: fn(*xs, mod), inputs, dict(mod.named_parameters()), last)
 
 
 # ---- 6. training tracks torch --------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@ anything else raises -- there is no eager / CPU fallback on purpose.
 import ctypes
 
 import torch
+import torch.nn.functional as Fn
 
 from . import _lib
 
@@ -30,6 +31,11 @@ def _ptr_array(objs):
 
 def _int_array(values, ctype=ctypes.c_int):
     return (ctype * len(values))(*values)
+
+
+def _ws(n, device):
+    """The float32 workspace of a `*_workspace_floats` query (at least one element, so that its pointer is never NULL)."""
+    return torch.empty((max(n, 1),), device=device, dtype=torch.float32)
 
 
 def _chk_gpu(who, t):
@@ -1552,10 +1558,16 @@ def linear_fwd(x, desc, weight, bias=None, epi=0, R=None):
     return y
 
 
-def linear_bwd_data(dy, weight, out, desc):
-    """out (token operand `desc`) = dy (rows, O) W; dy dense."""
-    nb, Mi, sb, si, sk = desc
+def linear_bwd_data(dy, weight, out=None, desc=None):
+    """out (token operand `desc`) = dy (rows, O) W; dy dense.  Without `out`: a fresh (rows, K) tensor, `desc` then being
+    `_dense(rows, K)` or left out (the tokens of an NCHW map are written into the caller's `out`)."""
     O, K = weight.shape
+    if out is None:
+        rows = dy.numel() // O
+        if desc not in (None, _dense(rows, K)):
+            raise ValueError(f"linear_bwd_data: the token operand {desc} is not _dense({rows}, {K}): pass `out`")
+        out, desc = torch.empty((rows, K), device=dy.device, dtype=torch.float32), _dense(rows, K)
+    nb, Mi, sb, si, sk = desc
     mm(dy, (Mi * O, O, 1), weight, (0, 1, K), out, (sb, si, sk), nb, Mi, K, O)
     return out
 
@@ -1575,7 +1587,7 @@ def linear_bwd_weight(dy, x, desc, O, K, want_weight=True, want_bias=True, x_gel
     dw = torch.empty((O, K), device=dev, dtype=torch.float32) if want_weight else None
     db = torch.empty((O,), device=dev, dtype=torch.float32) if want_bias else None
     n = linear_bwd_weight_workspace_floats(M, O, K)
-    ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32)
+    ws = _ws(n, dev)
     lay = _i64(Mi, sb, si, sk)
     _lib.check(_lib.lib().tpspp_linear_bwd_weight(_ptr(dy), _ptr(x), _vp(lay), 2 if x_gelu else 0, M, O, K, _ptr(dw), _ptr(db), _ptr(ws), n,
                                                   _stream(dy)), "tpspp_linear_bwd_weight")
@@ -1614,13 +1626,13 @@ def plane_ln_bwd(dy, x, weight, mean, rstd, dx=None, accumulate=False, want_para
     P = weight.numel()
     rows = x.numel() // P
     dev = x.device
-    dw = db = None
+    dw = db = ws = None
     n = 0
     if want_params:
         dw = torch.empty((P,), device=dev, dtype=torch.float32)
         db = torch.empty((P,), device=dev, dtype=torch.float32)
         n = plane_ln_bwd_workspace_floats(rows, P)
-    ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32) if want_params else None
+        ws = _ws(n, dev)
     if dx is None and not want_params:
         return None, None
     _lib.check(_lib.lib().tpspp_plane_ln_bwd(_ptr(dy), _ptr(x), _ptr(weight), _ptr(mean), _ptr(rstd), rows, P, _ptr(dx),
@@ -1629,8 +1641,60 @@ def plane_ln_bwd(dy, x, weight, mean, rstd, dx=None, accumulate=False, want_para
     return (dw.view(weight.shape), db.view(weight.shape)) if want_params else (None, None)
 
 
-def _need(ctx, i):
-    return bool(ctx.needs_input_grad[i])
+def _ln_bwd(dy, x, weight, mean, rstd, need, into=None):
+    """`plane_ln_bwd` as an autograd backward wants it, need = (x, weight, bias) -> (dx, dweight, dbias), None where not
+    needed and no launch when none is.  dx is a fresh tensor, or `into` with the gradient added to it in place."""
+    dx = (torch.empty_like(x) if into is None else into) if need[0] else None
+    dw, db = plane_ln_bwd(dy, x, weight, mean, rstd, dx=dx, accumulate=into is not None, want_params=need[1] or need[2])
+    return dx, dw if need[1] else None, db if need[2] else None
+
+
+def _mlp_fwd(x, nw, nb, eps, w1, b1, w2, b2, residual=False):
+    """fc2(GELU(fc1(LayerNorm(x)))) (+ x with residual) over rows of w1.shape[1] elements: (y shaped like x, mean, rstd)."""
+    hid, K = w1.shape
+    rows = x.numel() // K
+    xn, mean, rstd = plane_ln_fwd(x, nw, nb, eps)
+    g = linear_fwd(xn, _dense(rows, K), w1, b1, epi=2)
+    return linear_fwd(g, _dense(rows, hid), w2, b2, R=x if residual else None).view(x.shape), mean, rstd
+
+
+def _mlp_bwd(gy, x, nw, nb, mean, rstd, eps, w1, b1, w2, need, residual=False):
+    """Backward of `_mlp_fwd` from gy (contiguous, shaped like x), need = (x, nw, nb, w1, b1, w2, b2) -> the seven
+    gradients in that order.  The LayerNorm output and fc1's pre-activation u are recomputed.  With residual, dx is a copy
+    of gy that the LayerNorm backward adds to in place."""
+    hid, K = w1.shape
+    rows = x.numel() // K
+    xn, _, _ = plane_ln_fwd(x, nw, nb, eps)
+    u = linear_fwd(xn, _dense(rows, K), w1, b1)
+    # fc2's input GELU(u) is formed from u as the weight gradient stages it
+    dw2, db2 = linear_bwd_weight(gy, u, _dense(rows, hid), K, hid, need[5], need[6], x_gelu=True)
+    du = linear_bwd_data(gy, w2)
+    act_bwd(ACT_GELU, du, u, out=du)
+    del u
+    dw1, db1 = linear_bwd_weight(du, xn, _dense(rows, K), hid, K, need[3], need[4])
+    del xn
+    dx = dnw = dnb = None
+    if any(need[:3]):
+        dxn = linear_bwd_data(du, w1)
+        del du
+        into = torch.empty_like(gy).copy_(gy) if residual else None
+        dx, dnw, dnb = _ln_bwd(dxn, x, nw, mean, rstd, need[:3], into=into)
+    return dx, dnw, dnb, dw1, db1, dw2, db2
+
+
+def _two_linear_bwd(dy, h, w2, x, desc, w1, need, act=None):
+    """Backward of W2 f(W1 x + b1) + b2 from dy (rows, O) dense: h (rows, H) is the saved f(W1 x + b1), f the identity or
+    the activation `act` (ACT_RELU: one whose derivative `act_bwd` takes from its output), x the token operand `desc`.
+    need = (x, w1, b1, w2, b2) -> the five gradients in that order, dx shaped like x."""
+    H, K = w1.shape
+    rows = desc[0] * desc[1]
+    dw2, db2 = linear_bwd_weight(dy, h, _dense(rows, H), w2.shape[0], H, need[3], need[4])
+    dh = linear_bwd_data(dy, w2)
+    if act is not None:
+        act_bwd(act, dh, h, out=dh)
+    dw1, db1 = linear_bwd_weight(dh, x, desc, H, K, need[1], need[2])
+    dx = linear_bwd_data(dh, w1, torch.empty_like(x), desc) if need[0] else None
+    return dx, dw1, db1, dw2, db2
 
 
 class _DgabFunction(torch.autograd.Function):
@@ -1652,12 +1716,9 @@ class _DgabFunction(torch.autograd.Function):
         hv = linear_fwd(cath, _dense(N * C, H + T), mhw)
         A = torch.empty_like(x)
         _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
-        rows = N * C * H
-        x1 = linear_fwd(A, _dense(rows, W), pw, pb, R=x).view(N, C, H, W)
+        x1 = linear_fwd(A, _dense(N * C * H, W), pw, pb, R=x).view(N, C, H, W)
         del A, xn, catw, cath
-        x2n, m2, r2 = plane_ln_fwd(x1, ln2w, ln2b, eps2)
-        g = linear_fwd(x2n, _dense(rows, W), f1w, f1b, epi=2)
-        out = linear_fwd(g, _dense(rows, f1w.shape[0]), f2w, f2b, R=x1).view(N, C, H, W)
+        out, m2, r2 = _mlp_fwd(x1, ln2w, ln2b, eps2, f1w, f1b, f2w, f2b, residual=True)
         ctx.eps = (eps1, eps2)
         ctx.save_for_backward(x, y, wv, hv, x1, m1, r1, m2, r2, ln1w, ln1b, mww, mhw, pw, pb, ln2w, ln2b, f1w, f1b, f2w)
         return out
@@ -1672,24 +1733,13 @@ class _DgabFunction(torch.autograd.Function):
         L = _lib.lib()
         N, C, H, W = x.shape
         T = y.shape[2]
-        rows, hid = N * C * H, f1w.shape[0]
+        rows = N * C * H
         st = _stream(x)
         eps1, eps2 = ctx.eps
-        gout = gout.float().contiguous()
-        # ---- mlp (fc1 - GELU - fc2 along W) and norm2; x2n and u recomputed
-        x2n, _, _ = plane_ln_fwd(x1, ln2w, ln2b, eps2)
-        u = linear_fwd(x2n, _dense(rows, W), f1w, f1b)
-        # fc2's input GELU(u) is formed from u as the weight gradient stages it
-        dw_f2, db_f2 = linear_bwd_weight(gout, u, _dense(rows, hid), W, hid, need[12], need[13], x_gelu=True)
-        du = linear_bwd_data(gout, f2w, torch.empty((rows, hid), device=x.device, dtype=torch.float32), _dense(rows, hid))
-        act_bwd(ACT_GELU, du, u, out=du)
-        del u
-        dw_f1, db_f1 = linear_bwd_weight(du, x2n, _dense(rows, W), hid, W, need[10], need[11])
-        dx2n = linear_bwd_data(du, f1w, torch.empty((rows, W), device=x.device, dtype=torch.float32), _dense(rows, W))
-        del du
-        dx1 = torch.empty_like(gout).copy_(gout)          # (the kernels below accumulate into it in place)
-        dw_ln2, db_ln2 = plane_ln_bwd(dx2n, x1, ln2w, m2, r2, dx=dx1, accumulate=True, want_params=need[8] or need[9])
-        del dx2n, x2n
+        # ---- mlp (fc1 - GELU - fc2 along W) and norm2; x2n and u recomputed.  dx1 starts as a copy of gout (the residual)
+        # and the kernels below accumulate into it in place
+        dx1, *d_mlp = _mlp_bwd(gout.float().contiguous(), x1, ln2w, ln2b, m2, r2, eps2, f1w, f1b, f2w, (True, *need[8:14]),
+                               residual=True)
         # ---- attention: proj, gate, mlp_w / mlp_h, the pooled means; xn and A recomputed
         xn, _, _ = plane_ln_fwd(x, ln1w, ln1b, eps1)
         dw_p = db_p = None
@@ -1698,7 +1748,7 @@ class _DgabFunction(torch.autograd.Function):
             _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
             dw_p, db_p = linear_bwd_weight(dx1, A, _dense(rows, W), W, W, need[6], need[7])
             del A
-        dA = linear_bwd_data(dx1, pw, torch.empty((rows, W), device=x.device, dtype=torch.float32), _dense(rows, W))
+        dA = linear_bwd_data(dx1, pw)
         dxn = torch.empty_like(x)
         dwv, dhv = torch.empty_like(wv), torch.empty_like(hv)
         _lib.check(L.tpspp_dgab_gate_bwd(_ptr(dA), _ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(dxn), _ptr(dwv), _ptr(dhv),
@@ -1713,18 +1763,14 @@ class _DgabFunction(torch.autograd.Function):
             dw_mw, _ = linear_bwd_weight(dwv, catw, _dense(N * C, W + T), W + 1, W + T, need[4], False)
             dw_mh, _ = linear_bwd_weight(dhv, cath, _dense(N * C, H + T), H + 1, H + T, need[5], False)
             del catw, cath
-        dcatw = linear_bwd_data(dwv, mww, torch.empty((N * C, W + T), device=x.device, dtype=torch.float32),
-                                _dense(N * C, W + T))
-        dcath = linear_bwd_data(dhv, mhw, torch.empty((N * C, H + T), device=x.device, dtype=torch.float32),
-                                _dense(N * C, H + T))
+        dcatw = linear_bwd_data(dwv, mww)
+        dcath = linear_bwd_data(dhv, mhw)
         dy = torch.empty_like(y) if need[1] else None
         _lib.check(L.tpspp_dgab_pool_bwd(_ptr(dcatw), _ptr(dcath), N, C, H, W, T, _ptr(dxn), _ptr(dy), st),
                    "tpspp_dgab_pool_bwd")
         del dcatw, dcath
-        dx = dx1 if need[0] else None
-        dw_ln1, db_ln1 = plane_ln_bwd(dxn, x, ln1w, m1, r1, dx=dx, accumulate=True, want_params=need[2] or need[3])
-        return (dx, dy, dw_ln1 if need[2] else None, db_ln1 if need[3] else None, dw_mw, dw_mh, dw_p, db_p,
-                dw_ln2 if need[8] else None, db_ln2 if need[9] else None, dw_f1, db_f1, dw_f2, db_f2, None, None)
+        dx, dw_ln1, db_ln1 = _ln_bwd(dxn, x, ln1w, m1, r1, (need[0], need[2], need[3]), into=dx1)
+        return (dx, dy, dw_ln1, db_ln1, dw_mw, dw_mh, dw_p, db_p, *d_mlp, None, None)
 
 
 def _lin(m):
@@ -1783,22 +1829,12 @@ class _ScoreFunction(torch.autograd.Function):
         if need[0] or any(need[2:6]):
             da = torch.empty((N * HW, D), device=dev, dtype=torch.float32)
             mm(dT, (F * HW, 1, HW), b, (F * D, 1, D), da, (HW * D, D, 1), N, HW, D, F)
-            res[4], res[5] = linear_bwd_weight(da, a1, _dense(N * HW, f1w.shape[0]), D, f1w.shape[0], need[4], need[5])
-            da1 = linear_bwd_data(da, f2w, torch.empty((N * HW, f1w.shape[0]), device=dev, dtype=torch.float32),
-                                  _dense(N * HW, f1w.shape[0]))
+            res[0], *res[2:6] = _two_linear_bwd(da, a1, f2w, de, dd, f1w, (need[0], *need[2:6]))
             del da
-            res[2], res[3] = linear_bwd_weight(da1, de, dd, f1w.shape[0], f1w.shape[1], need[2], need[3])
-            if need[0]:
-                res[0] = linear_bwd_data(da1, f1w, torch.empty_like(de), dd)
         if need[1] or any(need[6:10]):
             db = torch.empty((N * F, D), device=dev, dtype=torch.float32)
             mm(dT, (F * HW, HW, 1), a, (HW * D, 1, D), db, (F * D, D, 1), N, F, D, HW)
-            res[8], res[9] = linear_bwd_weight(db, p1, _dense(N * F, p1w.shape[0]), D, p1w.shape[0], need[8], need[9])
-            dp1 = linear_bwd_data(db, p2w, torch.empty((N * F, p1w.shape[0]), device=dev, dtype=torch.float32),
-                                  _dense(N * F, p1w.shape[0]))
-            res[6], res[7] = linear_bwd_weight(dp1, en, de_, p1w.shape[0], p1w.shape[1], need[6], need[7])
-            if need[1]:
-                res[1] = linear_bwd_data(dp1, p1w, torch.empty_like(en), de_)
+            res[1], *res[6:10] = _two_linear_bwd(db, p1, p2w, en, de_, p1w, (need[1], *need[6:10]))
         return tuple(res)
 
 
@@ -1841,7 +1877,7 @@ class _CbamFunction(torch.autograd.Function):
         g = [torch.empty(t.shape, device=dev, dtype=torch.float32) if need[i + 1] else None
              for i, t in enumerate((w1, w2, cw, cb))]
         n = cbam_bwd_workspace_floats(N, C, Cr)
-        ws = torch.empty((max(n, 1),), device=dev, dtype=torch.float32)
+        ws = _ws(n, dev)
         _lib.check(_lib.lib().tpspp_cbam_bwd(_ptr(gout), _ptr(x), _ptr(w1), _ptr(w2), _ptr(cw), _ptr(cb), N, C, Cr, H, W,
                                              _ptr(dx), *(_ptr(t) for t in g), _ptr(ws), n, _stream(x)), "tpspp_cbam_bwd")
         return (dx if need[0] else None, *g)
@@ -1886,20 +1922,14 @@ class _TpePointsFunction(torch.autograd.Function):
         N = en.shape[0]
         de_ = _nchw_tokens(en)
         T = de_[1]
-        Ha, Hb = aw.shape[0], bw.shape[0]
-        dev = en.device
+        Hb = bw.shape[0]
         gcp = gcp.float().contiguous()
         res = [None] * 7
         res[5], res[6] = linear_bwd_weight(gcp, h2, _dense(N, T * Hb), cw.shape[0], T * Hb, need[5], need[6])
-        if need[0] or any(need[1:5]):
-            dh2 = linear_bwd_data(gcp, cw, torch.empty((N, T * Hb), device=dev, dtype=torch.float32), _dense(N, T * Hb))
+        if any(need[:5]):
+            dh2 = linear_bwd_data(gcp, cw)          # (N, T * Hb): the (N * T, Hb) rows of fc1b
             act_bwd(ACT_RELU, dh2, h2, out=dh2)
-            res[3], res[4] = linear_bwd_weight(dh2, h1, _dense(N * T, Ha), Hb, Ha, need[3], need[4])
-            dh1 = linear_bwd_data(dh2, bw, torch.empty((N * T, Ha), device=dev, dtype=torch.float32), _dense(N * T, Ha))
-            act_bwd(ACT_RELU, dh1, h1, out=dh1)
-            res[1], res[2] = linear_bwd_weight(dh1, en, de_, Ha, aw.shape[1], need[1], need[2])
-            if need[0]:
-                res[0] = linear_bwd_data(dh1, aw, torch.empty_like(en), de_)
+            res[:5] = _two_linear_bwd(dh2, h1, bw, en, de_, aw, need[:5], act=ACT_RELU)
         return tuple(res)
 
 
@@ -1963,7 +1993,7 @@ def bn_train_stats(z, eps=1e-5, momentum=0.1, running_mean=None, running_var=Non
     mean = torch.empty((C,), device=dev, dtype=torch.float32)
     rstd = torch.empty((C,), device=dev, dtype=torch.float32)
     nws = bn_stats_workspace_floats(N, C, HW)
-    ws = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+    ws = _ws(nws, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().tpspp_bn_train_stats(_ptr(z), N, C, HW, float(eps), -1.0 if momentum is None else float(momentum),
                                              _ptr(num_batches_tracked), _ptr(running_mean), _ptr(running_var), _ptr(mean),
@@ -2028,7 +2058,7 @@ def bn_bwd_reduce(dy, y, za, stats_a, zb=None, stats_b=None, relu=True):
     sdr = torch.empty((C,), device=dev, dtype=torch.float32)
     sxa = torch.empty((C,), device=dev, dtype=torch.float32)
     nws = bn_bwd_reduce_workspace_floats(N, C, HW)
-    ws = torch.empty((max(nws, 1),), device=dev, dtype=torch.float32)
+    ws = _ws(nws, dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().tpspp_bn_bwd_reduce(_ptr(dy), _ptr(y), int(bool(relu)), _ptr(za), _ptr(ma), _ptr(ra), _ptr(zb),
                                             _ptr(mb), _ptr(rb), N, C, HW, _ptr(sdr), _ptr(sxa), _ptr(sxb), _ptr(ws), nws,
@@ -2464,6 +2494,21 @@ def _attn_block_args(who, x, attn, drop_p):
     return x, biases, _attn_rate(who, drop_p)
 
 
+def _attn_proj_bwd(dp, x, nw, nb, mean, rstd, eps, w, need):
+    """Tail of an attention block's backward, the projection p = LayerNorm(x) W^T + b of the block's input, from dp (M, O):
+    need = (x, nw, nb, w, b) -> the five gradients in that order.  The LayerNorm output is recomputed for dW / db only."""
+    O, C = w.shape
+    dw = db = None
+    if need[3] or need[4]:
+        y, _, _ = plane_ln_fwd(x, nw, nb, eps)
+        dw, db = linear_bwd_weight(dp, y, _dense(x.numel() // C, C), O, C, need[3], need[4])
+        del y
+    dx = dnw = dnb = None
+    if any(need[:3]):
+        dx, dnw, dnb = _ln_bwd(linear_bwd_data(dp, w), x, nw, mean, rstd, need[:3])
+    return dx, dnw, dnb, dw, db
+
+
 class _AttnBlockFunction(torch.autograd.Function):
     """norm1 - q / k / v projections (one product) - attention - fc on x (N, T, C): the attention block of a TFEncoderLayer
     and, with key_mask and causal, the self-attention block of a TFDecoderLayer.  Saves x, the LayerNorm statistics, the
@@ -2495,27 +2540,16 @@ class _AttnBlockFunction(torch.autograd.Function):
         eps, drop_p, seed, offset, causal = ctx.cfg
         N, T, C = x.shape
         M, heads = N * T, C // 64
-        dev = x.device
+        res = [None] * 15
         ga = ga.float().contiguous()
-        dw_fc, db_fc = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[9], need[10])
-        dout = linear_bwd_data(ga, fcw, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
-        dqkv = torch.empty((M, 3 * C), device=dev, dtype=torch.float32)
+        res[9], res[10] = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[9], need[10])
+        dout = linear_bwd_data(ga, fcw)
+        dqkv = torch.empty((M, 3 * C), device=x.device, dtype=torch.float32)
         attn_train_bwd_ex(dout, qkv, 3 * C, qkv[:, C:], qkv[:, 2 * C:], 3 * C, out, lse, N, C, heads, T, T, valid_len, key_mask,
                           causal, drop_p, seed, offset, dqkv, 3 * C, dqkv[:, C:], dqkv[:, 2 * C:], 3 * C)
         del dout
-        y, _, _ = plane_ln_fwd(x, n1w, n1b, eps)
-        dw = db = None
-        if any(need[3:9]):
-            dw, db = linear_bwd_weight(dqkv, y, _dense(M, C), 3 * C, C, any(need[3:6]), any(need[6:9]))
-        del y
-        res = [None] * 15
-        if any(need[:3]):
-            dy = linear_bwd_data(dqkv, wqkv, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
-            dx = torch.empty_like(x) if need[0] else None
-            dw_ln, db_ln = plane_ln_bwd(dy, x, n1w, m1, r1, dx=dx, want_params=need[1] or need[2])
-            res[0], res[1], res[2] = dx, dw_ln if need[1] else None, db_ln if need[2] else None
+        *res[:3], dw, db = _attn_proj_bwd(dqkv, x, n1w, n1b, m1, r1, eps, wqkv, (*need[:3], any(need[3:6]), any(need[6:9])))
         res[3:6], res[6:9] = _unfuse(dw, need[3:6], C), _unfuse(db, need[6:9], C)
-        res[9], res[10] = dw_fc, db_fc
         return tuple(res)
 
 
@@ -2539,14 +2573,10 @@ class _FfnBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, nw, nb, w1, b1, w2, b2, eps):
-        N, T, C = x.shape
-        M = N * T
-        xn, m, r = plane_ln_fwd(x, nw, nb, eps)
-        g = linear_fwd(xn, _dense(M, C), w1, b1, epi=2)
-        f = linear_fwd(g, _dense(M, w1.shape[0]), w2, b2)
+        f, m, r = _mlp_fwd(x, nw, nb, eps, w1, b1, w2, b2)
         ctx.eps = eps
         ctx.save_for_backward(x, m, r, nw, nb, w1, b1, w2)
-        return f.view(N, T, C)
+        return f
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -2555,24 +2585,7 @@ class _FfnBlockFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         if not any(need[:7]):
             return (None,) * 8
-        N, T, C = x.shape
-        M, hid = N * T, w1.shape[0]
-        dev = x.device
-        gf = gf.float().contiguous()
-        xn, _, _ = plane_ln_fwd(x, nw, nb, ctx.eps)
-        u = linear_fwd(xn, _dense(M, C), w1, b1)
-        dw2, db2 = linear_bwd_weight(gf, u, _dense(M, hid), C, hid, need[5], need[6], x_gelu=True)
-        du = linear_bwd_data(gf, w2, torch.empty((M, hid), device=dev, dtype=torch.float32), _dense(M, hid))
-        act_bwd(ACT_GELU, du, u, out=du)
-        del u
-        dw1, db1 = linear_bwd_weight(du, xn, _dense(M, C), hid, C, need[3], need[4])
-        del xn
-        dx = dw_ln = db_ln = None
-        if any(need[:3]):
-            dxn = linear_bwd_data(du, w1, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
-            dx = torch.empty_like(x) if need[0] else None
-            dw_ln, db_ln = plane_ln_bwd(dxn, x, nw, m, r, dx=dx, want_params=need[1] or need[2])
-        return dx, dw_ln if need[1] else None, db_ln if need[2] else None, dw1, db1, dw2, db2, None
+        return (*_mlp_bwd(gf.float().contiguous(), x, nw, nb, m, r, ctx.eps, w1, b1, w2, need[:7]), None)
 
 
 def ffn_block_autograd(x, mlp, norm):
@@ -2598,9 +2611,7 @@ class _TokenLnFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         if not any(need[:3]):
             return (None,) * 4
-        dx = torch.empty_like(x) if need[0] else None
-        dw, db = plane_ln_bwd(gy.float().contiguous(), x, w, m, r, dx=dx, want_params=need[1] or need[2])
-        return dx, dw if need[1] else None, db if need[2] else None, None
+        return (*_ln_bwd(gy.float().contiguous(), x, w, m, r, need[:3]), None)
 
 
 def token_ln_autograd(x, ln):
@@ -2614,7 +2625,6 @@ def encoder_layer_autograd(x, lyr, valid_len=None, drop_p=0.0, seed=0, offset=0)
     matrix product, softmax, LayerNorm and GELU on HIP kernels; the residual additions and the two element-wise dropouts
     (after fc and after w_2, rate drop_p, PyTorch's generator) are PyTorch element-wise ops.  drop_p also drives the
     dropout on the attention probabilities, seeded by (seed, offset)."""
-    import torch.nn.functional as Fn
     a = attn_block_autograd(x, lyr.attn, lyr.norm1, valid_len, drop_p, seed, offset)
     x = x + Fn.dropout(a, drop_p, drop_p > 0)
     f = ffn_block_autograd(x, lyr.mlp, lyr.norm2)
@@ -2660,32 +2670,22 @@ class _CrossAttnBlockFunction(torch.autograd.Function):
         N, L, C = x.shape
         T, heads = enc.shape[1], C // 64
         M, MT = N * L, N * T
-        dev = x.device
-        ga = ga.float().contiguous()
         res = [None] * 14
+        ga = ga.float().contiguous()
         res[10], res[11] = linear_bwd_weight(ga, out, _dense(M, C), C, C, need[10], need[11])
-        dout = linear_bwd_data(ga, fcw, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
-        dqp = torch.empty((M, C), device=dev, dtype=torch.float32)
-        dkv = torch.empty((MT, 2 * C), device=dev, dtype=torch.float32)
+        dout = linear_bwd_data(ga, fcw)
+        dqp = torch.empty((M, C), device=x.device, dtype=torch.float32)
+        dkv = torch.empty((MT, 2 * C), device=x.device, dtype=torch.float32)
         attn_train_bwd_ex(dout, qp, C, kv, kv[:, C:], 2 * C, out, lse, N, C, heads, L, T, valid_len, None, False, drop_p, seed,
                           offset, dqp, C, dkv, dkv[:, C:], 2 * C)
         del dout
-        if need[4] or need[7]:
-            y, _, _ = plane_ln_fwd(x, nw, nb, eps)
-            dwq, dbq = linear_bwd_weight(dqp, y, _dense(M, C), C, C, need[4], need[7])
-            del y
-            res[4], res[7] = dwq, dbq
         if any(need[5:7]) or any(need[8:10]):
             dw, db = linear_bwd_weight(dkv, enc, _dense(MT, C), 2 * C, C, any(need[5:7]), any(need[8:10]))
             res[5:7], res[8:10] = _unfuse(dw, need[5:7], C), _unfuse(db, need[8:10], C)
-        if any((need[0], need[2], need[3])):
-            dy = linear_bwd_data(dqp, wq, torch.empty((M, C), device=dev, dtype=torch.float32), _dense(M, C))
-            dx = torch.empty_like(x) if need[0] else None
-            dw_ln, db_ln = plane_ln_bwd(dy, x, nw, m, r, dx=dx, want_params=need[2] or need[3])
-            res[0], res[2], res[3] = dx, dw_ln if need[2] else None, db_ln if need[3] else None
+        res[0], res[2], res[3], res[4], res[7] = _attn_proj_bwd(dqp, x, nw, nb, m, r, eps, wq,
+                                                                (need[0], need[2], need[3], need[4], need[7]))
         if need[1]:
-            res[1] = linear_bwd_data(dkv, wkv, torch.empty((MT, C), device=dev, dtype=torch.float32),
-                                     _dense(MT, C)).view(enc.shape)
+            res[1] = linear_bwd_data(dkv, wkv).view(enc.shape)
         return tuple(res)
 
 
@@ -2739,7 +2739,7 @@ def embed_bwd(dx, tok, num_classes, padding_idx):
         return torch.zeros((num_classes, C), device=dx.device, dtype=torch.float32)
     dw = torch.empty((num_classes, C), device=dx.device, dtype=torch.float32)
     n = embed_bwd_workspace_floats(M, num_classes, C)
-    ws = torch.empty((n,), device=dx.device, dtype=torch.float32)
+    ws = _ws(n, dx.device)
     _lib.check(_lib.lib().tpspp_embed_bwd(_ptr(dx), _ptr(tok), M, C, num_classes, -1 if padding_idx is None else padding_idx,
                                           _ptr(dw), _ptr(ws), n, _stream(dx)), "tpspp_embed_bwd")
     return dw
@@ -2875,7 +2875,7 @@ class _LinearFunction(torch.autograd.Function):
         M = x.numel() // K
         gy = gy.float().contiguous().view(M, O)
         dw, db = linear_bwd_weight(gy, x, _dense(M, K), O, K, need[1], need[2])
-        dx = linear_bwd_data(gy, w, torch.empty_like(x), _dense(M, K)) if need[0] else None
+        dx = linear_bwd_data(gy, w).view(x.shape) if need[0] else None
         return dx, dw, db
 
 
@@ -2894,7 +2894,6 @@ def decoder_layer_autograd(x, out_enc, lyr, key_mask=None, valid_len=None, drop_
     three residual additions and the three element-wise dropouts (rate drop_p, PyTorch's generator) are PyTorch ops.
     `offset` is the layer's index: the dropout on the attention probabilities uses (seed, 2 * offset) in the
     self-attention and (seed, 2 * offset + 1) in the cross-attention."""
-    import torch.nn.functional as Fn
     a = attn_block_autograd(x, lyr.self_attn, lyr.norm1, None, drop_p, seed, 2 * offset, key_mask=key_mask, causal=True)
     x = x + Fn.dropout(a, drop_p, drop_p > 0)
     a = cross_attn_block_autograd(x, out_enc, lyr.enc_attn, lyr.norm2, valid_len, drop_p, seed, 2 * offset + 1)
