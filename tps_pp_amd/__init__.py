@@ -15,6 +15,7 @@ from .nrtr_modality_transformer import NRTRModalityTransform  # noqa: F401
 from .nrtr_head import (NRTREncoder, NRTRDecoder, AttnConvertor, BaseConvertor,  # noqa: F401
                         EncodeDecodeRecognizer, NRTR, TFEncoderLayer, TFDecoderLayer, MultiHeadAttention,
                         PositionwiseFeedForward, PositionalEncoding)
+from .optim import Adam, AdamW, build_optimizer  # noqa: F401
 
 from .ocr_transforms import PIPELINES, ResizeOCR, NormalizeOCR, OCRBatchPreprocessor  # noqa: F401
 
@@ -24,4 +25,4 @@ __all__ = ["PIPELINES", "ResizeOCR", "NormalizeOCR", "OCRBatchPreprocessor",
            "TPS_PP", "Attention_Enhanced_TPS", "ResNetABI_v2_large", "BasicBlock",
            "NRTRModalityTransform", "ENCODERS", "DECODERS", "CONVERTORS", "DETECTORS", "build_encoder",
            "build_decoder", "build_convertor", "build_detector", "NRTREncoder", "NRTRDecoder", "AttnConvertor",
-           "BaseConvertor", "EncodeDecodeRecognizer", "NRTR"]
+           "BaseConvertor", "EncodeDecodeRecognizer", "NRTR", "Adam", "AdamW", "build_optimizer"]

@@ -1,4 +1,5 @@
-"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h, include/tpspp_train_dec.h).
+"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h, include/tpspp_train_dec.h,
+include/tpspp_train_opt.h).
 
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
@@ -123,6 +124,15 @@ _DEC_TRAIN_SIGNATURES = {
     "tpspp_seq_ce_bwd": ([_f, _f, _l, _l, _l, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f], _i),
 }
 
+# include/tpspp_train_opt.h: multi-tensor Adam / AdamW, the gradient norm with its clipping coefficient, the zeroing of all
+# gradients.  A fourth table: the other three stay as their tests pin them.
+_OPT_TRAIN_SIGNATURES = {
+    "tpspp_mt_adam": ([_f, _f, _i, _f, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _f, _f], _i),
+    "tpspp_mt_sumsq": ([_f, _i, _f, _i, _i, _i, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_mt_norm_finish": ([_f, _i, ctypes.c_float, _f, _f], _i),
+    "tpspp_mt_zero": ([_f, _i, _f, _i, _i, _i, _f], _i),
+}
+
 _lib = None
 
 
@@ -145,6 +155,11 @@ def dec_train_symbols():
     return sorted(_DEC_TRAIN_SIGNATURES)
 
 
+def opt_train_symbols():
+    """Names include/tpspp_train_opt.h declares (kept in sync by tests/test_optim_host.py)."""
+    return sorted(_OPT_TRAIN_SIGNATURES)
+
+
 def lib():
     """The loaded library; raises if it is absent (build it: `python -m tps_pp_amd.build`)."""
     global _lib
@@ -155,7 +170,7 @@ def lib():
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + \
-                list(_DEC_TRAIN_SIGNATURES.items()):
+                list(_DEC_TRAIN_SIGNATURES.items()) + list(_OPT_TRAIN_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
             fn.argtypes = argtypes
             fn.restype = restype

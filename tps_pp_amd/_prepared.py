@@ -7,7 +7,10 @@ replaced parameter), its device did, or the arithmetic configuration the caller 
 
 Blind spot: an edit through `param.data` bumps the version counter of a different tensor and is NOT seen.  After one,
 call `invalidate_prepared(module)` (`TPS_PP.invalidate_train_cache()` / `ResNetABI_v2_large.invalidate_train_cache()`
-do); otherwise a forward would keep using the stale layout.
+do); otherwise a forward would keep using the stale layout.  A kernel that writes parameters through raw pointers is the
+same blind spot; the one that exists, the multi-tensor Adam of `optim.py`, closes it itself: after its launch `step()`
+calls `torch.autograd.graph.increment_version` on every parameter it updated, so the key above moves and the next
+forward rebuilds (tests/test_gpu_optim.py shows it).
 
 All slots of a module live in one private dict in the module's `__dict__`: never a registered buffer or submodule, so
 `state_dict()`, `parameters()` and `buffers()` do not see them.

@@ -788,6 +788,44 @@ class EncodeDecodeRecognizer(nn.Module):
             return self.aug_test(imgs, img_metas, **kwargs)
         return self.simple_test(imgs, img_metas, **kwargs)
 
+    def _parse_losses(self, losses):
+        """`BaseRecognizer._parse_losses` (recognizer/base.py:96-129): every entry of the loss dict becomes a scalar (a
+        tensor its mean, a list of tensors the sum of their means; anything else raises TypeError), the entries whose
+        name contains 'loss' add up to the tensor to back-propagate, and `log_vars` holds every scalar and the total
+        under 'loss' as Python floats -- averaged over the ranks first when a process group is initialised.  The
+        `.item()` calls are the reference's own host synchronisation; it is confined to logging."""
+        import torch.distributed as dist
+        from collections import OrderedDict
+        log_vars = OrderedDict()
+        for name, value in losses.items():
+            if isinstance(value, torch.Tensor):
+                log_vars[name] = value.mean()
+            elif isinstance(value, list):
+                log_vars[name] = sum(v.mean() for v in value)
+            else:
+                raise TypeError(f"{name} is not a tensor or list of tensors")
+        loss = sum(v for k, v in log_vars.items() if "loss" in k)
+        log_vars["loss"] = loss
+        reduce = dist.is_available() and dist.is_initialized()
+        for name, value in log_vars.items():
+            if reduce:
+                value = value.data.clone()
+                dist.all_reduce(value.div_(dist.get_world_size()))
+            log_vars[name] = value.item()
+        return loss, log_vars
+
+    def train_step(self, data, optimizer):
+        """`BaseRecognizer.train_step` (recognizer/base.py:131-164): `self(**data)` and `_parse_losses`; back-propagation
+        and the optimiser step are the runner's (`optimizer` is unused here, as in the reference).  Returns
+        dict(loss, log_vars, num_samples)."""
+        loss, log_vars = self._parse_losses(self(**data))
+        return dict(loss=loss, log_vars=log_vars, num_samples=len(data["img_metas"]))
+
+    def val_step(self, data, optimizer=None):
+        """`BaseRecognizer.val_step` (recognizer/base.py:166-179): the same computation during validation epochs."""
+        loss, log_vars = self._parse_losses(self(**data))
+        return dict(loss=loss, log_vars=log_vars, num_samples=len(data["img_metas"]))
+
     def forward(self, img, img_metas, return_loss=True, **kwargs):
         """`BaseRecognizer.forward` (recognizer/base.py:74-92)."""
         if return_loss:
