@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 10  /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 11  /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
                                5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
@@ -46,7 +46,9 @@ extern "C" {
                                   tpspp_attn_train_bwd, tpspp_attn_dropout_mask;
                                10: the decoder's and the loss's training kernels, declared in tpspp_train_dec.h:
                                   tpspp_attn_train_fwd_ex / _bwd_ex, tpspp_embed_pos_fwd, tpspp_embed_bwd (+ _workspace_floats),
-                                  tpspp_seq_ce_fwd / _bwd */
+                                  tpspp_seq_ce_fwd / _bwd;
+                               11: the train pipeline's augmentation kernel, declared in tpspp_augment.h:
+                                  tpspp_augment_normalize_fwd */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */

@@ -17,9 +17,12 @@ from .nrtr_head import (NRTREncoder, NRTRDecoder, AttnConvertor, BaseConvertor, 
                         PositionwiseFeedForward, PositionalEncoding)
 from .optim import Adam, AdamW, build_optimizer  # noqa: F401
 
-from .ocr_transforms import PIPELINES, ResizeOCR, NormalizeOCR, OCRBatchPreprocessor  # noqa: F401
+from .ocr_transforms import (PIPELINES, ResizeOCR, NormalizeOCR, OCRBatchPreprocessor,  # noqa: F401
+                             OCRTrainBatchPreprocessor, RandomWrapper, OneOfWrapper, TorchVisionWrapper,
+                             RandomRotateTextDet)
 
-__all__ = ["PIPELINES", "ResizeOCR", "NormalizeOCR", "OCRBatchPreprocessor",
+__all__ = ["PIPELINES", "ResizeOCR", "NormalizeOCR", "OCRBatchPreprocessor", "OCRTrainBatchPreprocessor",
+           "RandomWrapper", "OneOfWrapper", "TorchVisionWrapper", "RandomRotateTextDet",
            "BACKBONES", "PREPROCESSOR", "build_backbone", "build_preprocessor",
            "register_into_mmocr", "TPSPreprocessor", "LocalizationNetwork", "GridGenerator",
            "TPS_PP", "Attention_Enhanced_TPS", "ResNetABI_v2_large", "BasicBlock",

@@ -1,5 +1,5 @@
 """ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h, include/tpspp_train_dec.h,
-include/tpspp_train_opt.h).
+include/tpspp_train_opt.h, include/tpspp_augment.h).
 
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
@@ -9,7 +9,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
@@ -133,6 +133,12 @@ _OPT_TRAIN_SIGNATURES = {
     "tpspp_mt_zero": ([_f, _i, _f, _i, _i, _i, _f], _i),
 }
 
+# include/tpspp_augment.h: the train pipeline's resize + augmentation + normalisation kernel.  A fifth table: the other four
+# stay as their tests pin them.
+_AUGMENT_SIGNATURES = {
+    "tpspp_augment_normalize_fwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _f], _i),
+}
+
 _lib = None
 
 
@@ -160,6 +166,11 @@ def opt_train_symbols():
     return sorted(_OPT_TRAIN_SIGNATURES)
 
 
+def augment_symbols():
+    """Names include/tpspp_augment.h declares (kept in sync by tests/test_augment_host.py)."""
+    return sorted(_AUGMENT_SIGNATURES)
+
+
 def lib():
     """The loaded library; raises if it is absent (build it: `python -m tps_pp_amd.build`)."""
     global _lib
@@ -170,7 +181,8 @@ def lib():
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
         for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + \
-                list(_DEC_TRAIN_SIGNATURES.items()) + list(_OPT_TRAIN_SIGNATURES.items()):
+                list(_DEC_TRAIN_SIGNATURES.items()) + list(_OPT_TRAIN_SIGNATURES.items()) + \
+                list(_AUGMENT_SIGNATURES.items()):
             fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
             fn.argtypes = argtypes
             fn.restype = restype

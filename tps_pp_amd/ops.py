@@ -1426,6 +1426,44 @@ def resize_normalize(packed, offsets, src_h, src_w, resize_w, lut, pad_value, N,
     return out
 
 
+# op codes of include/tpspp_augment.h
+AUG_END, AUG_AFFINE_NEAREST_PIL, AUG_PERSPECTIVE_BILINEAR_PIL, AUG_AFFINE_NEAREST_CV2 = 0, 1, 2, 3
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = 4, 5, 6, 7
+AUG_MAX_OPS, AUG_OP_PARAMS = 8, 8
+
+
+def augment_normalize(packed, offsets, src_h, src_w, resize_w, lut, pad_value, N, C, H, W, op_codes, op_params,
+                      interpolation=RESIZE_CV2, bgr=True):
+    """`tpspp_augment_normalize_fwd`: `resize_normalize` with a list of augmentation ops per image between the resize and
+    the normalisation (crnn_pp_pipeline.py:2-84; include/tpspp_augment.h has the arithmetic of each code).
+    `op_codes` (N, max_ops) int32 and `op_params` (N, max_ops, 8) float64 on the GPU, max_ops 1..8, code 0 ends a list;
+    `bgr`: channel 0 is blue, as mmcv.imread loads.  Codes 1, 2, 4..7 are Pillow's arithmetic (pinned), code 3 OpenCV's
+    (unpinned).  With every list empty the result has the bits of `resize_normalize`."""
+    if interpolation not in (RESIZE_CV2, RESIZE_PILLOW):
+        raise ValueError("augment_normalize: interpolation must be RESIZE_CV2 or RESIZE_PILLOW")
+    for name, t, dt in (("packed", packed, torch.uint8), ("offsets", offsets, torch.int64), ("src_h", src_h, torch.int32),
+                        ("src_w", src_w, torch.int32), ("resize_w", resize_w, torch.int32), ("lut", lut, torch.float32),
+                        ("op_codes", op_codes, torch.int32), ("op_params", op_params, torch.float64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.TpsppError(f"augment_normalize: {name} must be a GPU tensor (no CPU fallback)")
+        if t.dtype != dt or not t.is_contiguous():
+            raise TypeError(f"augment_normalize: {name} must be a contiguous {dt} tensor")
+    if offsets.numel() != N or src_h.numel() != N or src_w.numel() != N or resize_w.numel() != N or \
+            tuple(lut.shape) != (C, 256):
+        raise ValueError("augment_normalize: per-image arrays need N entries, lut must be (C, 256)")
+    if op_codes.dim() != 2 or op_codes.shape[0] != N or not 1 <= op_codes.shape[1] <= AUG_MAX_OPS or \
+            tuple(op_params.shape) != (N, op_codes.shape[1], AUG_OP_PARAMS):
+        raise ValueError(f"augment_normalize: op_codes must be (N, 1..{AUG_MAX_OPS}), op_params (N, max_ops, {AUG_OP_PARAMS})")
+    out = torch.empty((N, C, H, W), device=packed.device, dtype=torch.float32)
+    with torch.cuda.device(packed.device):
+        rc = _lib.lib().tpspp_augment_normalize_fwd(_ptr(packed), _ptr(offsets), _ptr(src_h), _ptr(src_w), _ptr(resize_w),
+                                                    _ptr(lut), int(pad_value), int(N), int(C), int(H), int(W), _ptr(out),
+                                                    int(interpolation), _ptr(op_codes), _ptr(op_params),
+                                                    int(op_codes.shape[1]), int(bool(bgr)), _stream(packed))
+    _lib.check(rc, "tpspp_augment_normalize_fwd")
+    return out
+
+
 # ---- backward of the fused warp (SURVEY.md section 8f, row F2) ------------------------------------------------
 def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None,
                   g_out1=None, P_hat_t=None, need_in0=True, need_in1=True, need_score=True, fixed_point=False,
