@@ -137,7 +137,7 @@ def main():
     variants = {"(a) resize_normalize": run_a}
     if a.parent_lib:
         other = ctypes.CDLL(os.path.abspath(a.parent_lib))
-        other.tpspp_resize_normalize_fwd.argtypes = _lib._SIGNATURES["tpspp_resize_normalize_fwd"][0]
+        other.tpspp_resize_normalize_fwd.argtypes = _lib._SIGNATURES["tpspp.h"]["tpspp_resize_normalize_fwd"][0]
         other.tpspp_resize_normalize_fwd.restype = ctypes.c_int
         run_p, out_p = resize_with(other)
         variants[f"(a) resize_normalize, {os.path.basename(os.path.dirname(os.path.abspath(a.parent_lib)))}"] = run_p

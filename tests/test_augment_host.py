@@ -14,15 +14,11 @@ import numpy as np
 import pytest
 
 import augment_ref as R
-from test_attn_train_host import declared
 from tps_pp_amd import (OCRTrainBatchPreprocessor, OneOfWrapper, RandomRotateTextDet, RandomWrapper, TorchVisionWrapper,
                         _lib, build, ocr_transforms as T, ops)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tpspp_augment.h")
-OTHER_HEADERS = [os.path.join(ROOT, "include", n) for n in ("tpspp.h", "tpspp_train_attn.h", "tpspp_train_dec.h",
-                                                            "tpspp_train_opt.h")]
-NAMES = {"tpspp_augment_normalize_fwd"}
 SKIP = ("PyramidRescale", "Albu")
 
 
@@ -87,29 +83,13 @@ def test_hsv_round_trip_equals_pillow_on_all_triples():
 
 
 # ---- the C boundary ---------------------------------------------------------------------------------------------------------
-def test_header_binding_and_shared_object_agree(lib):
-    decl = declared(HEADER)
-    assert set(decl) == NAMES == set(_lib.augment_symbols())
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name, nargs in decl.items():
-        assert hasattr(raw, name), f"{name} missing from libtpspp_hip.so"
-        fn = getattr(lib, name)
-        assert len(fn.argtypes) == nargs == 18, f"{name}: header has {nargs} parameters, binding {len(fn.argtypes)}"
-        assert fn.restype is ctypes.c_int
+def test_header_names_what_it_replaces_and_its_codes_are_the_python_ones():
     text = open(HEADER).read()
     assert "replaces:" in text and "UNPINNED" in text and "crnn_pp_pipeline.py:2-84" in text
     for k, code in (("END", 0), ("AFFINE_NEAREST_PIL", 1), ("PERSPECTIVE_BILINEAR_PIL", 2), ("AFFINE_NEAREST_CV2", 3),
                     ("BRIGHTNESS", 4), ("CONTRAST", 5), ("SATURATION", 6), ("HUE", 7)):
         assert getattr(ops, "AUG_" + k) == getattr(R, k) == code
         assert any(line.split()[:3] == ["#define", "TPSPP_AUG_" + k, str(code)] for line in text.splitlines()), k
-
-
-def test_new_name_stays_out_of_the_other_headers_and_tables(lib):
-    for h in OTHER_HEADERS:
-        assert not NAMES & set(declared(h)), h
-    assert not NAMES & (set(_lib.exported_symbols()) | set(_lib.train_symbols()) | set(_lib.dec_train_symbols()) |
-                        set(_lib.opt_train_symbols()))
-    assert lib.tpspp_abi_version() == _lib.ABI_VERSION >= 11
 
 
 def test_argument_errors_are_codes_with_messages_and_launch_nothing(lib):

@@ -11,13 +11,10 @@ import pytest
 import torch
 
 import test_gpu_optim as TG
-from test_attn_train_host import declared
 from tps_pp_amd import EncodeDecodeRecognizer, _lib, build, optim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "tpspp_train_opt.h")
-OTHER_HEADERS = [os.path.join(ROOT, "include", n) for n in ("tpspp.h", "tpspp_train_attn.h", "tpspp_train_dec.h")]
-NAMES = {"tpspp_mt_adam", "tpspp_mt_sumsq", "tpspp_mt_norm_finish", "tpspp_mt_zero"}
 
 
 @pytest.fixture(scope="module")
@@ -26,26 +23,11 @@ def lib():
     return _lib.lib()
 
 
-def test_header_binding_and_shared_object_agree(lib):
-    decl = declared(HEADER)
-    assert set(decl) == NAMES == set(_lib.opt_train_symbols())
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name, nargs in decl.items():
-        assert hasattr(raw, name), f"{name} missing from libtpspp_hip.so"
-        fn = getattr(lib, name)
-        assert len(fn.argtypes) == nargs, f"{name}: header has {nargs} parameters, binding {len(fn.argtypes)}"
-        assert fn.restype is ctypes.c_int
+def test_header_names_what_it_replaces():
     text = open(HEADER).read()
     assert "replaces:" in text
     for ref in ("torch.optim.Adam", "AdamW", "clip_grad_norm_", "OptimizerHook", "fused"):
         assert ref in text, ref
-
-
-def test_new_names_stay_out_of_the_other_headers_and_tables(lib):
-    for h in OTHER_HEADERS:
-        assert not NAMES & set(declared(h)), h
-    assert not NAMES & (set(_lib.exported_symbols()) | set(_lib.train_symbols()) | set(_lib.dec_train_symbols()))
-    assert lib.tpspp_abi_version() == _lib.ABI_VERSION
 
 
 def test_argument_errors_are_codes_with_messages_and_launch_nothing(lib):

@@ -1,5 +1,7 @@
-"""ctypes binding of libtpspp_hip.so (C ABI: include/tpspp.h, include/tpspp_train_attn.h, include/tpspp_train_dec.h,
-include/tpspp_train_opt.h, include/tpspp_augment.h).
+"""ctypes binding of libtpspp_hip.so.  The C ABI is the headers under include/; `_SIGNATURES` maps each header's file name
+to the `{name: (argtypes, restype)}` of the functions it declares, `headers()` lists them and `symbols(header)` gives one
+header's names (tests/test_capi_symbols.py holds every header, this table and the shared object to each other).  A new
+entry point goes under the header that declares it; a new header is a new key.
 
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
@@ -14,8 +16,10 @@ ABI_VERSION = 11
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int
 _l = ctypes.c_longlong
+_u64 = ctypes.c_ulonglong
 
-_SIGNATURES = {
+# header file name -> {function: (argtypes, restype)}; the entries keep a flat indent so that a signature is one short line
+_SIGNATURES = {"tpspp.h": {
     "tpspp_abi_version": ([], _i),
     "tpspp_last_error": ([], ctypes.c_char_p),
     "tpspp_solve_T": ([_f, _f, _i, _i, _f, _f], _i),
@@ -99,21 +103,12 @@ _SIGNATURES = {
                                 _f, ctypes.c_size_t, _f, _f, _f, _i, _f], _i),
     "tpspp_blocked_to_nchw_bf16": ([_f, _i, _i, _i, _f, _f], _i),
     "tpspp_attn_tensor2idx_fwd": ([_f, _i, _i, _i, _i, _i, _f, _f, _f], _i),
-}
-
-# include/tpspp_train_attn.h: the encoder's attention training kernels.  A table of its own: `exported_symbols()` is the
-# list of include/tpspp.h alone.
-_u64 = ctypes.c_ulonglong
-_TRAIN_SIGNATURES = {
+}, "tpspp_train_attn.h": {      # the encoder's attention training kernels
     "tpspp_attn_train_fwd": ([_f, _f, _f, _l, _i, _i, _i, _i, _i, _f, ctypes.c_float, _u64, _u64, _f, _f, _f], _i),
     "tpspp_attn_train_bwd": ([_f, _f, _f, _f, _l, _f, _f, _i, _i, _i, _i, _i, _f, ctypes.c_float, _u64, _u64, _f, _f, _f, _l,
                               _f], _i),
     "tpspp_attn_dropout_mask": ([_i, _i, _i, _i, ctypes.c_float, _u64, _u64, _f, _f], _i),
-}
-
-# include/tpspp_train_dec.h: the decoder's attention, its embedding and the sequence cross-entropy.  A table of its own
-# again: tests pin the exact name sets of the other two.
-_DEC_TRAIN_SIGNATURES = {
+}, "tpspp_train_dec.h": {       # the decoder's attention, its embedding and the sequence cross-entropy
     "tpspp_attn_train_fwd_ex": ([_f, _l, _f, _f, _l, _i, _i, _i, _i, _i, _f, _f, _i, ctypes.c_float, _u64, _u64, _f, _f, _f], _i),
     "tpspp_attn_train_bwd_ex": ([_f, _f, _l, _f, _f, _l, _f, _f, _i, _i, _i, _i, _i, _f, _f, _i, ctypes.c_float, _u64, _u64,
                                  _f, _l, _f, _f, _l, _f], _i),
@@ -122,22 +117,14 @@ _DEC_TRAIN_SIGNATURES = {
     "tpspp_embed_bwd": ([_f, _f, _l, _i, _i, _i, _f, _f, ctypes.c_size_t, _f], _i),
     "tpspp_seq_ce_fwd": ([_f, _l, _l, _l, _f, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f], _i),
     "tpspp_seq_ce_bwd": ([_f, _f, _l, _l, _l, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _f], _i),
-}
-
-# include/tpspp_train_opt.h: multi-tensor Adam / AdamW, the gradient norm with its clipping coefficient, the zeroing of all
-# gradients.  A fourth table: the other three stay as their tests pin them.
-_OPT_TRAIN_SIGNATURES = {
+}, "tpspp_train_opt.h": {       # multi-tensor Adam / AdamW, the gradient norm and its clipping coefficient, zeroing
     "tpspp_mt_adam": ([_f, _f, _i, _f, _i, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i, _f, _f], _i),
     "tpspp_mt_sumsq": ([_f, _i, _f, _i, _i, _i, _f, ctypes.c_size_t, _f], _i),
     "tpspp_mt_norm_finish": ([_f, _i, ctypes.c_float, _f, _f], _i),
     "tpspp_mt_zero": ([_f, _i, _f, _i, _i, _i, _f], _i),
-}
-
-# include/tpspp_augment.h: the train pipeline's resize + augmentation + normalisation kernel.  A fifth table: the other four
-# stay as their tests pin them.
-_AUGMENT_SIGNATURES = {
+}, "tpspp_augment.h": {         # the train pipeline's resize + augmentation + normalisation kernel
     "tpspp_augment_normalize_fwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _f], _i),
-}
+}}
 
 _lib = None
 
@@ -146,29 +133,14 @@ class TpsppError(RuntimeError):
     pass
 
 
-def exported_symbols():
-    """Names include/tpspp.h declares (kept in sync by tests/test_capi_symbols.py)."""
-    return sorted(_SIGNATURES)
+def headers():
+    """File names of the headers under include/ that declare the C ABI."""
+    return list(_SIGNATURES)
 
 
-def train_symbols():
-    """Names include/tpspp_train_attn.h declares (kept in sync by tests/test_attn_train_host.py)."""
-    return sorted(_TRAIN_SIGNATURES)
-
-
-def dec_train_symbols():
-    """Names include/tpspp_train_dec.h declares (kept in sync by tests/test_dec_train_host.py)."""
-    return sorted(_DEC_TRAIN_SIGNATURES)
-
-
-def opt_train_symbols():
-    """Names include/tpspp_train_opt.h declares (kept in sync by tests/test_optim_host.py)."""
-    return sorted(_OPT_TRAIN_SIGNATURES)
-
-
-def augment_symbols():
-    """Names include/tpspp_augment.h declares (kept in sync by tests/test_augment_host.py)."""
-    return sorted(_AUGMENT_SIGNATURES)
+def symbols(header):
+    """Names include/<header> declares (kept in sync by tests/test_capi_symbols.py)."""
+    return sorted(_SIGNATURES[header])
 
 
 def lib():
@@ -180,12 +152,11 @@ def lib():
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (argtypes, restype) in list(_SIGNATURES.items()) + list(_TRAIN_SIGNATURES.items()) + \
-                list(_DEC_TRAIN_SIGNATURES.items()) + list(_OPT_TRAIN_SIGNATURES.items()) + \
-                list(_AUGMENT_SIGNATURES.items()):
-            fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
-            fn.argtypes = argtypes
-            fn.restype = restype
+        for table in _SIGNATURES.values():
+            for name, (argtypes, restype) in table.items():
+                fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
+                fn.argtypes = argtypes
+                fn.restype = restype
         got = L.tpspp_abi_version()
         if got != ABI_VERSION:
             raise TpsppError(f"libtpspp_hip.so ABI {got} != binding ABI {ABI_VERSION}: rebuild")

@@ -25,10 +25,13 @@
 // rows 4g .. 4g + 3 of one column -- exactly the four consecutive rows that one accumulator quad of the MFMA layout
 // holds, so a lane makes 4 Philox calls for its 16 elements of a block.  Bitwise reproducible: no atomics, fixed orders.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 #include "tpspp_train_attn.h"
 #include "tpspp_train_dec.h"
 
 #include <math.h>
+
+using namespace tpspp_dev;
 
 namespace {
 
@@ -38,7 +41,6 @@ constexpr int LD = BT + 1;        // LDS row pitch in words
 constexpr int kMaxT = 256;
 constexpr float kScale = 0.125f;  // 1 / sqrt(64): a power of two, so scaling q or scaling q k^T is the same number
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float Tile[BT][LD];
 
 struct AttnParams {

@@ -23,11 +23,13 @@
 // backbones/resnet_v2_large.py:131-135 and layers/conv_layer.py:12-33 (BatchNorm folded on the host).
 // Bound: MFMA (fp32 matrix rate = 157 TFLOP/s peak).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 #include <type_traits>
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int BM = 128;       // output pixels per workgroup
 constexpr int BN = 64;        // output channels per workgroup
 constexpr int kThreads = 256;
@@ -35,8 +37,6 @@ constexpr int kThreads = 256;
 #define KC3 4
 #endif
 constexpr int kKC3 = KC3;       // input channels per K-chunk of the 3x3 kernels (layout of weight_tiled)
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvSrc {
     const float* p;

@@ -99,7 +99,7 @@ conv1x1_blk_kernel(const BParams P, int ntiles, int cg_total, int cg0)
         unsigned short* const ob = reinterpret_cast<unsigned short*>(P.out) + (((size_t)n * cg_total + cg0) * HW + px) * 8;
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
-            tpspp_u32x2 pk[4];
+            u32x2 pk[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float v[4];
@@ -108,14 +108,14 @@ conv1x1_blk_kernel(const BParams P, int ntiles, int cg_total, int cg0)
                     v[e] = acc[t][4 * g + e] + sBias[32 * t + 8 * g + 4 * half + e];
                     if (relu1) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
                 }
-                pk[g][0] = pack2_bf16(v[0], v[1]); pk[g][1] = pack2_bf16(v[2], v[3]);
+                pk[g][0] = pack_bf16(v[0], v[1]); pk[g][1] = pack_bf16(v[2], v[3]);
             }
             // the two half-wavefronts hold the two halves of a 16-byte unit: after the swap the lower one owns the unit of
             // channel group 4 t + g, the upper one that of 4 t + g + 1
 #pragma unroll
             for (int g = 0; g < 4; g += 2) {
-                const tpspp_u32x2 d0 = __builtin_amdgcn_permlane32_swap(pk[g][0], pk[g + 1][0], false, false);
-                const tpspp_u32x2 d1 = __builtin_amdgcn_permlane32_swap(pk[g][1], pk[g + 1][1], false, false);
+                const u32x2 d0 = __builtin_amdgcn_permlane32_swap(pk[g][0], pk[g + 1][0], false, false);
+                const u32x2 d1 = __builtin_amdgcn_permlane32_swap(pk[g][1], pk[g + 1][1], false, false);
                 u32x4 unit; unit[0] = d0[0]; unit[1] = d1[0]; unit[2] = d0[1]; unit[3] = d1[1];
                 *reinterpret_cast<u32x4*>(ob + (size_t)(4 * t + g + half) * HW * 8) = unit;
             }

@@ -239,7 +239,7 @@ conv3_wide_kernel(const BParams P)
     // per lane in flight together: one memory latency per workgroup instead of one per (fragment, channel half) -- the
     // epilogue was 12 % of the 256 -> 256 layer with the loads next to their use)
     constexpr bool RES = (EPI & 1) != 0, F32OUT = (EPI & 2) != 0;
-    tpspp_u32x2 rres[RES ? 4 : 1][2][4];
+    u32x2 rres[RES ? 4 : 1][2][4];
     int pixo[4], nimg[4];
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
@@ -254,7 +254,7 @@ conv3_wide_kernel(const BParams P)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const size_t bunit = (((size_t)(valid ? nimg[f] : 0) * CGo + ctile * 8 + 4 * h2 + g) * HW + pixo[f]) * 8 + 4 * half;
-                    rres[f][h2][g] = *reinterpret_cast<const tpspp_u32x2*>(reinterpret_cast<const unsigned short*>(P.res) + bunit);
+                    rres[f][h2][g] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(P.res) + bunit);
                 }
         }
     }
@@ -264,13 +264,13 @@ conv3_wide_kernel(const BParams P)
         const bool valid = n < P.N;
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
-            tpspp_u32x2 bpk[4];
+            u32x2 bpk[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 float v[4];
                 float rv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if constexpr (RES) {
-                    const tpspp_u32x2 rb = rres[f][h2][g];
+                    const u32x2 rb = rres[f][h2][g];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) rv[e] = bf16_bits_to_f32((unsigned short)((rb[e >> 1] >> (16 * (e & 1))) & 0xffffu));
                 }
@@ -289,10 +289,10 @@ conv3_wide_kernel(const BParams P)
                         if (valid) ob[(size_t)e * HW] = v[e];
                     continue;
                 }
-                bpk[g][0] = pack2_bf16(v[0], v[1]); bpk[g][1] = pack2_bf16(v[2], v[3]);
+                bpk[g][0] = pack_bf16(v[0], v[1]); bpk[g][1] = pack_bf16(v[2], v[3]);
                 if (g & 1) {
-                    const tpspp_u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
-                    const tpspp_u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
+                    const u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
+                    const u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
                     u32x4 unit; unit[0] = d0[0]; unit[1] = d1[0]; unit[2] = d0[1]; unit[3] = d1[1];
                     const int kg = ctile * 8 + 4 * h2 + (g - 1) + half;
                     if (valid)

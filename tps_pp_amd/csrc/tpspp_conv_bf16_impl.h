@@ -3,11 +3,10 @@
 // three-term-split instantiations): two translation units so that the ~70 instantiations compile in parallel.
 #pragma once
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 #include <type_traits>
 
-typedef unsigned int tpspp_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int tpspp_u32x2 __attribute__((ext_vector_type(2)));
-typedef short tpspp_s16x4 __attribute__((ext_vector_type(4)));
+using namespace tpspp_dev;
 
 namespace tpspp {          // shared by the two translation units: external linkage
 
@@ -22,7 +21,7 @@ struct BSrc {
 struct BParams {
     BSrc src[3];
     int nsrc;
-    const tpspp_u32x4* wt;          // [ctile][chunk][tap][k group][64][8] bf16, 16-B units
+    const u32x4* wt;          // [ctile][chunk][tap][k group][64][8] bf16, 16-B units
     const float* bias;        // (Cout) fp32 or null
     const void* res;          // (N, Cout, Ho, Wo) or null
     const float* post_scale;
@@ -41,38 +40,9 @@ namespace {
 using tpspp::BSrc;
 using tpspp::BParams;
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int BM = 256;       // output pixels per workgroup (NF = 2 fragments per wavefront; 128 with NF = 1)
 constexpr int BN = 64;        // output channels per workgroup
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ unsigned f32_to_bf16_bits(float f)
-{
-    // round to nearest even (inputs are finite activations)
-    unsigned u = __builtin_bit_cast(unsigned, f);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return u >> 16;
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// v_cvt_pk_bf16_f32: two fp32 -> packed bf16, round to nearest even
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ float bf16_bits_to_f32(unsigned short h)
-{
-    return __builtin_bit_cast(float, (unsigned)h << 16);
-}
 
 template <int KH, int SH, int SW, int TH, int TW, int NI, int KC>
 struct BCfg {
@@ -264,9 +234,9 @@ conv_tiled_bf16_kernel(const BParams P)
                     const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
 #pragma unroll
                     for (int c2 = 0; c2 < 4; ++c2) {
-                        const unsigned pk = pack2_bf16(f[2 * c2], f[2 * c2 + 1]);
+                        const unsigned pk = pack_bf16(f[2 * c2], f[2 * c2 + 1]);
                         const float h0 = __builtin_bit_cast(float, pk << 16), h1 = __builtin_bit_cast(float, pk & 0xffff0000u);
-                        const unsigned pl = pack2_bf16(f[2 * c2] - h0, f[2 * c2 + 1] - h1);
+                        const unsigned pl = pack_bf16(f[2 * c2] - h0, f[2 * c2 + 1] - h1);
                         rp[i][4 * g + c2] = (ok && have) ? pk : 0u;
                         if constexpr (X3) rpl[i][4 * g + c2] = (ok && have) ? pl : 0u;
                     }
@@ -288,12 +258,12 @@ conv_tiled_bf16_kernel(const BParams P)
                 for (int c = 0; c < KC; ++c) v[c] = (sp + (size_t)min(c, cleft - 1) * plane)[lo];
 #pragma unroll
                 for (int c2 = 0; c2 < KC / 2; ++c2) {
-                    const unsigned pk = pack2_bf16(v[2 * c2], v[2 * c2 + 1]);
+                    const unsigned pk = pack_bf16(v[2 * c2], v[2 * c2 + 1]);
                     const unsigned m = (2 * c2 + 1 < cleft) ? 0xffffffffu : ((2 * c2 < cleft) ? 0x0000ffffu : 0u);
                     rp[i][c2] = ok ? (pk & m) : 0u;
                     if constexpr (X3) {
                         const float h0 = __builtin_bit_cast(float, pk << 16), h1 = __builtin_bit_cast(float, pk & 0xffff0000u);
-                        const unsigned pl = pack2_bf16(v[2 * c2] - h0, v[2 * c2 + 1] - h1);
+                        const unsigned pl = pack_bf16(v[2 * c2] - h0, v[2 * c2 + 1] - h1);
                         rpl[i][c2] = ok ? (pl & m) : 0u;
                     }
                 }
@@ -368,10 +338,7 @@ conv_tiled_bf16_kernel(const BParams P)
                 const int im = r1 / (PH_ * NBLK), r2 = r1 - im * (PH_ * NBLK);
                 const int py = r2 / NBLK, blk = r2 - py * NBLK;
                 const unsigned short* p0 = R + (8 * g + (a >> 2)) * CHROW + (im * PH_ + py) * PWA + blk * 16 + 4 * (a & 3);
-                const tpspp_u32x2 k0 = __builtin_bit_cast(tpspp_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) tpspp_s16x4*)p0));
-                const tpspp_u32x2 k1 = __builtin_bit_cast(tpspp_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) tpspp_s16x4*)(p0 + 4 * CHROW)));
+                const u32x2 k0 = read_tr(p0), k1 = read_tr(p0 + 4 * CHROW);
                 const int px = blk * 16 + a - XOFF;
                 if (px >= 0 && px < PW) {
                     u32x4 v;
@@ -457,18 +424,18 @@ conv_tiled_bf16_kernel(const BParams P)
             const unsigned lo = valid ? (unsigned)((fimg[f] * P.Cout + 4 * half) * HoWo + oy * P.Wo + ox) : 0u;
     #pragma unroll
             for (int h2 = 0; h2 < NB; ++h2) {
-                tpspp_u32x2 bpk[4];
+                u32x2 bpk[4];
     #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v[4];
                     const int cu = 32 * h2 + 8 * g;                   // + 4*half (in `lo`) + e
                     // blocked tensors: this lane's four channels are 8 bytes of the unit (image, channel group, pixel)
                     const size_t bunit = (((size_t)n * (P.Cout >> 3) + ((co_base + cu) >> 3)) * HoWo + (size_t)(valid ? oy * P.Wo + ox : 0)) * 8 + 4 * half;
-                    tpspp_u32x2 rb; rb[0] = rb[1] = 0u;
+                    u32x2 rb; rb[0] = rb[1] = 0u;
                     float4 rb32 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                     if constexpr (!SIMPLE) {
                         if (blk_res && P.res_mode && valid && co_base + cu + 4 * half < P.Cout)
-                            rb = *reinterpret_cast<const tpspp_u32x2*>(reinterpret_cast<const unsigned short*>(P.res) + bunit);
+                            rb = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned short*>(P.res) + bunit);
                         if (blk32_res && P.res_mode && valid && co_base + cu + 4 * half < P.Cout)
                             rb32 = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(P.res) + bunit);
                     }
@@ -500,10 +467,10 @@ conv_tiled_bf16_kernel(const BParams P)
                         // the two half-wavefronts hold the two halves of a 16-byte unit: v_permlane32_swap pairs them up
                         // (lower half-wavefront: the unit of group g, upper: that of group g + 1), one 16-byte store
                         // per two groups
-                        bpk[g][0] = pack2_bf16(v[0], v[1]); bpk[g][1] = pack2_bf16(v[2], v[3]);
+                        bpk[g][0] = pack_bf16(v[0], v[1]); bpk[g][1] = pack_bf16(v[2], v[3]);
                         if (g & 1) {
-                            const tpspp_u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
-                            const tpspp_u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
+                            const u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
+                            const u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
                             u32x4 unit; unit[0] = d0[0]; unit[1] = d1[0]; unit[2] = d0[1]; unit[3] = d1[1];
                             const int kg = ((co_base + 32 * h2) >> 3) + (g - 1) + half;
                             const size_t bu = (((size_t)n * (P.Cout >> 3) + kg) * HoWo + (size_t)(valid ? oy * P.Wo + ox : 0)) * 8;
@@ -521,10 +488,10 @@ conv_tiled_bf16_kernel(const BParams P)
                             if (valid && (full_c || co4 + e < P.Cout)) (ob + (size_t)e * HoWo)[lo] = v[e];
                     } else {
                         unsigned short* ob = reinterpret_cast<unsigned short*>(P.out) + ubase + (size_t)cu * HoWo;
-                        const unsigned p01 = pack2_bf16(v[0], v[1]), p23 = pack2_bf16(v[2], v[3]);
+                        const unsigned p01 = pack_bf16(v[0], v[1]), p23 = pack_bf16(v[2], v[3]);
                         if (wide_out) {
-                            tpspp_u32x2 pk; pk[0] = p01; pk[1] = p23;
-                            *reinterpret_cast<tpspp_u32x2*>(otile + l31 * kOutPitch + cu + 4 * half) = pk;
+                            u32x2 pk; pk[0] = p01; pk[1] = p23;
+                            *reinterpret_cast<u32x2*>(otile + l31 * kOutPitch + cu + 4 * half) = pk;
                             continue;
                         }
                         if (valid && (full_c || co4 < P.Cout)) ob[lo] = (unsigned short)(p01 & 0xffffu);
@@ -546,10 +513,7 @@ conv_tiled_bf16_kernel(const BParams P)
     #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const unsigned short* pp = otile + (8 * q + (a >> 2)) * kOutPitch + 16 * i + 4 * (a & 3);
-                    const tpspp_u32x2 lo2 = __builtin_bit_cast(tpspp_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) tpspp_s16x4*)pp));
-                    const tpspp_u32x2 hi2 = __builtin_bit_cast(tpspp_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) tpspp_s16x4*)(pp + 4 * kOutPitch)));
+                    const u32x2 lo2 = read_tr(pp), hi2 = read_tr(pp + 4 * kOutPitch);
                     pv[i][0] = lo2[0]; pv[i][1] = lo2[1]; pv[i][2] = hi2[0]; pv[i][3] = hi2[1];
                 }
     #pragma unroll

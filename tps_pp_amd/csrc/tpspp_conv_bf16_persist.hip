@@ -355,7 +355,7 @@ conv3_blk_persist_kernel(const BParams P, int ntx, int nty, int ntiles)
             const int pix_o = (oy0 + fty[f]) * P.Wo + ox0 + ftx[f];
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
-                tpspp_u32x2 bpk[4];
+                u32x2 bpk[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v[4];
@@ -364,7 +364,7 @@ conv3_blk_persist_kernel(const BParams P, int ntx, int nty, int ntiles)
                     if constexpr (EPI == 1) {
                         const int cgr = (cu >> 3) < CGo ? (cu >> 3) : 0;      // (a channel group the tensor does not have: any valid unit)
                         const size_t bunit = (((size_t)n * CGo + cgr) * HoWo + pix_o) * 8 + 4 * half;
-                        const tpspp_u32x2 rb = *reinterpret_cast<const tpspp_u32x2*>(
+                        const u32x2 rb = *reinterpret_cast<const u32x2*>(
                             reinterpret_cast<const unsigned short*>(P.res) + bunit);
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
@@ -380,7 +380,7 @@ conv3_blk_persist_kernel(const BParams P, int ntx, int nty, int ntiles)
                         lo[0] = acc[f][h2][4 * g]; lo[1] = acc[f][h2][4 * g + 1]; hi[0] = acc[f][h2][4 * g + 2]; hi[1] = acc[f][h2][4 * g + 3];
                         blo[0] = bq[h2][g][0]; blo[1] = bq[h2][g][1]; bhi[0] = bq[h2][g][2]; bhi[1] = bq[h2][g][3];
                         lo = lo + blo; hi = hi + bhi;
-                        unsigned p0 = pack2_bf16(lo[0], lo[1]), p1 = pack2_bf16(hi[0], hi[1]);
+                        unsigned p0 = pack_bf16(lo[0], lo[1]), p1 = pack_bf16(hi[0], hi[1]);
                         if (relu1) {
                             const s16x2 z = {0, 0};
                             p0 = __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p0), z));
@@ -395,13 +395,13 @@ conv3_blk_persist_kernel(const BParams P, int ntx, int nty, int ntiles)
                             if (relu1) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
                             if constexpr (EPI == 1) { if (P.res_mode == 1) v[e] = v[e] + rv[e]; }
                         }
-                        if constexpr (EPI == 1) { bpk[g][0] = pack2_bf16(v[0], v[1]); bpk[g][1] = pack2_bf16(v[2], v[3]); }
+                        if constexpr (EPI == 1) { bpk[g][0] = pack_bf16(v[0], v[1]); bpk[g][1] = pack_bf16(v[2], v[3]); }
                     }
                     if constexpr (EPI != 2) {
                         // the two half-wavefronts hold the two halves of a 16-byte unit: v_permlane32_swap pairs them up
                         if (g & 1) {
-                            const tpspp_u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
-                            const tpspp_u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
+                            const u32x2 d0 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][0], bpk[g][0], false, false);
+                            const u32x2 d1 = __builtin_amdgcn_permlane32_swap(bpk[g - 1][1], bpk[g][1], false, false);
                             u32x4 unit; unit[0] = d0[0]; unit[1] = d1[0]; unit[2] = d0[1]; unit[3] = d1[1];
                             const int kg = 4 * h2 + (g - 1) + half;
                             if (kg < CGo)

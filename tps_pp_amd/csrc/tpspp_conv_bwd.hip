@@ -34,10 +34,12 @@
 // at backbones/tps_pp/tps_pp.py:126-131,149-169,537-562.
 // Bound: MFMA for the large layers; the gathers of the staging pass for the small ones.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int BP = 128;        // data gradient: source pixels per workgroup
 constexpr int BC = 64;         // data gradient: source channels per workgroup
@@ -46,8 +48,6 @@ constexpr int BO = 64;         // weight gradient: output channels per workgroup
 constexpr int RP = 32;         // weight gradient: reduction pixels per chunk
 constexpr int kTargetWgs = 1024;  // split-K: slices so that a layer fills ~4 workgroups per CU of a 256-CU part
 constexpr int kMaxSlices = 512;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct BwdSrc {
     const float* p;

@@ -93,7 +93,7 @@ conv_stem_bf16_kernel(const StemP P)
 #pragma unroll
         for (int i = 0; i < kSNP; ++i) {
             const int e = tid + 256 * i;
-            if (e < kSPS) sP[e] = u32x4{pack2_bf16(rv[i][0], rv[i][1]), pack2_bf16(rv[i][2], 0.0f), 0u, 0u};
+            if (e < kSPS) sP[e] = u32x4{pack_bf16(rv[i][0], rv[i][1]), pack_bf16(rv[i][2], 0.0f), 0u, 0u};
         }
     };
 
@@ -129,7 +129,7 @@ conv_stem_bf16_kernel(const StemP P)
             unsigned short* const ob = P.out + (((size_t)n * 4 * H + (y0 + wv)) * kSW) * 8;
 #pragma unroll
             for (int f = 0; f < 4; ++f) {
-                tpspp_u32x2 pk[4];
+                u32x2 pk[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     float v[4];
@@ -138,12 +138,12 @@ conv_stem_bf16_kernel(const StemP P)
                         v[e] = acc[f][4 * g + e] + bq[g][e];
                         if (P.relu) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
                     }
-                    pk[g][0] = pack2_bf16(v[0], v[1]); pk[g][1] = pack2_bf16(v[2], v[3]);
+                    pk[g][0] = pack_bf16(v[0], v[1]); pk[g][1] = pack_bf16(v[2], v[3]);
                 }
 #pragma unroll
                 for (int g = 0; g < 4; g += 2) {
-                    const tpspp_u32x2 d0 = __builtin_amdgcn_permlane32_swap(pk[g][0], pk[g + 1][0], false, false);
-                    const tpspp_u32x2 d1 = __builtin_amdgcn_permlane32_swap(pk[g][1], pk[g + 1][1], false, false);
+                    const u32x2 d0 = __builtin_amdgcn_permlane32_swap(pk[g][0], pk[g + 1][0], false, false);
+                    const u32x2 d1 = __builtin_amdgcn_permlane32_swap(pk[g][1], pk[g + 1][1], false, false);
                     u32x4 unit; unit[0] = d0[0]; unit[1] = d1[0]; unit[2] = d0[1]; unit[3] = d1[1];
                     *reinterpret_cast<u32x4*>(ob + ((size_t)(g + half) * plane + 32 * f + l31) * 8) = unit;
                 }
@@ -162,8 +162,8 @@ conv_stem_bf16_kernel(const StemP P)
                     v[e] = acc[f][4 * g + e] + bias;
                     if (P.relu) v[e] = v[e] > 0.0f ? v[e] : 0.0f;
                 }
-                tpspp_u32x2 pk; pk[0] = pack2_bf16(v[0], v[1]); pk[1] = pack2_bf16(v[2], v[3]);
-                *reinterpret_cast<tpspp_u32x2*>(ot + l31 * kOPitch + (32 * f + 8 * g + 4 * half) / 2) = pk;
+                u32x2 pk; pk[0] = pack_bf16(v[0], v[1]); pk[1] = pack_bf16(v[2], v[3]);
+                *reinterpret_cast<u32x2*>(ot + l31 * kOPitch + (32 * f + 8 * g + 4 * half) / 2) = pk;
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the tile is private to the wavefront: no barrier)
         unsigned short* const orow = P.out + ((size_t)n * 32 * H + (y0 + wv)) * kSW;

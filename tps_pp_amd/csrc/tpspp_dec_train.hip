@@ -13,9 +13,12 @@
 //     the sum of a row are reduced with a fixed butterfly, so every lane holds the same bits.  seq_ce_reduce_kernel: one
 //     workgroup adds the per-position losses (thread t the positions t, t + 256, ... ascending, then a fixed tree).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 #include "tpspp_train_dec.h"
 
 #include <math.h>
+
+using namespace tpspp_dev;
 
 namespace {
 
@@ -72,20 +75,6 @@ struct CeParams {
     long long s_n, s_l, s_k;
     int N, L, Lp, K, shift, ignore_index, reduction;
 };
-
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o);
-    return v;
-}
 
 // the target of scored position (b, t), or -1 where the position is ignored
 __device__ __forceinline__ int ce_target(const CeParams& P, int b, int t)

@@ -18,30 +18,14 @@
 // Reference: mmocr/models/textrecog/backbones/tps_pp/DGAB.py:25-77 (DGAB_Block.forward, Mlp.forward,
 // DGAB.forward), called from tps_pp.py:318-319.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int H = 16, W = 64, PT = 32, HID = 256;       // plane, points, MLP hidden width
 constexpr float kEps = 1e-5f;                            // nn.LayerNorm default
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// v_cvt_pk_bf16_f32: two fp32 -> packed bf16, round to nearest even
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ float readlane_f(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
 
 // Wavefront-wide reductions on the DPP path of the vector ALU (quad swaps, half-row and row mirrors, row broadcasts,
 // one v_readlane): 7 instructions and no LDS traffic, against 6 ds_bpermute round trips for the __shfl_xor butterfly --
@@ -52,7 +36,7 @@ __device__ __forceinline__ float dpp_f(float old, float v)
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
 }
 
-__device__ __forceinline__ float wave_sum(float v)
+__device__ __forceinline__ float wave_sum_dpp(float v)
 {
     v += dpp_f<0xB1>(0.0f, v);                 // quad_perm [1,0,3,2]
     v += dpp_f<0x4E>(0.0f, v);                 // quad_perm [2,3,0,1]
@@ -63,7 +47,7 @@ __device__ __forceinline__ float wave_sum(float v)
     return readlane_f(v, 63);
 }
 
-__device__ __forceinline__ float wave_max(float v)
+__device__ __forceinline__ float wave_max_dpp(float v)
 {
     v = fmaxf(v, dpp_f<0xB1>(v, v));
     v = fmaxf(v, dpp_f<0x4E>(v, v));
@@ -104,11 +88,11 @@ dgab_gate_kernel(const GateParams P)
     float s = 0.0f;
 #pragma unroll
     for (int r = 0; r < H; ++r) s += v[r];
-    const float mean = wave_sum(s) * (1.0f / (H * W));
+    const float mean = wave_sum_dpp(s) * (1.0f / (H * W));
     float q = 0.0f;
 #pragma unroll
     for (int r = 0; r < H; ++r) { const float d = v[r] - mean; q += d * d; }
-    const float var = wave_sum(q) * (1.0f / (H * W));
+    const float var = wave_sum_dpp(q) * (1.0f / (H * W));
     const float rstd = 1.0f / sqrtf(var + kEps);
     float colsum = 0.0f;
     float rowmean[H];
@@ -116,7 +100,7 @@ dgab_gate_kernel(const GateParams P)
     for (int r = 0; r < H; ++r) {
         v[r] = (v[r] - mean) * rstd * P.g1[r * W + lane] + P.b1[r * W + lane];
         colsum += v[r];
-        rowmean[r] = wave_sum(v[r]) * (1.0f / W);      // x.mean(3): over the columns
+        rowmean[r] = wave_sum_dpp(v[r]) * (1.0f / W);      // x.mean(3): over the columns
     }
     const float colmean = colsum * (1.0f / H);          // x.mean(2): over the rows
 
@@ -141,13 +125,13 @@ dgab_gate_kernel(const GateParams P)
         for (int t = 0; t < PT; ++t) ho = fmaf(P.mh_t[(H + t) * (H + 1) + o], readlane_f(yv, t), ho);
     }
     // softmaxes over w[0:64] (all lanes) and h[0:16] (lanes 0..15)
-    const float wmax = wave_max(wo);
+    const float wmax = wave_max_dpp(wo);
     const float we = expf(wo - wmax);
-    const float vw = we / wave_sum(we);
+    const float vw = we / wave_sum_dpp(we);
     const float hin = lane < H ? ho : -INFINITY;
-    const float hmax = wave_max(hin);
+    const float hmax = wave_max_dpp(hin);
     const float he = lane < H ? expf(ho - hmax) : 0.0f;
-    const float vh = he / wave_sum(he);
+    const float vh = he / wave_sum_dpp(he);
     const float hlast = readlane_f(ho, H);
 
     // A = (v_h * xn) * h_last + (v_w * xn) * w_last      (op order of DGAB.py:50)
@@ -413,14 +397,6 @@ __device__ __forceinline__ void gemm64b3(const u32x4* __restrict__ slab, const u
         acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0l, bb, acc[0], 0, 0, 0);
         acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1l, bb, acc[1], 0, 0, 0);
     }
-}
-
-// hi / lo halves of a pair: hi = bf16(v), lo = bf16(v - hi)
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo)
-{
-    hi = pack_bf16(v0, v1);
-    const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(v0 - h0, v1 - h1);
 }
 
 __device__ __forceinline__ void to_operands3(const float (&v)[32], u32x4 (&out)[4], u32x4 (&outl)[4])

@@ -36,17 +36,11 @@
 // (the 1x1 bias in registers) per workgroup, ring of 5 rows, LDS counters instead of barriers, pieces two steps ahead --
 // bit-identical and no faster (64-72 us): the producers' vector instructions, not the phases' order, set the step time.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
-
-constexpr int kWave = 64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct DownFParams {
     const unsigned short* in;       // (N, 32, H, W) bf16
@@ -83,16 +77,6 @@ constexpr int kRing = 3;
 constexpr int kW0Units = 256;
 constexpr int kTileBytes = 2048;                 // a wavefront's input tile [32 channels][32 pixels]
 constexpr int kSmemBytes = kW0Units * 16 + 128 * 4 + 4 * kTileBytes + kRing * kRowUnits * 16;
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ u32x2 read_tr(const unsigned short* p)
-{
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
-}
 
 __global__ void __launch_bounds__(256, 2)
 down_fused_kernel(const DownFParams P)
@@ -318,13 +302,6 @@ down_fused_kernel(const DownFParams P)
 // Ah Bh, Ah Bl, Al Bh per (chunk, tap) in the convolution kernel's order.  The 36 hi and 36 lo weight fragments of a
 // wavefront are 288 registers: one workgroup of four wavefronts per CU (512 registers each).
 constexpr int kSmemX3 = 2 * kW0Units * 16 + 128 * 4 + 2 * kRing * kRowUnits * 16;
-
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo)
-{
-    hi = pack_bf16(v0, v1);
-    const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(v0 - h0, v1 - h1);
-}
 
 struct DownXParams {
     const float* in;                // (N, 32, H, W) fp32

@@ -16,15 +16,16 @@
 // Reference: TPS_PP.forward / TPS_PP.grid, mmocr/models/textrecog/backbones/tps_pp/tps_pp.py:560-562,
 // 580-585 (down0, down1, down2, up_sample, torch.cat, down_feat).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 #ifndef FRONT_FENCE
 #define FRONT_FENCE 0
 #endif
 constexpr bool FENCE = FRONT_FENCE;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct FrontParams {
     const float* o0; const float* o1;      // (N, 32, H, W)

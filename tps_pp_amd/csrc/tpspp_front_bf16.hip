@@ -23,15 +23,11 @@
 // Reference: TPS_PP.forward / TPS_PP.grid, mmocr/models/textrecog/backbones/tps_pp/tps_pp.py:560-562,580-585.
 // Bound: HBM (2.4 MB per image at 17 kMAC per pixel).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
-
-constexpr int kWave = 64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct FrontBParams {
     const unsigned short* o0; const unsigned short* o1;   // (N, 32, H, W) bf16
@@ -47,15 +43,6 @@ struct FrontBParams {
     int blk;                                              // feat0 / feat1 / feat2 in the blocked layout (N, 8, H, W, 8)
     int N, H, W;
 };
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
 
 // ---- data movement -------------------------------------------------------------------------------------------------
 // A lane's MFMA operands are 2-byte elements of 16 (32) different channel planes, and its results are 2-byte elements
@@ -76,14 +63,6 @@ typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
 // distinct banks; reads: rows at 0 / 38 / 12 / 50 dwords mod 64).
 constexpr int kTileBytes = 8192;            // inputs: outs0 [32][32] | outs1 [32][32] | x doubled [64][32]; then the outputs
 constexpr int kOutPitch = 76;               // 16-bit elements per pixel row of the output tile
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u32x2 read_tr(const unsigned short* p)
-{
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
-}
 
 // one input tile of 2 KB in global memory: 128 pieces of 16 bytes, two per lane; a channel's row segment holds
 // 1 << QB pieces.  The pieces of the NEXT segment are fetched into registers while this one is computed.
@@ -401,13 +380,6 @@ struct FrontXParams {
     int N, H, W;
     int blk;                     // feat0 / feat1 / feat2 in the fp32 blocked layout (N, 8, H, W, 8) (tpspp_conv2d_bf16_fwd code 3)
 };
-
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo)
-{
-    hi = pack_bf16(v0, v1);
-    const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(v0 - h0, v1 - h1);
-}
 
 template <int NK>
 __device__ __forceinline__ void load_b3(const float* __restrict__ base, unsigned lo, int plane, u32x4 (&bh)[NK], u32x4 (&bl)[NK])

@@ -29,31 +29,16 @@
 
 #include <mutex>
 #include "tpspp_tokgemm.h"
+#include "tpspp_dev.h"
 
 #include <cstdlib>
 
+using namespace tpspp_dev;
+
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kDK = 64;                 // head width (d_k = d_v = 64: every NRTR config of the reference)
 constexpr int kKRow = kDK + 4;          // LDS row stride of the staged keys / values (16-B aligned rows)
-
-__device__ __forceinline__ float readlane_f(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, kWave));
-    return v;
-}
 
 // ---- re-layouts ---------------------------------------------------------------------------------
 // (N, C, T) -> (C, N*T): out[c][b*T + t] = in[b][c][t]   (rows of T stay contiguous on both sides)
@@ -243,8 +228,6 @@ attn_enc_kernel(const float* __restrict__ qkv, int C, int M, int T, const int* _
 //     same two keys.  No LDS, no barrier.
 // NJ = ceil(T / 32) key tiles (template, <= 4).  Scores are scaled by 1/8 through q, keys >= valid_len[b]
 // get probability 0.
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-
 // (round 6: compiled for three workgroups per CU -- NJ = 2, the 64-token case, took 172 registers = two wavefronts per SIMD,
 // 168 is three; the kernel waits for memory)
 template <int NJ>
@@ -274,7 +257,7 @@ attn_enc_mfma_kernel(const float* __restrict__ qkv, int C, int M, int T, const i
 #pragma unroll
     for (int ks = 0; ks < 32; ++ks) qf[ks] = qp[(size_t)(2 * ks + half) * M + ic] * 0.125f;
 
-    f32x16_t sc[NJ];
+    f32x16 sc[NJ];
 #pragma unroll
     for (int jb = 0; jb < NJ; ++jb) {
 #pragma unroll
@@ -313,7 +296,7 @@ attn_enc_mfma_kernel(const float* __restrict__ qkv, int C, int M, int T, const i
     // O^T = V P^T, two feature tiles of 32
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt) {
-        f32x16_t o;
+        f32x16 o;
 #pragma unroll
         for (int r = 0; r < 16; ++r) o[r] = 0.0f;
         const float* vrow = vp + (size_t)(dt * 32 + l31) * M;   // A-operand row: feature
@@ -947,23 +930,12 @@ dec_init_tokens_kernel(int* __restrict__ tokens, int Nb, int Lt, int start_idx, 
 //   * four wavefronts split K (K/64 MFMA k-steps each, every load of a wavefront in flight together), four partial
 //     tiles meet in 16 KB of LDS;
 //   * LayerNorm folded as in tpspp_linear_ln_fwd: sum and sum of squares of the raw row ride on the same loads.
-typedef __bf16 dbf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned du32x4 __attribute__((ext_vector_type(4)));
-typedef float df32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 dbf16x2 __attribute__((ext_vector_type(2)));
-
 struct DGemm {
-    const float* X; const du32x4* Wp; const float* bias; const float* colsum; const float* res; float* out;
+    const float* X; const u32x4* Wp; const float* bias; const float* colsum; const float* res; float* out;
     int M, K, Co;            // Co: valid outputs (the arranged weight is padded to a multiple of 32)
     float eps; int act;      // act: 0 none, 2 GELU (erf)
     int remap = 0;           // dec_gemm_tile
 };
-
-__device__ __forceinline__ unsigned dpack2(float lo, float hi)
-{
-    df32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, dbf16x2));
-}
 
 // Workgroup -> (token block, output tile) for the step GEMMs.  Workgroups go to the 8 XCDs round-robin in launch order and
 // every XCD has its own L2, which each launch fills with the X rows (the previous launch's output) and the W tiles its
@@ -1003,13 +975,13 @@ dec_gemm_x3_kernel(const DGemm P)
     const int ntiles = (P.Co + 31) >> 5;
     const float4* xp = reinterpret_cast<const float4*>(P.X + (size_t)mc * P.K + 16 * (wv * KSW) + 8 * half);
     float4 xa[KSW][2];
-    du32x4 ah[NT][KSW], al[NT][KSW];
+    u32x4 ah[NT][KSW], al[NT][KSW];
 #pragma unroll
     for (int j = 0; j < KSW; ++j) { xa[j][0] = xp[4 * j]; xa[j][1] = xp[4 * j + 1]; }   // every load of the wavefront in flight together
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl) {
         const int ct = ct0 + tl < ntiles ? ct0 + tl : ntiles - 1;     // (a tile past the last one repeats it; never finished)
-        const du32x4* wp = P.Wp + ((size_t)(ct * KS + wv * KSW) * 4 + half) * 32 + l31;
+        const u32x4* wp = P.Wp + ((size_t)(ct * KS + wv * KSW) * 4 + half) * 32 + l31;
 #pragma unroll
         for (int j = 0; j < KSW; ++j) { ah[tl][j] = wp[(size_t)j * 128]; al[tl][j] = wp[(size_t)j * 128 + 64]; }
     }
@@ -1030,7 +1002,7 @@ dec_gemm_x3_kernel(const DGemm P)
             if (P.res) r4[tl] = *reinterpret_cast<const float4*>(P.res + o[tl]);
         }
     }
-    f32x16_t acc[NT];
+    f32x16 acc[NT];
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl)
 #pragma unroll
@@ -1039,23 +1011,23 @@ dec_gemm_x3_kernel(const DGemm P)
 #pragma unroll
     for (int j = 0; j < KSW; ++j) {
         const float x[8] = {xa[j][0].x, xa[j][0].y, xa[j][0].z, xa[j][0].w, xa[j][1].x, xa[j][1].y, xa[j][1].z, xa[j][1].w};
-        du32x4 bh, bl;
+        u32x4 bh, bl;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const unsigned pk = dpack2(x[2 * q], x[2 * q + 1]);
+            const unsigned pk = pack_bf16(x[2 * q], x[2 * q + 1]);
             const float h0 = __builtin_bit_cast(float, pk << 16), h1 = __builtin_bit_cast(float, pk & 0xffff0000u);
             bh[q] = pk;
-            bl[q] = dpack2(x[2 * q] - h0, x[2 * q + 1] - h1);
+            bl[q] = pack_bf16(x[2 * q] - h0, x[2 * q + 1] - h1);
             if (LN) {
                 s1 += x[2 * q] + x[2 * q + 1];
                 s2 = fmaf(x[2 * q], x[2 * q], s2);
                 s2 = fmaf(x[2 * q + 1], x[2 * q + 1], s2);
             }
         }
-        const dbf16x8 Bh = __builtin_bit_cast(dbf16x8, bh), Bl = __builtin_bit_cast(dbf16x8, bl);
+        const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh), Bl = __builtin_bit_cast(bf16x8, bl);
 #pragma unroll
         for (int tl = 0; tl < NT; ++tl) {
-            const dbf16x8 Ah = __builtin_bit_cast(dbf16x8, ah[tl][j]), Al = __builtin_bit_cast(dbf16x8, al[tl][j]);
+            const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[tl][j]), Al = __builtin_bit_cast(bf16x8, al[tl][j]);
             acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc[tl], 0, 0, 0);
             acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc[tl], 0, 0, 0);
             acc[tl] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc[tl], 0, 0, 0);
@@ -1149,7 +1121,7 @@ dec_gemm_f32_kernel(const DGemmF P)
             if (P.res) r4[tl] = *reinterpret_cast<const float4*>(P.res + o[tl]);
         }
     }
-    f32x16_t acc[NT];
+    f32x16 acc[NT];
 #pragma unroll
     for (int tl = 0; tl < NT; ++tl)
 #pragma unroll
@@ -1220,7 +1192,7 @@ bool dec_gemm_x3(hipStream_t st, const float* X, const void* Wp, const float* bi
     if (!f32 && K == 512 && colsum && Co >= 1024) {
         const dim3 grid3((unsigned)((M + 31) / 32), (unsigned)(((Co + 31) / 32 + 2) / 3));
         DGemm P;
-        P.X = X; P.Wp = reinterpret_cast<const du32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
+        P.X = X; P.Wp = reinterpret_cast<const u32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
         P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = 1;
         hipLaunchKernelGGL((dec_gemm_x3_kernel<8, true, 3>), grid3, dim3(256), 0, st, P);
         return true;
@@ -1239,7 +1211,7 @@ bool dec_gemm_x3(hipStream_t st, const float* X, const void* Wp, const float* bi
         return true;
     }
     DGemm P;
-    P.X = X; P.Wp = reinterpret_cast<const du32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
+    P.X = X; P.Wp = reinterpret_cast<const u32x4*>(Wp); P.bias = bias; P.colsum = colsum; P.res = res; P.out = out;
     P.M = M; P.K = K; P.Co = Co; P.eps = eps; P.act = act; P.remap = 1;
     if (K == 512) {
         if (colsum) hipLaunchKernelGGL((dec_gemm_x3_kernel<8, true>), grid, dim3(256), 0, st, P);

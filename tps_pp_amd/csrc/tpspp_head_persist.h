@@ -134,10 +134,10 @@ struct PGemm {
 // splits it over four: a 512-thread workgroup has 256 registers per lane, and with an eighth of K per wavefront the weights
 // of all three q|k|v tiles -- 96 registers -- can be requested before the barrier)
 template <int KSW>
-__device__ __forceinline__ void pgemm_load_w(du32x4 (&ah)[KSW], du32x4 (&al)[KSW], const PGemm& G, int ct, int wv, int half, int l31)
+__device__ __forceinline__ void pgemm_load_w(u32x4 (&ah)[KSW], u32x4 (&al)[KSW], const PGemm& G, int ct, int wv, int half, int l31)
 {
     constexpr int KS = 8 * KSW;                             // 16-wide k-steps of the whole K
-    const du32x4* wp = reinterpret_cast<const du32x4*>(G.Wp) + ((size_t)(ct * KS + wv * KSW) * 4 + half) * 32 + l31;
+    const u32x4* wp = reinterpret_cast<const u32x4*>(G.Wp) + ((size_t)(ct * KS + wv * KSW) * 4 + half) * 32 + l31;
 #pragma unroll
     for (int j = 0; j < KSW; ++j) { ah[j] = wp[(size_t)j * 128]; al[j] = wp[(size_t)j * 128 + 64]; }
 }
@@ -190,7 +190,7 @@ __device__ __forceinline__ bool pgemm_phase(const PGemm& G, int tb, int ct0, PSh
     const int ntiles = (G.Co + 31) >> 5;
     const bool wg_active = ct0 < ntiles;                   // (w1: 8 tiles, classifier: 3 -- the other workgroups only pass the barrier)
     const int m0 = tb * 32;                                 // (tb: the cluster's token block in the whole batch)
-    du32x4 ah[NT][KSW], al[NT][KSW];
+    u32x4 ah[NT][KSW], al[NT][KSW];
     // in front of the barrier: everything that does not depend on the previous phase -- the weights, and the epilogue's
     // operands (column sums, bias, and the residual: it was produced at least two phases ago, i.e. behind barriers this
     // workgroup has already passed)
@@ -230,17 +230,17 @@ __device__ __forceinline__ bool pgemm_phase(const PGemm& G, int tb, int ct0, PSh
     float s1 = 0.0f, s2 = 0.0f, mean = 0.0f, rstd = 1.0f;
     const float* xs = S.sX + l31 * kPXPitch + 16 * (wv * KSW) + 8 * half;
     // the lane's B fragments (hi / lo halves of its 8 k per k-step) once, for every tile
-    du32x4 bh[KSW], bl[KSW];
+    u32x4 bh[KSW], bl[KSW];
 #pragma unroll
     for (int j = 0; j < KSW; ++j) {
         const float4 x0 = *reinterpret_cast<const float4*>(xs + 16 * j), x1 = *reinterpret_cast<const float4*>(xs + 16 * j + 4);
         const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const unsigned pk = dpack2(x[2 * q], x[2 * q + 1]);
+            const unsigned pk = pack_bf16(x[2 * q], x[2 * q + 1]);
             const float h0 = __builtin_bit_cast(float, pk << 16), h1 = __builtin_bit_cast(float, pk & 0xffff0000u);
             bh[j][q] = pk;
-            bl[j][q] = dpack2(x[2 * q] - h0, x[2 * q + 1] - h1);
+            bl[j][q] = pack_bf16(x[2 * q] - h0, x[2 * q + 1] - h1);
             if (LN) {
                 s1 += x[2 * q] + x[2 * q + 1];
                 s2 = fmaf(x[2 * q], x[2 * q], s2);
@@ -256,13 +256,13 @@ __device__ __forceinline__ bool pgemm_phase(const PGemm& G, int tb, int ct0, PSh
         // wavefronts 0 - 3 finish the tile: accumulator registers 4 w .. 4 w + 3 = outputs 32 ct + 8 w + 4 half + (0 .. 3) of token l31
         const bool mine = wv < 4 && ct < ntiles && m < G.M && c < G.Co;
         const size_t o = (size_t)mc * G.ldo + (c < G.Co ? c : 0);
-        f32x16_t acc;
+        f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 #pragma unroll
         for (int j = 0; j < KSW; ++j) {
-            const dbf16x8 Bh = __builtin_bit_cast(dbf16x8, bh[j]), Bl = __builtin_bit_cast(dbf16x8, bl[j]);
-            const dbf16x8 Ah = __builtin_bit_cast(dbf16x8, ah[tl][j]), Al = __builtin_bit_cast(dbf16x8, al[tl][j]);
+            const bf16x8 Bh = __builtin_bit_cast(bf16x8, bh[j]), Bl = __builtin_bit_cast(bf16x8, bl[j]);
+            const bf16x8 Ah = __builtin_bit_cast(bf16x8, ah[tl][j]), Al = __builtin_bit_cast(bf16x8, al[tl][j]);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bh, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ah, Bl, acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Al, Bh, acc, 0, 0, 0);
@@ -363,7 +363,7 @@ __device__ __forceinline__ bool pgemm_phase_f32(const PGemm& G, int tb, int ct0,
         const int c = ct * 32 + 8 * (wv & 3) + 4 * half;
         const bool mine = wv < 4 && ct < ntiles && m < G.M && c < G.Co;
         const size_t o = (size_t)mc * G.ldo + (c < G.Co ? c : 0);
-        f32x16_t acc;
+        f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
 #pragma unroll

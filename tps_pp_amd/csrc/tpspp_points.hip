@@ -11,25 +11,13 @@
 // Everything is fp32 with fp32 accumulation; these feed the control points, which the TPS solve
 // amplifies by up to ~223x, so no reduced precision anywhere.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int CH = 64, NPT = 32, PH = 2, PW = 16;
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // one wavefront per image; lane = channel, 32 registers = the pixels of that channel
 __global__ void __launch_bounds__(64)

@@ -23,19 +23,19 @@
 // Replaces (reference, mmocr/models/textrecog/): the autograd of backbones/tps_pp/DGAB.py:25-77 and
 // backbones/tps_pp/tps_pp.py:27-82,293-323.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 
 #include <math.h>
 
+using namespace tpspp_dev;
+
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int TM = 64;          // mm / wgrad: output rows per workgroup
 constexpr int TN = 64;          // mm / wgrad: output columns per workgroup
 constexpr int TK = 16;          // K chunk staged through LDS
 constexpr int kMaxSlices = 512;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
@@ -515,8 +515,6 @@ struct CbamParams {
     float* ws;                // backward: [N][Cr*C + C*Cr + 18 + 1]
     int C, Cr, H, W;
 };
-
-__device__ __forceinline__ float sigmoidf(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 // shared front of the forward and the backward: x, out1 = ca * x, channel avg / max (+ argmax), the MLP's hidden layer,
 // the spatial map (channel mean / max of out1, + argmax)

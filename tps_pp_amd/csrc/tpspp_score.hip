@@ -9,13 +9,13 @@
 // Reference: Transformation_Parameter_Estimation.get_score / atten_score,
 // mmocr/models/textrecog/backbones/tps_pp/tps_pp.py:293-312 (einsum 'bmc,bnc->bmn', * 64^-0.5, tanh).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int C = 64, M1 = 32, M2 = 128, PT = 32;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ScoreParams {
     const float* de;       // (N, 64, n)
@@ -114,11 +114,6 @@ score_kernel(const ScoreParams P)
 // Result registers chain into the next layer's operand as in tpspp_front_bf16.hip (k-slots in the order
 // [0,1,2,3,8,9,10,11,4,5,6,7,12,..,15] inside every 16 features: the weight slabs are permuted on the host, the
 // per-image point matrix while it is staged).  ~5e-6 of scale before the tanh.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct ScoreXParams {
     const float* de;       // (N, 64, n)
     const u32x4* w1;       // [hi|lo][4 k-steps][2][32 out][8]   natural k order
@@ -130,19 +125,6 @@ struct ScoreXParams {
     int n;
     float scale;
 };
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-__device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigned& lo)
-{
-    hi = pack_bf16(v0, v1);
-    const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
-    lo = pack_bf16(v0 - h0, v1 - h1);
-}
 
 __device__ __forceinline__ f32x16 mfma3(const u32x4& ah, const u32x4& al, const u32x4& bh, const u32x4& bl, f32x16 acc)
 {

@@ -34,31 +34,15 @@
 #include "tpspp_common.h"
 #include <cstdlib>
 #include "tpspp_tokgemm.h"
+#include "tpspp_dev.h"
+
+using namespace tpspp_dev;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int BM = 128, KST = 32;                // tokens per workgroup, k per stage
 constexpr int PITCH = 160;                       // 16-bit elements per k row of the LDS tile (80 words)
 constexpr int EPITCH = 68;                       // words per output row of the epilogue's tile
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned pack2(float lo, float hi)
-{
-    f32x2 v; v[0] = lo; v[1] = hi;
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ u32x2 read_tr(const unsigned short* p)
-{
-    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
-}
 
 template <bool X3, int NCI>
 __global__ void __launch_bounds__(256, 2)
@@ -94,13 +78,13 @@ tok_gemm_kernel(const tpspp::TokGemmArgs P)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int idx = tid + 256 * i, row = idx >> 5, c4 = idx & 31;
-            const unsigned h0 = pack2(xr[i].x, xr[i].y), h1 = pack2(xr[i].z, xr[i].w);
+            const unsigned h0 = pack_bf16(xr[i].x, xr[i].y), h1 = pack_bf16(xr[i].z, xr[i].w);
             u32x2 hv; hv[0] = h0; hv[1] = h1;
             *reinterpret_cast<u32x2*>(&sX[buf][0][row][4 * c4]) = hv;
             if (X3) {
                 const float f0 = __builtin_bit_cast(float, h0 << 16), f1 = __builtin_bit_cast(float, h0 & 0xffff0000u);
                 const float f2 = __builtin_bit_cast(float, h1 << 16), f3 = __builtin_bit_cast(float, h1 & 0xffff0000u);
-                u32x2 lv; lv[0] = pack2(xr[i].x - f0, xr[i].y - f1); lv[1] = pack2(xr[i].z - f2, xr[i].w - f3);
+                u32x2 lv; lv[0] = pack_bf16(xr[i].x - f0, xr[i].y - f1); lv[1] = pack_bf16(xr[i].z - f2, xr[i].w - f3);
                 *reinterpret_cast<u32x2*>(&sX[buf][HL - 1][row][4 * c4]) = lv;
             }
         }
@@ -225,11 +209,7 @@ tok_gemm_kernel(const tpspp::TokGemmArgs P)
                     else {
                         unsigned h[4];
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            unsigned u = __builtin_bit_cast(unsigned, o[e]);
-                            u += 0x7fffu + ((u >> 16) & 1u);
-                            h[e] = u >> 16;
-                        }
+                        for (int e = 0; e < 4; ++e) h[e] = f32_to_bf16_bits(o[e]);
                         u32x2 pk; pk[0] = h[0] | (h[1] << 16); pk[1] = h[2] | (h[3] << 16);
                         *reinterpret_cast<u32x2*>(reinterpret_cast<unsigned short*>(P.out) + off) = pk;
                     }

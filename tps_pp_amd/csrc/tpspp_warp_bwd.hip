@@ -18,12 +18,14 @@
 //           preprocessor/tps_preprocessor.py:71-83,270-282 (torch.bmm / F.grid_sample backward).
 // Bound: L2 atomics + HBM (every g_out element read once, 4 atomics per tap set).
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 
 #include <type_traits>
 
+using namespace tpspp_dev;
+
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kMaxK = 64;          // F + 3 <= 64, as in the forward
 
 struct BwdParams {

@@ -2,14 +2,13 @@
 // Arithmetic contract: see include/tpspp.h; everything here must stay bit-identical to
 // oracle/tps_oracle.c (weight_form 2).  Compiled with -ffp-contract=off.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "tpspp_dev.h"
 
 #include <cstdint>
 #include <type_traits>
 
 namespace tpspp_dev {
 
-constexpr int kWave = 64;
 constexpr int kMaxK = 64;  // F + 3 <= 64: one lane per row of T in the wave-level solve
 
 struct Taps {
@@ -89,11 +88,6 @@ __device__ __forceinline__ void sample_planes(const float* __restrict__ in, floa
         return;
     }
     for (; c < C; ++c) out[(size_t)c * n] = bilerp(in + (size_t)c * HW, t);
-}
-
-__device__ __forceinline__ float readlane_f(float v, int lane)
-{
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
 // One wavefront: T[i] = sum_q inv[i][q] * Cz[q], q ascending, FMA chain from 0.  Lane i owns row i.

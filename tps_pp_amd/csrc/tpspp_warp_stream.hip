@@ -93,9 +93,7 @@ __device__ __forceinline__ void store_elem(char* base, unsigned pix, float v, fl
 }
 __device__ __forceinline__ void store_elem(char* base, unsigned pix, float v, unsigned short*)
 {
-    unsigned u = __builtin_bit_cast(unsigned, v);                       // round to nearest even
-    u += 0x7fffu + ((u >> 16) & 1u);
-    *reinterpret_cast<unsigned short*>(base + 2u * pix) = (unsigned short)(u >> 16);
+    *reinterpret_cast<unsigned short*>(base + 2u * pix) = (unsigned short)f32_to_bf16_bits(v);   // round to nearest even
 }
 
 template <typename T>
