@@ -804,7 +804,9 @@ int tpspp_layernorm_cm_fwd(const float* x, const float* gamma, const float* beta
  * Multi-head self-attention of the encoder on already projected q/k/v:
  *   qkv (3C, N*T) channel-major: rows [0,C) = q, [C,2C) = k, [2C,3C) = v; head h = rows [64h, 64h+64)
  *   out (C, N*T):  softmax_j(q_i . k_j / 8  masked to j < valid_len[b]) . v_j   per image b and head
- *   valid_len (N) device int32 or NULL (no mask); T <= 256.
+ *   valid_len (N) device int32 or NULL (no mask); T <= 256.  1 <= valid_len[b]; values above T mean T.  The columns of k
+ *   and v at or beyond valid_len[b] are never used: whatever they hold, NaN included, reaches no output (the columns of
+ *   q there are queries like any other, and their outputs are written).
  * replaces: common/modules/transformer_module.py:24-33,82-93 (ScaledDotProductAttention inside
  *           MultiHeadAttention) with the key mask of encoders/nrtr_encoder.py:51-65
  */
@@ -820,7 +822,16 @@ int tpspp_attn_enc_fwd(const float* qkv, int N, int C, int T, const int* valid_l
  *   w_gamma (K, Cout) = diag(gamma) W_kmajor,   w_colsum (Cout) = column sums of w_gamma,
  *   bias_eff (Cout)   = beta^T W_kmajor (+ bias)  or NULL when that is zero,
  * so that  W^T LN(x)[:, m] = rstd_m (w_gamma^T x[:, m] - mean_m w_colsum) + bias_eff  and the kernel multiplies
- * the raw activation (mean / rstd of every column are accumulated from the same loads, biased variance, eps).
+ * the activation as it loads it (mean / rstd of every column are accumulated from the same loads, biased variance, eps).
+ * Every column is shifted by the median of three of its values (features 0, K/2 and K-1) before it enters the products
+ * and the sums, which leaves the identity as it is; both differences then lose digits as |mean - shift| / std of the
+ * column grows, not as |mean| / std does.  Measured on an MI355X against float64 (tests/test_gpu_head_primitives.py,
+ * K = 127 .. 513, both layouts): at |mean| / std = 16 and 64 of every column the relative L2 error is 1.2e-7 .. 2.7e-7 and
+ * 1.2e-7 .. 3.0e-7, next to 3.5e-7 .. 5.4e-7 and 1.1e-6 .. 1.9e-6 of PyTorch's fp32 LayerNorm -> Linear (the same formula
+ * on the unshifted values, in fp32 on the CPU: 5.3e-6 .. 1.3e-5 and 9.0e-5 .. 2.0e-4); with one feature 64 or 1000 away
+ * from the rest, in a sampled row or not, 1.1e-7 .. 3.2e-7.  The worst case is a shift that is itself an outlier: features
+ * 0 and K-1 both 64 or 1000 above the rest give 9.8e-7 .. 1.3e-6 at K = 128 and 5.5e-6 .. 1.1e-5 at K = 512 / 513
+ * (PyTorch and the unshifted formula: 1.2e-7 .. 3.7e-7).
  * replaces: `norm` followed by a projection, common/layers/transformer_layers.py:150-163
  */
 int tpspp_linear_ln_fwd(const float* x, int K, int M, float eps, const float* w_gamma,

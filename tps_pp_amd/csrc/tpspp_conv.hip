@@ -683,11 +683,20 @@ conv1x1_skinny_f32_kernel(const ConvParams P)
 // out = act(W^T LN(x) + bias) [+ res] for a channel-major x (K, M) with few columns (a decoder step).
 // With gamma folded into the weight rows on the host (Wg = diag(gamma) W) the normalisation commutes with
 // the product:   W^T LN(x)[:, m] = rstd_m (Wg^T x[:, m] - mean_m colsum(Wg)) + W^T beta,
-// so the MFMAs run on the RAW activation while the same loads feed sum / sum-of-squares per column
+// so the MFMAs run on the activation as loaded while the same loads feed sum / sum-of-squares per column
 // (two VALU FMAs per value); mean and rstd meet the accumulators in the epilogue.  The split-K workgroup
 // touches all K values of its 32 columns exactly once (4 wavefronts x 2 k-parities), so the statistics
 // cost one extra LDS row per wavefront in the reduction that is there anyway: no separate LayerNorm
-// launch, no normalised copy of x in HBM.  var = E[x^2] - mean^2 in fp32 (inputs are O(1) activations).
+// launch, no normalised copy of x in HBM.
+// Every column is SHIFTED as it is loaded by s_m = the median of three of its values, x[0][m], x[K/2][m], x[K-1][m] (one
+// subtraction per value; the same s_m in every wavefront, so the partial sums add up): the MFMAs and the statistics run on
+// d = x - s_m, for which
+//   Wg^T x - mean colsum = Wg^T d - mean(d) colsum   and   var(x) = E[d^2] - mean(d)^2.
+// Both differences lose digits as (mean / std)^2 of what they are formed from grows.  On the raw values that is the column's
+// own ratio (|mean| >> std; or K = 2 with two nearly equal values: a relative error of 1e-3 at mean 0); on d it is
+// |mean - s_m| / std, about 1 whenever s_m is a typical value of the column.  The median of three is one unless two of the
+// three sampled features are outliers of their column on the same side; then the ratio can reach sqrt(K) (include/tpspp.h
+// gives the measured loss).  A single value (x[0][m]) would be that bad for one outlying feature.
 // LN_ON_A = false: x is the B operand, output (Cout, M) channel-major;
 // LN_ON_A = true : operands swapped, x is the A operand, output (M, Cout') token-major.
 struct LnArgs {
@@ -716,6 +725,9 @@ conv1x1_skinny_ln_f32_kernel(const ConvParams P, const LnArgs L)
     const bool pix_ok = pix < HoWo, co_ok = co < P.Cout;
     const float* xp = P.src[0].p + (size_t)n * K * HoWo + (pix_ok ? pix : 0);
     const float* wp = P.wt + (co_ok ? co : 0);
+    const float* xcol = LN_ON_A ? wp : xp;                 // this lane's column of x: rows are xstep apart
+    const size_t xstep = LN_ON_A ? (size_t)P.Cout : (size_t)HoWo;
+    const float shift = __builtin_amdgcn_fmed3f(xcol[0], xcol[(size_t)(K >> 1) * xstep], xcol[(size_t)(K - 1) * xstep]);
 
     f32x16 acc;
 #pragma unroll
@@ -735,7 +747,8 @@ conv1x1_skinny_ln_f32_kernel(const ConvParams P, const LnArgs L)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < UB; ++u) {
-            const float xv = LN_ON_A ? a[u] : b[u];
+            const float xv = (LN_ON_A ? a[u] : b[u]) - shift;
+            if (LN_ON_A) a[u] = xv; else b[u] = xv;
             s1 += xv;
             s2 = fmaf(xv, xv, s2);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
@@ -750,8 +763,8 @@ conv1x1_skinny_ln_f32_kernel(const ConvParams P, const LnArgs L)
             const int kk = k_ok ? k : k_lo;
             const float av = wp[(size_t)kk * P.Cout];
             const float bv = xp[(size_t)kk * HoWo];
-            a[u] = (k_ok && co_ok) ? av : 0.0f;
-            b[u] = (k_ok && pix_ok) ? bv : 0.0f;
+            a[u] = (k_ok && co_ok) ? (LN_ON_A ? av - shift : av) : 0.0f;      // a value that is not there stays 0
+            b[u] = (k_ok && pix_ok) ? (LN_ON_A ? bv : bv - shift) : 0.0f;
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -769,7 +782,7 @@ conv1x1_skinny_ln_f32_kernel(const ConvParams P, const LnArgs L)
     __syncthreads();
     constexpr int RPW = NW >= 16 ? 1 : 16 / NW;          // accumulator registers finished per wavefront (see the plain kernel)
     if (!pix_ok || wv * RPW >= 16) return;
-    float mean_l = 0.0f, rstd_l = 0.0f;
+    float mean_l = 0.0f, rstd_l = 0.0f;                    // (mean: of the shifted column, which is what acc was formed from)
     if (!LN_ON_A) {                                        // statistics of this lane's pixel column
         float t1 = 0.0f, t2 = 0.0f;
 #pragma unroll

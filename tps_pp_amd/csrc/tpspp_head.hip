@@ -227,7 +227,8 @@ attn_enc_kernel(const float* __restrict__ qkv, int C, int M, int T, const int* _
 //     those two keys (half = 0, 1) are taken as the k-pair of MFMA step r; the A operand reads V at the
 //     same two keys.  No LDS, no barrier.
 // NJ = ceil(T / 32) key tiles (template, <= 4).  Scores are scaled by 1/8 through q, keys >= valid_len[b]
-// get probability 0.
+// get probability 0 and their V columns are not read (the index is clamped to the last valid key), so whatever a
+// masked column of k or v holds, NaN included, cannot reach the output.
 // (round 6: compiled for three workgroups per CU -- NJ = 2, the 64-token case, took 172 registers = two wavefronts per SIMD,
 // 168 is three; the kernel waits for memory)
 template <int NJ>
@@ -246,6 +247,7 @@ attn_enc_mfma_kernel(const float* __restrict__ qkv, int C, int M, int T, const i
     const size_t col0 = (size_t)b * T;
     int nvalid = valid_len ? valid_len[b] : T;
     nvalid = nvalid < T ? nvalid : T;
+    const int jlast = nvalid > 0 ? nvalid - 1 : 0;           // the last valid key: what a masked V column index is clamped to
     const int i = ib * 32 + l31;                             // this lane's query (B-operand column)
     const int ic = i < T ? i : T - 1;
     const float* qp = qkv + (size_t)(kDK * h) * M + col0;
@@ -306,7 +308,7 @@ attn_enc_mfma_kernel(const float* __restrict__ qkv, int C, int M, int T, const i
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int j = jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                vf[r] = vrow[j < T ? j : T - 1];
+                vf[r] = vrow[j < nvalid ? j : jlast];             // a masked column is never read: 0 x NaN would reach o
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) o = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[r], sc[jb][r], o, 0, 0, 0);
@@ -929,7 +931,9 @@ dec_init_tokens_kernel(int* __restrict__ tokens, int Nb, int Lt, int start_idx, 
 //     accumulated in fp32 (~5e-6 of a layer's scale, as in tpspp_conv2d_bf16_fwd's split3);
 //   * four wavefronts split K (K/64 MFMA k-steps each, every load of a wavefront in flight together), four partial
 //     tiles meet in 16 KB of LDS;
-//   * LayerNorm folded as in tpspp_linear_ln_fwd: sum and sum of squares of the raw row ride on the same loads.
+//   * LayerNorm folded by the identity of tpspp_linear_ln_fwd, but on the RAW row: its sum and sum of squares ride on the
+//     same loads.  (tpspp_linear_ln_fwd shifts every column by the median of three of its values first; this kernel does
+//     not, so the two differ numerically once |mean| >> std of a token: include/tpspp.h gives that kernel's figures.)
 struct DGemm {
     const float* X; const u32x4* Wp; const float* bias; const float* colsum; const float* res; float* out;
     int M, K, Co;            // Co: valid outputs (the arranged weight is padded to a multiple of 32)
