@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TPSPP_ABI_VERSION 11  /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
+#define TPSPP_ABI_VERSION 12  /* 2 (round 4): tpspp_warp_bwd and tpspp_nrtr_decoder_fwd carry the sizes of their workspace / pointer table;
                                3: tpspp_down_fused_bf16_fwd / _x3_fwd / _f32_fwd, tpspp_token_gemm_bf16_fwd, tpspp_front_fwd and tpspp_front_bf16_fwd takes feat0 = feat1 = NULL;
                                4 (round 6): tpspp_nrtr_decoder_fwd takes status_out, tpspp_resize_normalize_fwd takes interpolation;
                                5 (round 6): tpspp_warp_plan_create / _run / _run_on / _destroy;
@@ -48,7 +48,9 @@ extern "C" {
                                   tpspp_attn_train_fwd_ex / _bwd_ex, tpspp_embed_pos_fwd, tpspp_embed_bwd (+ _workspace_floats),
                                   tpspp_seq_ce_fwd / _bwd;
                                11: the train pipeline's augmentation kernel, declared in tpspp_augment.h:
-                                  tpspp_augment_normalize_fwd */
+                                  tpspp_augment_normalize_fwd;
+                               12: no new entry point: tpspp_warp_fwd / tpspp_warp_plan_* accept TPSPP_IO_BF16 on a classic
+                                  call with the prepared table (bf16 images in and out on the in-place kernel) */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -144,8 +146,18 @@ int tpspp_prepare_mirror_table(const float* p_hat, int p_hat_ld, int Ho, int Wo,
 #define TPSPP_IO_BF16 4            /* table_flags bit: in0 / in1 / out0 / out1 hold bfloat16 (the pointers are
                                       reinterpreted; everything else stays fp32).  The bf16 configuration
                                       (BASELINE.json configs[2]): T, grid and interpolation in fp32 exactly as
-                                      without the flag, one round-to-nearest-even at the store.  Shapes the
-                                      plane-streaming kernel takes only (TPS_PP geometry); else TPSPP_EINVAL. */
+                                      without the flag, one round-to-nearest-even at the store.  Accepted for
+                                      (a) a classic call with the prepared table: one input, no score / p_xy,
+                                      H0 == Ho, W0 == Wo, C0 in {1, 3}, F = 20, p_hat_t from
+                                      tpspp_prepare_mirror_table with TPSPP_TABLE_MIRROR4 | TPSPP_TABLE_PACKED,
+                                      in0 / out0 16-byte aligned, a bf16 image that fits the LDS (every geometry
+                                      with a prepared table up to 64x256x3); grid_or_null / idx_or_null keep the
+                                      bits they have without the flag;
+                                      (b) shapes the plane-streaming kernel takes (TPS_PP geometry).
+                                      Anything else: TPSPP_EINVAL, and tpspp_last_error names the condition that
+                                      is not met (a classic call without p_hat_t, without the two table bits or
+                                      without mirror symmetry included).  tpspp_warp_set_tuning's kernel_choice /
+                                      bands are not consulted when the bit is set. */
 
 /*
  * The fused hot path: T-solve -> grid -> bilinear warp of in0 (and in1 when non-NULL) in ONE kernel;
@@ -156,6 +168,7 @@ int tpspp_prepare_mirror_table(const float* p_hat, int p_hat_ld, int Ho, int Wo,
  *   coalesced / LDS-staged fast kernels; NULL selects the generic kernel -- identical results);
  *   table_flags: OR of TPSPP_TABLE_MIRROR4, TPSPP_TABLE_PACKED, TPSPP_TABLE_SPAN (only meaningful with p_hat_t),
  *   TPSPP_SCORE_TRANSPOSED (none of them changes results) and TPSPP_IO_BF16 (bf16 images in and out);
+ *   with TPSPP_IO_BF16 the classic rectifier (prepared table required) and the TPS_PP geometry are served, see the bit;
  *   grid_or_null (N,Ho*Wo,2); idx_or_null (N,Ho*Wo,2) int32 = NW corner in in0.
  * replaces: GridGenerator.build_P_prime + F.grid_sample   tps_preprocessor.py:71-83
  *           Attention_Enhanced_TPS.build_P_prime + 2x F.grid_sample   tps_pp.py:597-615

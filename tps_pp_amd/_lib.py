@@ -11,7 +11,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtpspp_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _f = ctypes.c_void_p       # device pointers travel as integers
 _i = ctypes.c_int

@@ -1090,7 +1090,17 @@ TPSPP_EXPORT int tpspp_warp_fwd(const float* in0, int C0, int H0, int W0,
     if (N == 0) return TPSPP_OK;
     hipStream_t st = tpspp::as_stream(stream);
     if (table_flags & TPSPP_IO_BF16) {
-        // bf16 images in and out (the bf16 configuration): plane-streaming kernel only
+        // bf16 images in and out (the bf16 configuration).  A classic call with the prepared table: the in-place kernel with
+        // bf16 planes (tpspp_warp_geo_bf16.h); tpspp_warp_set_tuning is not consulted on this branch.
+        const bool classic = !in1 && !score && !p_xy && H0 == Ho && W0 == Wo;
+        const bool table_ok = p_hat_t && (table_flags & TPSPP_TABLE_MIRROR4) && (table_flags & TPSPP_TABLE_PACKED);
+        const bool aligned = reinterpret_cast<uintptr_t>(in0) % 16 == 0 && reinterpret_cast<uintptr_t>(out0) % 16 == 0;
+        const char* why = classic ? tpspp::geo_bf16_kernel_refusal(C0, Ho, Wo, F) : nullptr;
+        if (classic && table_ok && aligned && !why) {
+            const float* packed = p_hat_t + (size_t)(F + 3) * Ho * Wo;           // second part of the prepared table
+            if (tpspp::launch_geo_bf16_kernel(C0, Ho, Wo, F, in0, ctrl, inv_delta_c, packed, N, out0, grid_or_null, idx_or_null, st))
+                return tpspp::check_launch("tpspp_warp_fwd(in-place, bf16 planes)");
+        }
         tpspp::StreamArgs A;
         A.in0 = in0; A.C0 = C0; A.H0 = H0; A.W0 = W0;
         A.in1 = in1; A.C1 = C1; A.H1 = H1; A.W1 = W1;
@@ -1100,9 +1110,22 @@ TPSPP_EXPORT int tpspp_warp_fwd(const float* in0, int C0, int H0, int W0,
         A.p_hat = p_hat; A.p_hat_ld = p_hat_ld; A.p_xy = p_xy; A.p_hat_t = p_hat_t;
         A.N = N; A.F = F; A.Ho = Ho; A.Wo = Wo;
         A.out0 = out0; A.out1 = out1; A.grid = grid_or_null; A.idx = idx_or_null;
-        if (!tpspp::stream_kernel_applicable(A))
-            return tpspp::fail(TPSPP_EINVAL, "tpspp_warp_fwd: TPSPP_IO_BF16 needs a shape the plane-streaming kernel "
+        if (!tpspp::stream_kernel_applicable(A)) {
+            // say what a classic call lacks; any other call gets the plane-streaming kernel's conditions
+            const char* missing = !classic ? nullptr
+                                  : !p_hat_t ? "p_hat_t is NULL: the classic kernels read the table of tpspp_prepare_mirror_table"
+                                  : !table_ok ? "table_flags lack TPSPP_TABLE_MIRROR4 | TPSPP_TABLE_PACKED (a mirror-symmetric table "
+                                                "prepared by tpspp_prepare_mirror_table)"
+                                  : why ? why
+                                  : !aligned ? "in0 / out0 are not 16-byte aligned" : nullptr;
+            if (missing)
+                return tpspp::fail(TPSPP_EINVAL, "tpspp_warp_fwd: TPSPP_IO_BF16 on a classic call (one input, H0 == Ho, W0 == Wo) "
+                                   "needs the prepared table, C0 in {1, 3}, F = 20, 16-byte aligned images and a bf16 image "
+                                   "that fits the LDS; here: %s", missing);
+            return tpspp::fail(TPSPP_EINVAL, "tpspp_warp_fwd: TPSPP_IO_BF16 needs a classic call with the prepared table (one "
+                               "input, H0 == Ho, W0 == Wo, no score / p_xy) or a shape the plane-streaming kernel "
                                "takes (F = 20 or 32, <= 1024 output pixels, planes that fit the LDS ring)");
+        }
         return tpspp::launch_stream_kernel(A, g_trace, st);
     }
 

@@ -29,4 +29,12 @@ void span_set_tuning(int bands, int gather, int lds_kb, int no_spec);
 bool launch_span_kernel(int C, int H, int W, int F, const float* in, const float* ctrl, const float* inv_delta_c,
                         const float* span_packed, int N, float* out, float* grid, int32_t* idx, hipStream_t st);
 
+// ---- bf16 images in and out (tpspp_warp_geo_bf16.h): the in-place kernel with run-time geometry, one image per workgroup ----
+// nullptr when (C, H = Ho, W = Wo, F) fits the kernel (C in {1, 3}, F = 20, a packed table exists, the bf16 image fits the
+// LDS), else the condition that is not met
+const char* geo_bf16_kernel_refusal(int C, int H, int W, int F);
+// enqueue it (in / out: bf16 bits, 16-byte aligned); false (nothing launched) when not applicable
+bool launch_geo_bf16_kernel(int C, int H, int W, int F, const void* in, const float* ctrl, const float* inv_delta_c,
+                            const float* packed, int N, void* out, float* grid, int32_t* idx, hipStream_t st);
+
 }  // namespace tpspp

@@ -223,12 +223,18 @@ def _warp_call(who, in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, out
                want_grid=False, want_idx=False):
     """The checks of one `tpspp_warp_fwd` call, for `warp` and `WarpPlan` (who): -> (the checked tensors, in argument
     order, that must outlive the launch; the final table_flags; the argument tuple).  `warp` takes bfloat16 images
-    (TPSPP_IO_BF16: T, grid and interpolation stay fp32) and allocates the outputs it is not given; a plan is fp32 and works
-    on its caller's buffers."""
+    (TPSPP_IO_BF16: T, grid and interpolation stay fp32) and allocates the outputs it is not given; a plan works on its
+    caller's buffers and is bfloat16 when in0 (and in1) and out0 (and out1) all are -- mixed dtypes raise before anything
+    else is looked at."""
     plan = who == "WarpPlan"
     table_flags = int(table_flags)
     io_dtype = torch.float32
-    if not plan and isinstance(in0, torch.Tensor) and in0.dtype == torch.bfloat16:
+    if plan and isinstance(in0, torch.Tensor):
+        for nm, t in (("in1", in1), ("out0", out0), ("out1", out1)):
+            if isinstance(t, torch.Tensor) and t.dtype != in0.dtype:
+                raise TypeError(f"WarpPlan: in0 / in1 / out0 / out1 must share their dtype (all float32 or all bfloat16); "
+                                f"in0 is {in0.dtype}, {nm} is {t.dtype}")
+    if isinstance(in0, torch.Tensor) and in0.dtype == torch.bfloat16:
         if in1 is not None and in1.dtype != torch.bfloat16:
             raise TypeError("warp: in0 and in1 must share their dtype")
         io_dtype = torch.bfloat16

@@ -78,10 +78,13 @@ class LocalizationNetwork(nn.Module):
         convolutions over the batch.  No CPU / library-kernel path."""
         ops.require_gpu(batch_img, "LocalizationNetwork", self.training)
         n = batch_img.size(0)
-        x = batch_img.float().contiguous()
         mode = getattr(self, "compute_dtype", None)
         if mode is None and not hasattr(self, "compute_dtype"):
             mode = default_compute_dtype()
+        # (a bf16 image goes to the plain-bf16 convolution as it is: the kernel rounds an fp32 source to bf16 as it stages
+        # it, so the widened copy would give the same bits)
+        as_is = mode == torch.bfloat16 and batch_img.dtype == torch.bfloat16
+        x = batch_img.contiguous() if as_is else batch_img.float().contiguous()
         if mode == torch.bfloat16 or mode == "bf16x3":
             # bf16 configuration: the four convolutions on the bf16 matrix cores (fp32 maps in and out: operands are
             # rounded as they are staged, accumulation / bias / ReLU fp32); pooling and the two FCs stay fp32.
@@ -169,8 +172,22 @@ class TPSPreprocessor(BasePreprocessor):
         self.LocalizationNetwork = LocalizationNetwork(num_fiducial, num_img_channel)
         self.GridGenerator = GridGenerator(num_fiducial, rectified_img_size)
 
+    def set_compute_dtype(self, mode):
+        """Opt-in precision switch of the eval path (not in the reference: its modules are fp32).
+        None (the default): a bf16 input is widened, the output is fp32.
+        torch.bfloat16: `forward` returns bf16 -- the image reaches the warp as bf16 (an fp32 input is cast once; T, grid
+        and interpolation stay fp32, one rounding at the store) and the localisation network runs its bf16 convolutions.
+        "bf16x3": the localisation network's three-term bf16 split only; image in and out stay fp32.
+        The training / gradient path stays fp32 in every mode."""
+        if not (mode is None or mode == "bf16x3" or mode == torch.bfloat16):
+            raise ValueError('set_compute_dtype: None, "bf16x3" or torch.bfloat16')
+        self.io_dtype = torch.bfloat16 if mode == torch.bfloat16 else None
+        self.LocalizationNetwork.compute_dtype = mode
+        return self
+
     def rectify(self, batch_img, batch_C_prime, want_grid=False, want_idx=False):
-        """The hot path alone: control points -> rectified image (fused HIP kernel)."""
+        """The hot path alone: control points -> rectified image (fused HIP kernel).  A bfloat16 image gives a bfloat16
+        result (needs the prepared table, i.e. a mirror-symmetric P_hat and a geometry that has one)."""
         gg = self.GridGenerator
         P_hat_t, flags = gg.prepared_table()
         out, _, grid, idx = ops.warp(batch_img, batch_C_prime, gg.inv_delta_C, gg.P_hat,
@@ -199,5 +216,10 @@ class TPSPreprocessor(BasePreprocessor):
             ctrl = self.LocalizationNetwork._forward_torch(batch_img.float())
             return ops.warp_autograd(batch_img.float(), ctrl.float(), gg.inv_delta_C, gg.P_hat,
                                      self.rectified_img_size, P_hat_t=P_hat_t, table_flags=flags)
+        if getattr(self, "io_dtype", None) == torch.bfloat16:
+            ops.require_gpu(batch_img, "TPSPreprocessor")
+            img = batch_img if batch_img.dtype == torch.bfloat16 else batch_img.to(torch.bfloat16)
+            batch_C_prime = self.LocalizationNetwork(img)
+            return self.rectify(img, batch_C_prime.float())
         batch_C_prime = self.LocalizationNetwork(batch_img)
         return self.rectify(batch_img.float(), batch_C_prime.float())
