@@ -157,7 +157,11 @@ int tpspp_prepare_mirror_table(const float* p_hat, int p_hat_ld, int Ho, int Wo,
                                       Anything else: TPSPP_EINVAL, and tpspp_last_error names the condition that
                                       is not met (a classic call without p_hat_t, without the two table bits or
                                       without mirror symmetry included).  tpspp_warp_set_tuning's kernel_choice /
-                                      bands are not consulted when the bit is set. */
+                                      bands are not consulted when the bit is set.
+                                      tpspp_warp_bwd honours the bit too: g_out0 / g_out1 / in0 / in1 / g_in0 / g_in1
+                                      hold bfloat16; grid, T, the tables, score, g_ctrl, g_score, the workspace and
+                                      all accumulation stay as without it.  Served and refused forms: see
+                                      tpspp_warp_bwd. */
 
 /*
  * The fused hot path: T-solve -> grid -> bilinear warp of in0 (and in1 when non-NULL) in ONE kernel;
@@ -226,6 +230,19 @@ void tpspp_warp_plan_destroy(tpspp_warp_plan_t* plan);
  * p_xy == NULL (p_xy means the TPS_PP table layout, whose p_hat lacks the [1, x, y] columns the one-launch form reads from the
  * transposed classic table), p_hat_t given and 16-byte aligned, C0 <= 3, F <= 21, Ho*Wo in (1024, 4096] and a multiple of 4,
  * the fp64 accumulator, and the TPSPP_BWD_TWO_KERNELS flag bit unset.
+ * TPSPP_IO_BF16 in `table_flags`: g_out0, g_out1, in0, in1, g_in0 and g_in1 hold bfloat16 (the pointers are reinterpreted, as in
+ * the forward).  Everything else keeps its type: grid, T, the tables, score, g_ctrl, g_score, the workspace (dL/d grid in its
+ * first N * Ho*Wo * 2 floats included) and all accumulation.  bf16 is widened exactly to fp32 as it is read; every product,
+ * chain and accumulator is the fp32 kernel's; g_in0 / g_in1 are the fp32 kernel's values on the widened inputs, rounded once
+ * to nearest even when the finished LDS plane is stored; NaN and Inf behave as without the bit.  g_ctrl, g_score and dL/d grid
+ * have the bits of the fp32 call on the widened inputs.  Served: (a) the one-launch form, under its conditions above with the
+ * image staged at two bytes per pixel (8 C0 H0 W0 bytes of LDS <= 78 KB); (b) the sampling + parameter kernels where
+ * dL/d input is finished in LDS: Ho*Wo <= 4096, input planes of at most 4096 pixels, one or two inputs, with or without a
+ * score; both accumulators; TPSPP_BWD_TWO_KERNELS keeps its meaning.  Both need H0*W0 (and H1*W1) to be a multiple of 8 (bf16
+ * planes of whole 16-byte pieces) and in0 / in1 / g_in0 / g_in1 16-byte aligned.  Refused with TPSPP_EINVAL before any launch
+ * or memset, tpspp_last_error naming the condition: every shape that without the bit accumulates dL/d input in HBM (more than
+ * 4096 output pixels, a plane of more than 4096 pixels) -- a bf16 sum cannot be accumulated there -- and misaligned planes.
+ * These conditions are checked before the N == 0 return: a call with N = 0 tells whether a geometry is served.
  * replaces: autograd through backbones/tps_pp/tps_pp.py:467-496,597-615;
  *           preprocessor/tps_preprocessor.py:71-83,270-282
  */

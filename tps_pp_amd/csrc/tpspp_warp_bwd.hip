@@ -56,6 +56,11 @@ struct BwdParams {
 constexpr int kCPT = 8;
 constexpr int kBwdMaxG = 8;      // sampling workgroups per (image, input) of kernel A'': bounds the workspace
 
+// An image / output-gradient element as the LDS-accumulating kernels read it.  IO = float, or unsigned short for
+// TPSPP_IO_BF16 (bfloat16 bits, widened exactly: every product, chain and accumulator behind the load is the fp32 kernel's).
+__device__ __forceinline__ float ld_io(const float* p) { return *p; }
+__device__ __forceinline__ float ld_io(const unsigned short* p) { return bf16_bits_to_f32(*p); }
+
 __global__ void __launch_bounds__(256)
 warp_bwd_sample_kernel(const BwdParams P, int chunks0, float* __restrict__ g_grid)
 {
@@ -222,10 +227,13 @@ warp_bwd_sample_lds_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* 
 // the pass's largest |g|), and a non-finite incoming gradient poisons exactly the four taps it touches, as ATen's
 // kernel does.  The sum of fp32 terms in fp64 is exact up to 2^-53 relative per addition: the fp32 result is the
 // correctly rounded sum except for ties broken by the order of arrival.
-template <int PPT, int NT, bool F64>
-__global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
-warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* __restrict__ g_grid_part,
-                            int* __restrict__ arrivals)
+// IO (TPSPP_IO_BF16): the element type of in / g_out / g_in.  bf16 elements are widened as they are read; a finished plane is
+// rounded to fp32 exactly as without the bit and then once more, to nearest even, to bf16 (v_cvt_pk_bf16_f32: NaN stays NaN,
+// Inf stays Inf): g_in is the fp32 kernel's result on the widened inputs, rounded once.  Stores are 8 bytes per lane.
+template <typename IO, int PPT, int NT, bool F64>
+__device__ __forceinline__ void
+warp_bwd_sample_lds2_body(const BwdParams& P, int G, int cpt0, int cpt1, float* __restrict__ g_grid_part,
+                          int* __restrict__ arrivals)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];   // [cpt][H*W] fixed point
     __shared__ float sMax[2][NT / 64];
@@ -238,12 +246,17 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
     const int chunks = (C + cpt - 1) / cpt;
     const bool want = P.g_in[i] != nullptr;
     const int tid = threadIdx.x;
+    // KG: pixels whose taps are derived and requested together.  All PPT of them, once per workgroup -- except in the bf16 form
+    // with 1024 threads.  There 128 registers per thread do not hold the taps' state and 32 widened values next to the
+    // addresses of 40 two-byte loads (34 registers spilled), and a kernel with a private segment is not shipped: that form
+    // requests the pass's incoming gradients first (the fixed-point scale needs them all) and then derives and requests the
+    // taps KG pixels at a time, in every pass again, from the grid (same expressions, same bits; the grid stays in L2).
+    constexpr int KG = (!std::is_same<IO, float>::value && NT == 1024) ? 2 : PPT;
     if (blockIdx.x == 0 && tid == 0) arrivals[b] = 0;      // the parameter kernel's arrival counter of this image (next launch)
 
     // this thread's pixels: taps once
     int o00[PPT]; float fw[PPT], fn[PPT], mx[PPT], my[PPT]; bool inx[PPT], iny[PPT], livep[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
+    auto derive = [&](int k) {
         const int p = tid + k * NT;
         livep[k] = p < P.n;
         const float2 g = reinterpret_cast<const float2*>(P.grid)[(size_t)b * P.n + (livep[k] ? p : 0)];
@@ -257,6 +270,11 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
         fw[k] = ix - fx; fn[k] = iy - fy;
         inx[k] = (x0 + 1) < W; iny[k] = (y0 + 1) < H;
         o00[k] = y0 * W + x0;
+    };
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        if constexpr (KG == PPT) derive(k);
+        else livep[k] = tid + k * NT < P.n;
     }
     float gx[PPT], gy[PPT];
 #pragma unroll
@@ -270,23 +288,26 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
     for (int ch = grp; ch < chunks; ch += G) {
         const int c_lo = ch * cpt;
         const int nc = min(cpt, C - c_lo);
-        const float* in = P.in[i] + ((size_t)b * C + c_lo) * plane;
-        const float* go = P.g_out[i] + ((size_t)b * C + c_lo) * P.n;
-        float* gi = want ? P.g_in[i] + ((size_t)b * C + c_lo) * plane : nullptr;
+        const IO* in = reinterpret_cast<const IO*>(P.in[i]) + ((size_t)b * C + c_lo) * plane;
+        const IO* go = reinterpret_cast<const IO*>(P.g_out[i]) + ((size_t)b * C + c_lo) * P.n;
+        IO* gi = want ? reinterpret_cast<IO*>(P.g_in[i]) + ((size_t)b * C + c_lo) * plane : nullptr;
         for (int c2 = 0; c2 < nc; c2 += 2) {               // two planes per pass: same taps, same weights
             const bool two = c2 + 1 < nc;
-            const float* pl0 = in + (size_t)c2 * plane;
-            const float* pl1 = in + (size_t)(two ? c2 + 1 : c2) * plane;
+            const IO* pl0 = in + (size_t)c2 * plane;
+            const IO* pl1 = in + (size_t)(two ? c2 + 1 : c2) * plane;
             float gv[PPT][2], v[PPT][2][4];
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {                // every load of the pass in flight together
-                const int p = livep[k] ? tid + k * NT : 0;
+            auto load_taps = [&](int k) {
                 const int a01 = inx[k] ? o00[k] + 1 : o00[k], a10 = iny[k] ? o00[k] + W : o00[k];
                 const int a11 = (inx[k] && iny[k]) ? o00[k] + W + 1 : o00[k];
-                gv[k][0] = go[(size_t)c2 * P.n + p];
-                gv[k][1] = go[(size_t)(two ? c2 + 1 : c2) * P.n + p];
-                v[k][0][0] = pl0[o00[k]]; v[k][0][1] = pl0[a01]; v[k][0][2] = pl0[a10]; v[k][0][3] = pl0[a11];
-                v[k][1][0] = pl1[o00[k]]; v[k][1][1] = pl1[a01]; v[k][1][2] = pl1[a10]; v[k][1][3] = pl1[a11];
+                v[k][0][0] = ld_io(pl0 + o00[k]); v[k][0][1] = ld_io(pl0 + a01); v[k][0][2] = ld_io(pl0 + a10); v[k][0][3] = ld_io(pl0 + a11);
+                v[k][1][0] = ld_io(pl1 + o00[k]); v[k][1][1] = ld_io(pl1 + a01); v[k][1][2] = ld_io(pl1 + a10); v[k][1][3] = ld_io(pl1 + a11);
+            };
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {                // every load of the pass in flight together (KG == PPT)
+                const int p = livep[k] ? tid + k * NT : 0;
+                gv[k][0] = ld_io(go + (size_t)c2 * P.n + p);
+                gv[k][1] = ld_io(go + (size_t)(two ? c2 + 1 : c2) * P.n + p);
+                if constexpr (KG == PPT) load_taps(k);
             }
             // fixed-point scale of this pass: 2^(50 - e) with 2^e > max |g| over the two planes (a term then has 50
             // significant bits, 4096 terms stay below 2^62)
@@ -327,6 +348,13 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
             }
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
+                if constexpr (KG != PPT) {                 // the taps of the next KG pixels
+                    if (k % KG == 0) {
+                        __builtin_amdgcn_sched_barrier(0);  // (or the scheduler hoists every group's loads to the top again)
+#pragma unroll
+                        for (int j = 0; j < KG; ++j) { derive(k + j); load_taps(k + j); }
+                    }
+                }
                 if (!livep[k]) continue;
                 const float w = fw[k], nn = fn[k], e = 1.0f - w, s = 1.0f - nn;
                 const float nw = s * e, ne = s * w, sw = nn * e, se = nn * w;
@@ -363,7 +391,7 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
                 // the pass's planes out (fixed point -> fp32, 16-byte stores) and zeroed for the next pass: the same
                 // thread reads and clears a piece
                 const int m4 = ((two ? 2 : 1) * plane) >> 2;
-                float4* gi4 = reinterpret_cast<float4*>(gi + (size_t)c2 * plane);
+                IO* gout = gi + (size_t)c2 * plane;
                 const float nanv = __builtin_nanf("");
                 for (int e = tid; e < m4; e += NT) {
                     const ulonglong2 r0 = acc2[2 * e], r1 = acc2[2 * e + 1];
@@ -378,7 +406,8 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
                     o.z = (float)((double)(long long)r1.x * inv_scale); o.w = (float)((double)(long long)r1.y * inv_scale);
                     if (!fin[4 * e >= plane ? 1 : 0]) o = make_float4(nanv, nanv, nanv, nanv);   // (planes are whole float4s)
                     }
-                    gi4[e] = o;
+                    if constexpr (std::is_same<IO, float>::value) reinterpret_cast<float4*>(gout)[e] = o;
+                    else reinterpret_cast<uint2*>(gout)[e] = make_uint2(pack_bf16(o.x, o.y), pack_bf16(o.z, o.w));
                 }
                 __syncthreads();
             }
@@ -386,9 +415,29 @@ warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float*
     }
     // (slice stride = the G * nin workgroups of this image: with one input no slice stays empty, nothing to zero)
     float2* part = reinterpret_cast<float2*>(g_grid_part) + ((size_t)b * gridDim.x + blockIdx.x) * P.n;
+    if constexpr (KG != PPT) {                             // (the border-clip factors)
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) derive(k);
+    }
 #pragma unroll
     for (int k = 0; k < PPT; ++k)
         if (livep[k]) part[tid + k * NT] = make_float2(gx[k] * mx[k], gy[k] * my[k]);
+}
+
+template <int PPT, int NT, bool F64>
+__global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
+warp_bwd_sample_lds2_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* __restrict__ g_grid_part,
+                            int* __restrict__ arrivals)
+{
+    warp_bwd_sample_lds2_body<float, PPT, NT, F64>(P, G, cpt0, cpt1, g_grid_part, arrivals);
+}
+
+template <int PPT, int NT, bool F64>
+__global__ void __launch_bounds__(NT, NT == 256 ? 2 : 1)
+warp_bwd_sample_lds2_bf16_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* __restrict__ g_grid_part,
+                                 int* __restrict__ arrivals)
+{
+    warp_bwd_sample_lds2_body<unsigned short, PPT, NT, F64>(P, G, cpt0, cpt1, g_grid_part, arrivals);
 }
 
 // ---- kernel B: parameter gradients from g_grid.  B1: S workgroups per image, each over n / S pixels: dL/d score,
@@ -558,10 +607,13 @@ warp_bwd_params_kernel(const BwdParams P, float* __restrict__ g_grid, const floa
 // of ~12 terms per lane: ~1e-5 of the largest entry).
 constexpr int kClassicNT = 1024;
 
-template <int C>
-__global__ void __launch_bounds__(kClassicNT, 8)
-warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
+// IO (TPSPP_IO_BF16) as in kernel A'': the image is staged at two bytes per pixel and a tap is a 16-bit LDS read, widened; the
+// accumulators, the chains and dL/d grid are the fp32 form's; a finished accumulator is rounded to fp32 and then once to bf16.
+template <int C, typename IO>
+__device__ __forceinline__ void
+warp_bwd_classic_body(const BwdParams& P, float* __restrict__ g_grid)
 {
+    constexpr bool kF32 = std::is_same<IO, float>::value;
     extern __shared__ __attribute__((aligned(16))) unsigned long long acc[];   // see the phases below
     __shared__ double sPart[kClassicNT / kWave][6];
     __shared__ double sGT[24 * 2];
@@ -574,9 +626,9 @@ warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
 
     // ---- requests: this thread's 4 grid points and incoming gradients, and the image's planes -> LDS ----
-    const float* in = P.in[0] + (size_t)b * C * plane;
-    const float* go = P.g_out[0] + (size_t)b * C * n;
-    float* sin_ = reinterpret_cast<float*>(acc);               // phase A: [C][plane] fp32 (+ W + 1 words that masked taps may read)
+    const IO* in = reinterpret_cast<const IO*>(P.in[0]) + (size_t)b * C * plane;
+    const IO* go = reinterpret_cast<const IO*>(P.g_out[0]) + (size_t)b * C * n;
+    IO* sin_ = reinterpret_cast<IO*>(acc);                     // phase A: [C][plane] elements (+ W + 1 that masked taps may read)
     float2 g4[PPT];
     float gv[PPT][C];
 #pragma unroll
@@ -586,9 +638,9 @@ warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
         g4[k] = reinterpret_cast<const float2*>(P.grid)[(size_t)b * n + pc];
 #pragma unroll
         for (int c = 0; c < C; ++c)                            // (32-bit byte offsets from the image's uniform base)
-            gv[k][c] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(go) + 4u * (unsigned)(c * n + pc));
+            gv[k][c] = ld_io(reinterpret_cast<const IO*>(reinterpret_cast<const char*>(go) + (unsigned)sizeof(IO) * (unsigned)(c * n + pc)));
     }
-    for (int e = tid; e < (C * plane) >> 2; e += NT)
+    for (int e = tid; e < (C * plane) >> (kF32 ? 2 : 3); e += NT)   // 16-byte pieces
         reinterpret_cast<float4*>(sin_)[e] = reinterpret_cast<const float4*>(in)[e];
     __syncthreads();
 
@@ -625,8 +677,8 @@ warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 // (a masked tap is read anyway -- the word exists: next row, next plane or the pad -- and replaced by zero)
-                const float* q = sin_ + c * plane + o00;
-                const float v00 = q[0], r01 = q[1], r10 = q[W], r11 = q[W + 1];
+                const IO* q = sin_ + c * plane + o00;
+                const float v00 = ld_io(q), r01 = ld_io(q + 1), r10 = ld_io(q + W), r11 = ld_io(q + W + 1);
                 const float g = gv[k][c];
                 const float a01 = inx ? r01 : 0.0f, a10 = iny ? r10 : 0.0f, a11 = inxy ? r11 : 0.0f;
                 gx += ((a01 - v00) * s + (a11 - a10) * nn) * g;
@@ -685,10 +737,12 @@ warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
         __syncthreads();                                       // every contribution has landed
         // (one 16-byte LDS read = two accumulators per lane: consecutive lanes on consecutive banks; two reads per lane for a
         // 16-byte store put the lanes 32 bytes apart -- a two-way bank conflict on every read)
-        float2* gi2 = reinterpret_cast<float2*>(P.g_in[0] + (size_t)b * C * plane);
+        IO* gi = reinterpret_cast<IO*>(P.g_in[0]) + (size_t)b * C * plane;
         for (int e = tid; e < (C * plane) >> 1; e += NT) {
             const ulonglong2 r0 = acc2[e];
-            gi2[e] = make_float2((float)__longlong_as_double((long long)r0.x), (float)__longlong_as_double((long long)r0.y));
+            const float o0 = (float)__longlong_as_double((long long)r0.x), o1 = (float)__longlong_as_double((long long)r0.y);
+            if constexpr (kF32) reinterpret_cast<float2*>(gi)[e] = make_float2(o0, o1);
+            else reinterpret_cast<unsigned*>(gi)[e] = pack_bf16(o0, o1);
         }
         __syncthreads();                                       // the planes' space is free
     }
@@ -805,6 +859,20 @@ warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
     }
 }
 
+template <int C>
+__global__ void __launch_bounds__(kClassicNT, 8)
+warp_bwd_classic_kernel(const BwdParams P, float* __restrict__ g_grid)
+{
+    warp_bwd_classic_body<C, float>(P, g_grid);
+}
+
+template <int C>
+__global__ void __launch_bounds__(kClassicNT, 8)
+warp_bwd_classic_bf16_kernel(const BwdParams P, float* __restrict__ g_grid)
+{
+    warp_bwd_classic_body<C, unsigned short>(P, g_grid);
+}
+
 }  // namespace
 
 namespace { int g_bwd_fixed_point = 0; }
@@ -841,6 +909,27 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
     TPSPP_REQUIRE(p_hat_ld >= (p_xy ? F : F + 3), "tpspp_warp_bwd: p_hat_ld too small");
     TPSPP_REQUIRE(!g_score || score, "tpspp_warp_bwd: g_score without score");
     TPSPP_REQUIRE(!g_in1 || in1, "tpspp_warp_bwd: g_in1 without in1");
+    const size_t elems0 = (size_t)H0 * W0, elems1 = in1 ? (size_t)H1 * W1 : 0;
+    if (table_flags & TPSPP_IO_BF16) {
+        // bf16 images and gradients: only the forms that finish a plane in LDS are served (a bf16 sum cannot be accumulated
+        // in HBM).  Conditions for two-byte planes: a plane of whole 16-byte pieces is 8 elements (then every plane of a
+        // 16-byte aligned tensor starts at a 16-byte boundary: the classic form stages the image in such pieces; g_in leaves
+        // in 4- / 8-byte pieces); kernel A'' holds two planes of 8-byte accumulators in 64 KB.  Refused before the N == 0
+        // return, so that a caller can ask with N = 0 whether a geometry is served (ops._WarpFunction does, in its forward).
+        const char* why =
+            (size_t)Ho * Wo > 4096 ? "Ho*Wo > 4096 output pixels"
+            : (elems0 > 4096 || elems1 > 4096) ? "an input plane of more than 4096 pixels (two planes of accumulators do not fit 64 KB of LDS)"
+            : (elems0 % 8 != 0 || elems1 % 8 != 0) ? "H0*W0 (H1*W1) is not a multiple of 8: bf16 planes are not whole 16-byte pieces"
+            : (reinterpret_cast<uintptr_t>(in0) % 16 != 0 || reinterpret_cast<uintptr_t>(in1) % 16 != 0 ||
+               reinterpret_cast<uintptr_t>(g_in0) % 16 != 0 || reinterpret_cast<uintptr_t>(g_in1) % 16 != 0)
+                  ? "in0 / in1 / g_in0 / g_in1 are not 16-byte aligned"
+            : (reinterpret_cast<uintptr_t>(g_out0) % 2 != 0 || reinterpret_cast<uintptr_t>(g_out1) % 2 != 0)
+                  ? "g_out0 / g_out1 are not 2-byte aligned" : nullptr;
+        if (why)
+            return tpspp::fail(TPSPP_EINVAL, "tpspp_warp_bwd: TPSPP_IO_BF16 is served where dL/d input is finished in LDS (Ho*Wo "
+                               "<= 4096, input planes of at most 4096 pixels and a multiple of 8, 16-byte aligned images); "
+                               "here: %s", why);
+    }
     if (N == 0) return TPSPP_OK;
     hipStream_t st = tpspp::as_stream(stream);
     BwdParams P;
@@ -870,7 +959,68 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
     // transposed classic table --, so it excludes the one-launch form whether or not a score is given; the classic rectifier
     // never passes it: tps_pp_amd/tps_preprocessor.py.  Per call: TPSPP_BWD_TWO_KERNELS.)
     const bool two_kernels = (table_flags & TPSPP_BWD_TWO_KERNELS) != 0;
-    if (!in1 && !score && !p_xy && !fixed_point && !two_kernels && C0 <= 3 && F + 3 <= 24 &&
+    const bool io_bf16 = (table_flags & TPSPP_IO_BF16) != 0;
+    // kernel A'' for either element type: the grid, the workspace slices and the LDS are the same (the accumulators are 8
+    // bytes per element whatever the planes hold)
+    auto launch_lds2 = [&](auto io) {
+        constexpr bool BF16 = decltype(io)::value;
+        // channels per chunk: a chunk is worked off two planes at a time, so the LDS only ever holds two
+        const int cpt0 = 8, cpt1 = 8;
+        const int chunks0 = (C0 + cpt0 - 1) / cpt0, chunks1 = in1 ? (C1 + cpt1 - 1) / cpt1 : 0;
+        const int most = chunks0 > chunks1 ? chunks0 : chunks1;
+        const bool big = P.n > 1024;                        // 1024-thread workgroups, 4 pixels per thread
+        int G = ((big ? 1024 : 4096) + N * P.nin - 1) / (N * P.nin);      // ~16 (4) workgroups of 256 (1024) threads per CU
+        G = G < 1 ? 1 : (G > most ? most : G);
+        G = G > kBwdMaxG ? kBwdMaxG : G;
+        slots = G * P.nin;                                  // every slice is written by its workgroup (round 5: was 2 G with a
+                                                            // 26-MB memset of the unused half for single-input calls)
+        const size_t accb = 2 * 8 * (elems0 > elems1 ? elems0 : elems1);      // two planes x 8 bytes per element
+        const dim3 g2((unsigned)(G * P.nin), (unsigned)N);
+        auto go = [&](auto f64) {
+            constexpr bool F64 = decltype(f64)::value;
+#define TPSPP_LDS2(PPT, NT)                                                                                                  \
+            do {                                                                                                             \
+                if constexpr (BF16) hipLaunchKernelGGL((warp_bwd_sample_lds2_bf16_kernel<PPT, NT, F64>), g2, dim3(NT), accb, st, P, G, \
+                                             cpt0, cpt1, part, arrivals);                                                    \
+                else hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<PPT, NT, F64>), g2, dim3(NT), accb, st, P, G, cpt0,     \
+                                        cpt1, part, arrivals);                                                               \
+            } while (0)
+            if (P.n <= 256)       TPSPP_LDS2(1, 256);
+            else if (P.n <= 512)  TPSPP_LDS2(2, 256);
+            else if (P.n <= 1024) TPSPP_LDS2(4, 256);
+            else                  TPSPP_LDS2(4, 1024);
+#undef TPSPP_LDS2
+        };
+        if (fixed_point) go(std::false_type{});
+        else go(std::true_type{});
+        arrivals_zeroed = true;
+    };
+    if (io_bf16) {
+        // the one-launch form: the fp32 form's conditions with the image staged at TWO bytes per pixel.  LDS = the fp64
+        // accumulators of all planes (8 bytes per element); it must also hold the staged image plus the W0 + 1 elements a
+        // masked tap may read behind it (2 bytes each) and, later, dL/d grid (8 bytes per output pixel); the image is
+        // staged in 16-byte pieces (elems0 % 8 == 0 and in0 aligned: checked before the N == 0 return), g_in0 leaves in 4-byte pieces.
+        const size_t lds = (size_t)C0 * elems0 * 8;
+        if (!in1 && !score && !p_xy && !fixed_point && !two_kernels && C0 <= 3 && F + 3 <= 24 &&
+            p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && P.n % 4 == 0 &&
+            P.n > 1024 && lds <= 78 * 1024 && lds >= (size_t)P.n * 8 && lds >= ((size_t)C0 * elems0 + W0 + 1) * 2) {
+            auto go = [&](auto cc) {
+                constexpr int CC = decltype(cc)::value;
+                static bool attr_done[tpspp::kMaxDevices] = {};
+                if (tpspp::first_use_on_device(attr_done)) {
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&warp_bwd_classic_bf16_kernel<CC>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024);
+                    (void)hipGetLastError();
+                }
+                hipLaunchKernelGGL(warp_bwd_classic_bf16_kernel<CC>, dim3((unsigned)N), dim3(kClassicNT), lds, st, P, g_grid_ws);
+            };
+            if (C0 == 1) go(std::integral_constant<int, 1>{});
+            else if (C0 == 2) go(std::integral_constant<int, 2>{});
+            else go(std::integral_constant<int, 3>{});
+            return tpspp::check_launch("tpspp_warp_bwd(classic, bf16 planes)");
+        }
+        launch_lds2(std::true_type{});
+    } else if (!in1 && !score && !p_xy && !fixed_point && !two_kernels && C0 <= 3 && F + 3 <= 24 &&
         p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && P.n % 4 == 0 &&
         P.n > 1024 && P.n <= 4096 && (size_t)C0 * plane0 * 2 <= 78 * 1024 && (size_t)C0 * plane0 * 2 >= (size_t)P.n * 8 &&
         (size_t)C0 * plane0 * 2 >= (size_t)C0 * plane0 + ((size_t)W0 + 1) * 4 &&
@@ -890,31 +1040,9 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
         else if (C0 == 2) go(std::integral_constant<int, 2>{});
         else go(std::integral_constant<int, 3>{});
         return tpspp::check_launch("tpspp_warp_bwd(classic)");
-    }
-    if (P.n <= 4096 && plane0 <= kLds2 && plane1 <= kLds2 && plane0 % 16 == 0 && plane1 % 16 == 0 &&
+    } else if (P.n <= 4096 && plane0 <= kLds2 && plane1 <= kLds2 && plane0 % 16 == 0 && plane1 % 16 == 0 &&
         (!g_in0 || reinterpret_cast<uintptr_t>(g_in0) % 16 == 0) && (!g_in1 || reinterpret_cast<uintptr_t>(g_in1) % 16 == 0)) {
-        // channels per chunk: a chunk is worked off two planes at a time, so the LDS only ever holds two
-        const int cpt0 = 8, cpt1 = 8;
-        const int chunks0 = (C0 + cpt0 - 1) / cpt0, chunks1 = in1 ? (C1 + cpt1 - 1) / cpt1 : 0;
-        const int most = chunks0 > chunks1 ? chunks0 : chunks1;
-        const bool big = P.n > 1024;                        // 1024-thread workgroups, 4 pixels per thread
-        int G = ((big ? 1024 : 4096) + N * P.nin - 1) / (N * P.nin);      // ~16 (4) workgroups of 256 (1024) threads per CU
-        G = G < 1 ? 1 : (G > most ? most : G);
-        G = G > kBwdMaxG ? kBwdMaxG : G;
-        slots = G * P.nin;                                  // every slice is written by its workgroup (round 5: was 2 G with a
-                                                            // 26-MB memset of the unused half for single-input calls)
-        const size_t accb = 2 * 2 * (plane0 > plane1 ? plane0 : plane1);      // two planes x 8 bytes per element
-        const dim3 g2((unsigned)(G * P.nin), (unsigned)N);
-        auto go = [&](auto f64) {
-            constexpr bool F64 = decltype(f64)::value;
-            if (P.n <= 256)       hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<1, 256, F64>), g2, block, accb, st, P, G, cpt0, cpt1, part, arrivals);
-            else if (P.n <= 512)  hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<2, 256, F64>), g2, block, accb, st, P, G, cpt0, cpt1, part, arrivals);
-            else if (P.n <= 1024) hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<4, 256, F64>), g2, block, accb, st, P, G, cpt0, cpt1, part, arrivals);
-            else                  hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<4, 1024, F64>), g2, dim3(1024), accb, st, P, G, cpt0, cpt1, part, arrivals);
-        };
-        if (fixed_point) go(std::false_type{});
-        else go(std::true_type{});
-        arrivals_zeroed = true;
+        launch_lds2(std::false_type{});
     } else {
     if (hipMemsetAsync(g_grid_ws, 0, (size_t)N * P.n * 2 * sizeof(float), st) != hipSuccess)
         return tpspp::check_launch("tpspp_warp_bwd(memset)");

@@ -720,6 +720,18 @@ class EncodeDecodeRecognizer(nn.Module):
                 part.set_train_backend(val)
         return self
 
+    def set_train_io_dtype(self, dtype):
+        """None or torch.bfloat16 for the rectifier this recogniser owns (`TPS_PP.set_train_io_dtype` of `tpsnet`,
+        `TPSPreprocessor.set_train_io_dtype` of `preprocessor`): bf16 maps / images and gradients through the
+        transformation stage of the training graph.  The stages around it keep their dtype (they widen what they are
+        handed).  No effect on the eval path."""
+        owned = [m for m in (self.tpsnet, self.preprocessor) if m is not None and hasattr(m, "set_train_io_dtype")]
+        if not owned and dtype is not None:
+            raise ValueError("set_train_io_dtype: this recogniser owns no rectifier with a bf16 training path")
+        for m in owned:
+            m.set_train_io_dtype(dtype)
+        return self
+
     def extract_feat(self, img, test=False, **kwargs):
         if self.preprocessor is not None:
             img = self.preprocessor(img)

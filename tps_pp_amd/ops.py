@@ -1480,8 +1480,18 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
     reproducible from run to run; the default fp64 LDS atomics keep every term's bits but their sum depends on arrival
     order, so two runs may differ by one fp32 ulp at rounding ties (include/tpspp.h).  `two_kernels=True`
     (TPSPP_BWD_TWO_KERNELS, this call only): the sampling + parameter kernels even where the classic rectifier's one-launch
-    form would run."""
-    g_out0, in0 = _chk("g_out0", g_out0, 4), _chk("in0", in0, 4)
+    form would run.
+    The images and the output gradients are all float32 or all bfloat16 (TPSPP_IO_BF16; mixed dtypes raise TypeError before
+    anything else is looked at): g_in0 / g_in1 come back in the images' dtype, g_ctrl / g_score, the grid, the tables and
+    all accumulation stay fp32.  bfloat16 is served where dL/d input is finished in LDS (include/tpspp.h); any other
+    shape raises with the library's message."""
+    io_dtype = in0.dtype if isinstance(in0, torch.Tensor) else None
+    for nm, t in (("g_out0", g_out0), ("in1", in1), ("g_out1", g_out1)):
+        if isinstance(t, torch.Tensor) and t.dtype != io_dtype:
+            raise TypeError(f"warp_backward: in0 / in1 / g_out0 / g_out1 must share their dtype (all float32 or all "
+                            f"bfloat16); in0 is {io_dtype}, {nm} is {t.dtype}")
+    io = (torch.bfloat16,) if io_dtype == torch.bfloat16 else _F32
+    g_out0, in0 = _chk("g_out0", g_out0, 4, io), _chk("in0", in0, 4, io)
     grid, ctrl = _chk("grid", grid, 3), _chk("ctrl", ctrl, 3)
     inv_delta_C, P_hat = _chk("inv_delta_C", inv_delta_C, 2), _chk("P_hat", P_hat, 2)
     N, C0, H0, W0 = in0.shape
@@ -1490,7 +1500,8 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
     n = Ho * Wo
     if tuple(g_out0.shape) != (N, C0, Ho, Wo) or tuple(grid.shape) != (N, n, 2):
         raise ValueError("warp_backward: g_out0 / grid shape")
-    flags = (BWD_FIXED_POINT if fixed_point else 0) | (BWD_TWO_KERNELS if two_kernels else 0)
+    flags = (BWD_FIXED_POINT if fixed_point else 0) | (BWD_TWO_KERNELS if two_kernels else 0) | \
+        (IO_BF16 if io_dtype == torch.bfloat16 else 0)
     g_score = None
     if score is not None:
         score, transposed = _chk_score("warp_backward", score, N, n, F)
@@ -1503,7 +1514,7 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
         P_hat_t = _chk("P_hat_t", P_hat_t, 2)
     C1 = H1 = W1 = 0
     if in1 is not None:
-        in1, g_out1 = _chk("in1", in1, 4), _chk("g_out1", g_out1, 4)
+        in1, g_out1 = _chk("in1", in1, 4, io), _chk("g_out1", g_out1, 4, io)
         _, C1, H1, W1 = in1.shape
         if tuple(g_out1.shape) != (N, C1, Ho, Wo):
             raise ValueError("warp_backward: g_out1 shape")
@@ -1526,10 +1537,21 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
 
 class _WarpFunction(torch.autograd.Function):
     """Differentiable `warp`: HIP forward (`tpspp_warp_fwd`) and HIP backward (`tpspp_warp_bwd`).  The tables
-    (inv_delta_C, P_hat, P_xy) are constants of the module and get no gradient."""
+    (inv_delta_C, P_hat, P_xy) are constants of the module and get no gradient.  bfloat16 in0 (and in1): the bf16 forward
+    (its grid output is fp32, with the bits the fp32 forward gives for the same control points) and the bf16 backward:
+    bf16 outputs, bf16 gradients to in0 / in1, fp32 gradients to ctrl / score."""
 
     @staticmethod
     def forward(ctx, in0, ctrl, score, in1, inv_delta_C, P_hat, P_xy, P_hat_t, out_hw, table_flags):
+        if isinstance(in0, torch.Tensor) and in0.dtype == torch.bfloat16 and in0.is_cuda:
+            # a geometry the bf16 backward refuses raises here, with the library's message, not in the middle of .backward():
+            # tpspp_warp_bwd checks it before its N == 0 return (no launch; the pointers only stand in for their alignment)
+            H1, W1 = (int(in1.shape[2]), int(in1.shape[3])) if in1 is not None else (0, 0)
+            a, b = in0.data_ptr(), _ptr(in1)
+            rc = _lib.lib().tpspp_warp_bwd(a, a, 1, int(in0.shape[2]), int(in0.shape[3]), b, b, 1 if in1 is not None else 0,
+                                           H1, W1, a, a, a, a, 64, 0, 0, 0, IO_BF16, 0, 1, int(out_hw[0]), int(out_hw[1]),
+                                           a, b, a, 0, a, 0, 0)
+            _lib.check(rc, "tpspp_warp_bwd")
         out0, out1, grid, _ = warp(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=P_xy, score=score, in1=in1,
                                    want_grid=True, P_hat_t=P_hat_t, table_flags=table_flags)
         ctx.out_hw = out_hw
@@ -1544,21 +1566,23 @@ class _WarpFunction(torch.autograd.Function):
         in0, ctrl, score, in1, inv_delta_C, P_hat, P_xy, P_hat_t, grid = ctx.saved_tensors
         g0 = g[0]
         g1 = g[1] if len(g) > 1 else None
+        # (a missing or differently typed output gradient takes the images' dtype: bf16 images give and take bf16 gradients)
         if g0 is None:
-            g0 = torch.zeros((in0.shape[0], in0.shape[1]) + tuple(ctx.out_hw), device=in0.device)
+            g0 = torch.zeros((in0.shape[0], in0.shape[1]) + tuple(ctx.out_hw), device=in0.device, dtype=in0.dtype)
         if in1 is not None and g1 is None:
-            g1 = torch.zeros((in1.shape[0], in1.shape[1]) + tuple(ctx.out_hw), device=in0.device)
+            g1 = torch.zeros((in1.shape[0], in1.shape[1]) + tuple(ctx.out_hw), device=in0.device, dtype=in0.dtype)
         need = ctx.needs_input_grad
         g_in0, g_in1, g_ctrl, g_score = warp_backward(
-            g0.float(), in0, grid, ctrl, inv_delta_C, P_hat, ctx.out_hw, P_xy=P_xy, score=score, in1=in1,
-            g_out1=None if g1 is None else g1.float(), P_hat_t=P_hat_t, need_in0=need[0],
+            g0.to(in0.dtype), in0, grid, ctrl, inv_delta_C, P_hat, ctx.out_hw, P_xy=P_xy, score=score, in1=in1,
+            g_out1=None if g1 is None else g1.to(in0.dtype), P_hat_t=P_hat_t, need_in0=need[0],
             need_in1=need[3], need_score=need[2])
         return (g_in0, g_ctrl if need[1] else None, g_score, g_in1, None, None, None, None, None, None)
 
 
 def warp_autograd(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None, P_hat_t=None,
                   table_flags=0):
-    """`warp` inside an autograd graph: returns out0 or (out0, out1); gradients flow to in0, ctrl, score, in1."""
+    """`warp` inside an autograd graph: returns out0 or (out0, out1); gradients flow to in0, ctrl, score, in1.
+    bfloat16 in0 / in1 stay bfloat16 in both directions (no fp32 copy of the images, the outputs or their gradients)."""
     return _WarpFunction.apply(in0, ctrl, score, in1, inv_delta_C, P_hat, P_xy, P_hat_t,
                                (int(out_hw[0]), int(out_hw[1])), int(table_flags))
 

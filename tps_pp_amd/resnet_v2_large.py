@@ -100,6 +100,12 @@ class BasicBlock(nn.Module):
         return ops.conv2d([out], c2, self.conv2.stride, True, residual=residual, res_mode=2)
 
 
+def _widen_bf16(t):
+    """The training blocks work in their parameters' dtype: a bf16 `tpsnet` output (`TPS_PP.set_train_io_dtype`) is widened,
+    anything else passes as it is."""
+    return t.float() if t.dtype == torch.bfloat16 else t
+
+
 @BACKBONES.register_module()
 class ResNetABI_v2_large(TrainBackendMixin, nn.Module):
     """`resnet_v2_large.py:25-196`."""
@@ -188,7 +194,7 @@ class ResNetABI_v2_large(TrainBackendMixin, nn.Module):
             n = names[id(blk)]
             cws = (self._train_cw(f"{n}.conv1", blk.conv1), self._train_cw(f"{n}.conv2", blk.conv2),
                    self._train_cw(f"{n}.downsample.0", blk.downsample[0]) if blk.downsample is not None else None)
-            return ops.bn_block_autograd(t, blk, cws, name=n)
+            return ops.bn_block_autograd(_widen_bf16(t), blk, cws, name=n)
 
         return self._run(x, tpsnet, stem, block, **kwargs)
 
@@ -260,4 +266,4 @@ class ResNetABI_v2_large(TrainBackendMixin, nn.Module):
     def _forward_torch(self, x, tpsnet=None, **kwargs):
         """Plain PyTorch composition of the same layers: the TRAINING graph and the host-side tests' reference."""
         return self._run(x, tpsnet, lambda t: self.relu1(self.bn1(self.conv1(t))),
-                         lambda blk, t, inner: blk._forward_torch(t), **kwargs)
+                         lambda blk, t, inner: blk._forward_torch(_widen_bf16(t)), **kwargs)

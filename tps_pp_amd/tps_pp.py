@@ -667,6 +667,22 @@ class TPS_PP(TrainBackendMixin, nn.Module):
         three.  Touches neither the parameters, the state_dict nor the eval path."""
         return super().set_train_backend(mode)
 
+    def set_train_io_dtype(self, dtype):
+        """Opt-in dtype of the transformation stage in the graph-building forward (`.train()`, or inputs that carry
+        gradients).  None (the default): fp32 images, outputs and gradients, as before.  torch.bfloat16: `feat_grid` and
+        `batch_img` reach `ops.warp_autograd` as bf16, `output` / `mp_img` come back bf16 and the warp's backward reads and
+        writes bf16 (TPSPP_IO_BF16 of tpspp_warp_fwd / tpspp_warp_bwd: no fp32 copy of the maps or their gradients); the
+        control-point regressor still gets fp32 inputs and produces fp32 control points and score on every train backend.
+        A geometry the bf16 backward does not serve raises at forward with the library's message."""
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError("set_train_io_dtype: None or torch.bfloat16")
+        self._train_io_dtype = dtype
+        return self
+
+    @property
+    def train_io_dtype(self):
+        return getattr(self, "_train_io_dtype", None)
+
     def _train_conv(self, name, mod, srcs, stride):
         """One ConvModule (conv + in-place ReLU) on `ops.conv2d_autograd`; the forward's weight layouts are cached
         per layer and rebuilt on the device when the parameters change (`_prepared`, which also names the blind spot
@@ -744,12 +760,13 @@ class TPS_PP(TrainBackendMixin, nn.Module):
             return control_point, torch.zeros((n, de.shape[2] * de.shape[3], T.num_fiducial), device=de.device)
         return control_point, ops.score_autograd(de, en_feat, T).transpose(1, 2)
 
-    def _forward_autograd(self, batch_img, outs):
+    def _forward_autograd(self, batch_img, outs, warp_img=None):
         """Training graph: the transformation stage runs on the HIP kernels in both
         directions (`ops.warp_autograd`: tpspp_warp_fwd / tpspp_warp_bwd); the control-point regressor is the
         composition of the same layers, its convolutions on PyTorch's kernels (train backend "torch", the default) or
         on the HIP forward / backward kernels (`set_train_backend("hip")`), so autograd reaches its parameters.  GPU
-        tensors only."""
+        tensors only.  `warp_img` (set_train_io_dtype(torch.bfloat16)): the caller's image in bf16; the warp then takes it
+        and a bf16 `feat_grid`, the regressor above still ran on the fp32 `batch_img`."""
         ops.require_gpu(batch_img, "TPS_PP")
         if self.train_backend in ("hip", "hip_all"):
             control_point, atten_score, feat_grid = self._regress_train_hip(batch_img, outs,
@@ -758,9 +775,13 @@ class TPS_PP(TrainBackendMixin, nn.Module):
             control_point, atten_score, feat_grid = self._regress_torch(batch_img, outs)
         at = self.atten_tps
         P_xy, P_hat_t = at.device_constants(batch_img.device)
-        output, mp_img = ops.warp_autograd(feat_grid.float(), control_point.float(), at.hat_C, at.P_hat,
+        if warp_img is not None:
+            feat_grid, batch_img = feat_grid.to(warp_img.dtype), warp_img
+        else:
+            feat_grid, batch_img = feat_grid.float(), batch_img.float()
+        output, mp_img = ops.warp_autograd(feat_grid, control_point.float(), at.hat_C, at.P_hat,
                                            self.rectified_img_size, P_xy=P_xy, score=atten_score.float(),
-                                           in1=batch_img.float(), P_hat_t=P_hat_t)
+                                           in1=batch_img, P_hat_t=P_hat_t)
         return {"output": output, "logits": None, "mp_img": mp_img, "pc_score": atten_score}
 
     def _inputs_want_grad(self, batch_img, outs):
@@ -805,6 +826,9 @@ class TPS_PP(TrainBackendMixin, nn.Module):
                         "all-HIP inference path (or set_train_backend(\"hip\") for the convolutions of training).")
                 self._logged_autograd = True
             self._check_geometry(batch_img, outs)
+            if self.train_io_dtype is not None:
+                return self._forward_autograd(batch_img.float(), [o.float() for o in outs],
+                                              warp_img=batch_img.to(self.train_io_dtype))
             return self._forward_autograd(batch_img.float(), [o.float() for o in outs])
         control_point, atten_score, feat_grid = self.regress(batch_img, outs)
         # (the score stays the transposed view of its (N, F, n) buffer: ops.warp reads it in place)

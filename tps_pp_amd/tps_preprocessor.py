@@ -157,6 +157,8 @@ class TPSPreprocessor(BasePreprocessor):
         init_cfg (dict or list[dict], optional): kept for config compatibility.
     """
 
+    train_io_dtype = None        # set_train_io_dtype
+
     def __init__(self, num_fiducial=20, img_size=(32, 100), rectified_img_size=(32, 100),
                  num_img_channel=1, init_cfg=None):
         super().__init__(init_cfg=init_cfg)
@@ -183,6 +185,17 @@ class TPSPreprocessor(BasePreprocessor):
             raise ValueError('set_compute_dtype: None, "bf16x3" or torch.bfloat16')
         self.io_dtype = torch.bfloat16 if mode == torch.bfloat16 else None
         self.LocalizationNetwork.compute_dtype = mode
+        return self
+
+    def set_train_io_dtype(self, dtype):
+        """Opt-in dtype of the image in the graph-building forward (`.train()`, or an input that carries gradients).
+        None (the default): fp32, as before.  torch.bfloat16: the image reaches `ops.warp_autograd` as bf16, the rectified
+        image comes back bf16 and the warp's backward reads and writes bf16 (TPSPP_IO_BF16 of tpspp_warp_fwd /
+        tpspp_warp_bwd); the localisation network still gets the fp32 image and produces fp32 control points.  A
+        geometry the bf16 kernels do not serve raises at forward with the library's message."""
+        if dtype is not None and dtype != torch.bfloat16:
+            raise ValueError("set_train_io_dtype: None or torch.bfloat16")
+        self.train_io_dtype = dtype
         return self
 
     def rectify(self, batch_img, batch_C_prime, want_grid=False, want_idx=False):
@@ -214,7 +227,8 @@ class TPSPreprocessor(BasePreprocessor):
             gg = self.GridGenerator
             P_hat_t, flags = gg.prepared_table()
             ctrl = self.LocalizationNetwork._forward_torch(batch_img.float())
-            return ops.warp_autograd(batch_img.float(), ctrl.float(), gg.inv_delta_C, gg.P_hat,
+            io = self.train_io_dtype
+            return ops.warp_autograd(batch_img.float() if io is None else batch_img.to(io), ctrl.float(), gg.inv_delta_C, gg.P_hat,
                                      self.rectified_img_size, P_hat_t=P_hat_t, table_flags=flags)
         if getattr(self, "io_dtype", None) == torch.bfloat16:
             ops.require_gpu(batch_img, "TPSPreprocessor")
