@@ -28,6 +28,8 @@ CASES = [
     (2, 1, 64, 256, 0.45),
     (1, 3, 64, 256, 0.45),      # the largest staged image: 96 KB
     (3, 3, 16, 64, 0.3),
+    (2, 1, 128, 256, 0.45),     # four workgroups per image
+    (1, 3, 96, 256, 0.45),      # three: the non-power-of-two division of the banded copy-out, 144 KB of LDS
 ]
 
 

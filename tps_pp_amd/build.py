@@ -23,7 +23,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", f"--offload-arch={ARCH}", "-ff
 
 
 # per-file extra flags: tpspp_warp_geo.hip without the SLP vectoriser (it packs the grid chains into v_pk_fma_f32: slower)
-EXTRA = {"tpspp_warp_geo.hip": ["-fno-slp-vectorize"], "tpspp_warp_geo_bf16.hip": ["-fno-slp-vectorize"]}
+EXTRA = {"tpspp_warp_geo.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

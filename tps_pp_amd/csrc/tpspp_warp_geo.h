@@ -27,19 +27,21 @@ namespace tpspp_geo {
 using namespace tpspp_dev;
 using tpspp_pair::gchar;
 using tpspp_pair::make_taps_lite;
-using tpspp_pair::perm_x;
-using tpspp_pair::perm_y;
+using tpspp_pair::mirror_vals;
 using tpspp_pair::store16_nt;
 using tpspp_pair::TapsLite;
 using tpspp_pair::v4f;
 using tpspp_pair::v4f_a4;
 using tpspp_pair::wait_flag_lds;
 
+// one record for both kernels: tps_warp_geo_kernel (fp32 planes) and tps_warp_geo_bf16_kernel (tpspp_warp_geo_bf16.h)
 struct GeoParams {
-    const float* in; const float* ctrl; const float* inv_delta_c;
+    const void* in;        // planes of float or of bf16 bits, (N, C, H, W)
+    const float* ctrl; const float* inv_delta_c;
     const float* packed;   // pack_img_table_kernel layout for (QP, BW, CG) below, thread order of the WHOLE quadrant
     int N;
-    float* out; float* grid; int32_t* idx;
+    void* out;             // planes like `in`
+    float* grid; int32_t* idx;   // optional, fp32 / int32 for either element
     int H, W;              // input = output size
     int BW, CG;            // pixel block width (32 / BW rows), column groups per half-row
     int RGB;               // row-group batches of the quadrant (a thread owns QP row groups of one batch)
@@ -50,10 +52,12 @@ struct GeoParams {
 
 // LDS floats in front of the images: T (2 K per image, padded to 4) + 4 flag words
 __host__ __device__ constexpr int geo_img_off(int K, int IMGS) { return ((2 * K * IMGS + 3) & ~3) + 4; }
-inline size_t geo_lds_bytes(int K, int C, int H, int W, int IMGS)
+// LDS bytes for EB-byte planes: T + flags | the images in whole 1-KB DMA pieces | what out-of-image taps of the last row may
+// read (the 2-byte planes have always carried 8 bytes more than that)
+inline size_t geo_lds_bytes(int K, int C, int H, int W, int IMGS, int EB)
 {
-    const int pieces = (IMGS * C * H * W * 4 + 1023) / 1024;
-    return (size_t)(geo_img_off(K, IMGS) + pieces * 256 + W + 4) * 4;   // + what out-of-image taps of the last row may read
+    const int pieces = (IMGS * C * H * W * EB + 1023) / 1024;
+    return (size_t)(geo_img_off(K, IMGS) + pieces * 256) * 4 + (size_t)(W + 4) * EB + (EB == 2 ? 8 : 0);
 }
 
 constexpr int kGeoAwait = 6;   // image B's requests start when <= 6 of a loader's requests for A are outstanding,
@@ -117,7 +121,7 @@ tps_warp_geo_kernel(const GeoParams P)
         const int total_bytes = (hasB ? 2 : 1) * img_elems * 4;
         const int pieces = (total_bytes + 1023) >> 10;
         const int PA = (img_elems * 4 + 1023) >> 10;         // pieces that hold bytes of image A
-        const char* src = reinterpret_cast<const char*>(P.in + (size_t)b0 * img_elems);
+        const char* src = reinterpret_cast<const char*>(static_cast<const float*>(P.in) + (size_t)b0 * img_elems);
         auto dma = [&](int piece) {
             int off = piece * 1024 + lane * 16;
             if (off >= total_bytes) off = 0;                 // tail lanes re-read a valid address (their bytes land in the pad)
@@ -213,19 +217,7 @@ tps_warp_geo_kernel(const GeoParams P)
 #pragma unroll
         for (int j = 0; j < QP; ++j) {
             float val[4];
-            if constexpr (q == 0) {
-                val[0] = val[1] = val[2] = val[3] = v[j][0];
-            } else if constexpr (q == 1) {                    // P.x flips under the x-mirror
-                val[0] = v[j][1]; val[1] = -v[j][1]; val[2] = v[j][1]; val[3] = -v[j][1];
-            } else if constexpr (q == 2) {                    // P.y flips under the y-mirror
-                val[0] = v[j][2]; val[1] = v[j][2]; val[2] = -v[j][2]; val[3] = -v[j][2];
-            } else {
-                constexpr int k = q - 3;
-                val[0] = v[j][3 + k];
-                val[1] = v[j][3 + perm_x<F>(k)];
-                val[2] = v[j][3 + perm_y<F>(k)];
-                val[3] = v[j][3 + perm_x<F>(perm_y<F>(k))];
-            }
+            mirror_vals<F, q>(v[j], val);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll

@@ -1,9 +1,13 @@
-// Launcher of the run-time-geometry in-place warp kernel (tpspp_warp_geo.h): geometry planning + the (C, QP, AUX)
-// instantiations.  Its own translation unit: compiled with -fno-slp-vectorize (tps_pp_amd/build.py) -- the vectoriser
-// packs the (x, y) pairs of the grid chains into v_pk_fma_f32, which is slower here (profiles/r04_warp_lab.txt: a
-// packed FMA occupies the SIMD for two passes and the kernel is bound by VALU time, not by issue slots).
+// Launcher of the run-time-geometry in-place warp kernels (tpspp_warp_geo.h, fp32 planes; tpspp_warp_geo_bf16.h, bf16
+// planes): one geometry planner + the (C, QP, AUX) instantiations of both.  Its own translation unit: compiled with
+// -fno-slp-vectorize (tps_pp_amd/build.py) -- the vectoriser packs the (x, y) pairs of the grid chains into v_pk_fma_f32,
+// which is slower here (profiles/r04_warp_lab.txt: a packed FMA occupies the SIMD for two passes and the kernel is bound by
+// VALU time, not by issue slots).
+#include <cassert>
+
 #include "tpspp_common.h"
 #include "tpspp_warp_geo.h"
+#include "tpspp_warp_geo_bf16.h"
 #include "tpspp_warp_span.h"
 #include "tpspp_warp_geo_launch.h"
 
@@ -167,32 +171,44 @@ void launch_span_aux(const tpspp_span::SpanParams& P, const SpanPlan& pl, hipStr
 int g_geo_pair = 1;          // lab knob: 0 = never an image pair per workgroup
 int g_geo_force_bands = 0;   // lab knob (tpspp_warp_set_tuning's `bands` with kernel_choice 7): 0 = heuristic
 
-bool plan_geo(int C, int H, int W, int F, Plan* p)
+// The decomposition for planes of EB bytes per pixel (4: fp32, 2: bf16): the table's QP (the packed table is shared by
+// both), the fewest bands whose workgroup fits the wavefront budget, one loader per ~40 KB.  bf16 planes: C in {1, 3}, one
+// image per workgroup, and the lab knobs are not consulted.  `why`: the condition that is not met (the bf16 dispatcher
+// prints it); the texts are worded for bf16 planes, the only caller that asks: an fp32 caller passes none.
+bool plan_geo(int EB, int C, int H, int W, int F, Plan* p, const char** why = nullptr)
 {
-    if (!(C == 1 || C == 3 || C == 4) || F != 20) return false;
+    const bool bf16 = EB == 2;
+    assert(!why || bf16);
+    auto refuse = [&](const char* msg) { if (why) *why = msg; return false; };
+    if (!(C == 1 || C == 3 || (C == 4 && !bf16))) return refuse("C0 must be 1 or 3");
+    if (F != 20) return refuse("F must be 20");
     const int QP = geo_qp(H, W);
-    if (QP == 0 || (H * W) % 4 != 0) return false;
+    // (the planes leave as 16-byte pieces: 4 fp32 or 8 bf16 pixels)
+    if (QP == 0 || (H * W) % (16 / EB) != 0) return refuse("no prepared table for this geometry (Ho % 16 == 0, Wo % 4 == 0)");
     p->QP = QP;
     p->BW = tpspp_img::img_block_w(W);
     const int BH = 32 / p->BW;
     p->CG = ((W / 2) + p->BW - 1) / p->BW;
     p->RGB = ((H / 2) / BH) / QP;
     p->imgs = 1;
-    p->lds = tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 1);
-    if (p->lds > 160 * 1024) return false;
+    p->lds = tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 1, EB);
+    if (p->lds > 160 * 1024) return refuse("the bf16 image does not fit the LDS (160 KB)");
     // loaders: one per ~40 KB of image; workgroup size: <= 16 wavefronts, <= 12 from QP = 3 on (register budget)
-    p->nload = (int)((size_t)C * H * W * 4 / (40 * 1024)) + 1;
+    p->nload = (int)((size_t)C * H * W * EB / (40 * 1024)) + 1;
     if (p->nload > 3) p->nload = 3;
     const int max_waves = QP >= 3 ? 12 : 16;
+    const int force_bands = bf16 ? 0 : g_geo_force_bands;
     bool found = false;
     for (int B = 1; B <= p->RGB && !found; ++B) {
         if (p->RGB % B) continue;
-        if (g_geo_force_bands > 0 && B != g_geo_force_bands && B < p->RGB) continue;
+        if (force_bands > 0 && B != force_bands && B < p->RGB) continue;
         const int nthr = p->CG * (p->RGB / B) * 32;
         const int NW = (nthr + kWave - 1) / kWave;
+        if (bf16 && ((p->RGB / B) * QP * BH * W) % 8 != 0) continue;   // a band's row range leaves in whole 16-byte pieces
         if (NW + p->nload <= max_waves && NW <= 13) { p->bands = B; p->nthr = nthr; p->NW = NW; found = true; }
     }
-    if (!found) return false;
+    if (!found) return refuse("no decomposition of the quadrant into workgroups");
+    if (bf16) return true;                                   // never an image pair
     // image pair per workgroup: one workgroup covers the quadrant, QP x C <= 6 results per mirror pixel (registers),
     // two images fit the LDS, and every loader has >= kGeoKB pieces of image B to issue behind image A's
     const int pieces1 = (C * H * W * 4) / 1024;
@@ -202,17 +218,20 @@ bool plan_geo(int C, int H, int W, int F, Plan* p)
     // (QP <= 2: launch_qp has the pair form for one and two quadrant pixels per thread only -- a plan that said "pair" for QP 3 / 4
     // was launched as the one-image kernel with the pair's LDS layout: 64x160 C = 1 faulted once its quadrant fitted one workgroup)
     if (g_geo_pair && p->bands == 1 && p->NW >= 2 && QP <= 2 && QP * C <= 6 && pieces1 / nload2 >= tpspp_geo::kGeoKB && p->NW + nload2 <= 16 &&
-        tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 2) <= 160 * 1024) {
+        tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 2, EB) <= 160 * 1024) {
         p->imgs = 2; p->nload = nload2;
-        p->lds = tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 2);
+        p->lds = tpspp_geo::geo_lds_bytes(F + 3, C, H, W, 2, EB);
     }
     return true;
 }
 
-template <int C, int QP, int IMGS, bool AUX>
+// E: the plane element, float or (bf16) unsigned short
+template <typename E, int C, int QP, int IMGS, bool AUX>
 void launch_one(const tpspp_geo::GeoParams& P, const Plan& pl, hipStream_t st)
 {
-    auto kern = tpspp_geo::tps_warp_geo_kernel<20, C, QP, IMGS, AUX>;
+    void (*kern)(const tpspp_geo::GeoParams);
+    if constexpr (sizeof(E) == 4) kern = tpspp_geo::tps_warp_geo_kernel<20, C, QP, IMGS, AUX>;
+    else kern = tpspp_geo::tps_warp_geo_bf16_kernel<20, C, QP, AUX>;
     static bool attr_done[kMaxDevices] = {};
     if (first_use_on_device(attr_done)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -222,24 +241,45 @@ void launch_one(const tpspp_geo::GeoParams& P, const Plan& pl, hipStream_t st)
     hipLaunchKernelGGL(kern, dim3(groups * (unsigned)pl.bands), dim3((unsigned)((pl.NW + pl.nload) * kWave)), pl.lds, st, P);
 }
 
-template <int C, int QP, int IMGS>
+template <typename E, int C, int QP, int IMGS>
 void launch_aux(const tpspp_geo::GeoParams& P, const Plan& pl, hipStream_t st)
 {
-    if (P.grid || P.idx) launch_one<C, QP, IMGS, true>(P, pl, st);
-    else launch_one<C, QP, IMGS, false>(P, pl, st);
+    if (P.grid || P.idx) launch_one<E, C, QP, IMGS, true>(P, pl, st);
+    else launch_one<E, C, QP, IMGS, false>(P, pl, st);
 }
 
-template <int C>
+template <typename E, int C>
 void launch_qp(const tpspp_geo::GeoParams& P, const Plan& pl, hipStream_t st)
 {
+    constexpr bool kPair = sizeof(E) == 4;                   // the pair form exists for fp32 planes only
     switch (pl.QP) {
-    case 1: if (pl.imgs == 2) launch_aux<C, 1, 2>(P, pl, st); else launch_aux<C, 1, 1>(P, pl, st); break;
+    case 1:
+        if constexpr (kPair) { if (pl.imgs == 2) { launch_aux<E, C, 1, 2>(P, pl, st); break; } }
+        launch_aux<E, C, 1, 1>(P, pl, st); break;
     case 2:
-        if constexpr (2 * C <= 6) { if (pl.imgs == 2) { launch_aux<C, 2, 2>(P, pl, st); break; } }
-        launch_aux<C, 2, 1>(P, pl, st); break;
-    case 3: launch_aux<C, 3, 1>(P, pl, st); break;
-    default: launch_aux<C, 4, 1>(P, pl, st); break;
+        if constexpr (kPair && 2 * C <= 6) { if (pl.imgs == 2) { launch_aux<E, C, 2, 2>(P, pl, st); break; } }
+        launch_aux<E, C, 2, 1>(P, pl, st); break;
+    case 3: launch_aux<E, C, 3, 1>(P, pl, st); break;
+    default: launch_aux<E, C, 4, 1>(P, pl, st); break;
     }
+}
+
+// plan + launch for planes of E
+template <typename E>
+bool launch_geo(int C, int H, int W, int F, const void* in, const float* ctrl, const float* inv_delta_c,
+                const float* packed, int N, void* out, float* grid, int32_t* idx, hipStream_t st)
+{
+    Plan pl;
+    if (!plan_geo((int)sizeof(E), C, H, W, F, &pl)) return false;
+    tpspp_geo::GeoParams P;
+    P.in = in; P.ctrl = ctrl; P.inv_delta_c = inv_delta_c; P.packed = packed; P.N = N;
+    P.out = out; P.grid = grid; P.idx = idx;
+    P.H = H; P.W = W; P.BW = pl.BW; P.CG = pl.CG; P.RGB = pl.RGB; P.bands = pl.bands; P.nthr = pl.nthr; P.NW = pl.NW;
+    P.img_off = tpspp_geo::geo_img_off(F + 3, pl.imgs);
+    if (C == 1) launch_qp<E, 1>(P, pl, st);
+    else if (C == 3) launch_qp<E, 3>(P, pl, st);
+    else if constexpr (sizeof(E) == 4) launch_qp<E, 4>(P, pl, st);
+    return true;
 }
 
 }  // namespace
@@ -250,7 +290,7 @@ void span_set_tuning(int bands, int gather, int lds_kb, int no_spec) { g_span_ba
 bool geo_kernel_single_workgroup(int C, int H, int W, int F)
 {
     Plan pl;
-    return plan_geo(C, H, W, F, &pl) && pl.bands == 1;
+    return plan_geo(4, C, H, W, F, &pl) && pl.bands == 1;
 }
 
 bool span_kernel_applicable(int C, int H, int W, int F)
@@ -281,23 +321,26 @@ bool launch_span_kernel(int C, int H, int W, int F, const float* in, const float
 bool geo_kernel_applicable(int C, int H, int W, int F)
 {
     Plan pl;
-    return plan_geo(C, H, W, F, &pl);
+    return plan_geo(4, C, H, W, F, &pl);
 }
 
 bool launch_geo_kernel(int C, int H, int W, int F, const float* in, const float* ctrl, const float* inv_delta_c,
                        const float* packed, int N, float* out, float* grid, int32_t* idx, hipStream_t st)
 {
+    return launch_geo<float>(C, H, W, F, in, ctrl, inv_delta_c, packed, N, out, grid, idx, st);
+}
+
+const char* geo_bf16_kernel_refusal(int C, int H, int W, int F)
+{
     Plan pl;
-    if (!plan_geo(C, H, W, F, &pl)) return false;
-    tpspp_geo::GeoParams P;
-    P.in = in; P.ctrl = ctrl; P.inv_delta_c = inv_delta_c; P.packed = packed; P.N = N;
-    P.out = out; P.grid = grid; P.idx = idx;
-    P.H = H; P.W = W; P.BW = pl.BW; P.CG = pl.CG; P.RGB = pl.RGB; P.bands = pl.bands; P.nthr = pl.nthr; P.NW = pl.NW;
-    P.img_off = tpspp_geo::geo_img_off(F + 3, pl.imgs);
-    if (C == 1) launch_qp<1>(P, pl, st);
-    else if (C == 3) launch_qp<3>(P, pl, st);
-    else launch_qp<4>(P, pl, st);
-    return true;
+    const char* why = nullptr;
+    return plan_geo(2, C, H, W, F, &pl, &why) ? nullptr : why;
+}
+
+bool launch_geo_bf16_kernel(int C, int H, int W, int F, const void* in, const float* ctrl, const float* inv_delta_c,
+                            const float* packed, int N, void* out, float* grid, int32_t* idx, hipStream_t st)
+{
+    return launch_geo<unsigned short>(C, H, W, F, in, ctrl, inv_delta_c, packed, N, out, grid, idx, st);
 }
 
 }  // namespace tpspp

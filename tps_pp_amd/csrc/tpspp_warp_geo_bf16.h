@@ -1,5 +1,6 @@
 // Classic-geometry warp with bf16 images in and out (TPSPP_IO_BF16 with the prepared table): the run-time-geometry in-place
-// kernel of tpspp_warp_geo.h, one image per workgroup, with both ends narrowed to bf16.
+// kernel of tpspp_warp_geo.h, one image per workgroup, with both ends narrowed to bf16.  Parameter record (GeoParams), LDS
+// byte count (geo_lds_bytes with 2-byte planes), planner and launchers are that kernel's (tpspp_warp_geo.hip).
 //
 // The arithmetic is that of the fp32 in-place kernels, unchanged: T rows and grid coordinates are the k-ascending fp32 FMA
 // chains from zero, the tap descriptors are make_taps_lite()'s, the four-tap blend is the same three fp32 FMAs behind one
@@ -20,47 +21,11 @@
 #pragma once
 #include "tpspp_warp_geo.h"
 
-namespace tpspp_geo16 {
-
-using namespace tpspp_dev;
-using tpspp_geo::geo_img_off;
-using tpspp_pair::gchar;
-using tpspp_pair::make_taps_lite;
-using tpspp_pair::perm_x;
-using tpspp_pair::perm_y;
-using tpspp_pair::store16_nt;
-using tpspp_pair::TapsLite;
-using tpspp_pair::v4f;
-using tpspp_pair::v4f_a4;
-using tpspp_pair::wait_flag_lds;
-
-struct Geo16Params {
-    const unsigned short* in;   // bf16 bits, (N, C, H, W)
-    const float* ctrl; const float* inv_delta_c;
-    const float* packed;        // pack_img_table_kernel layout for (QP, BW, CG) below, thread order of the WHOLE quadrant
-    int N;
-    unsigned short* out;        // bf16 bits, (N, C, H, W)
-    float* grid; int32_t* idx;  // optional, fp32 / int32 as without the flag
-    int H, W;                   // input = output size
-    int BW, CG;                 // pixel block width (32 / BW rows), column groups per half-row
-    int RGB;                    // row-group batches of the quadrant (a thread owns QP row groups of one batch)
-    int bands;                  // workgroups per image; each owns RGB / bands batches
-    int nthr, NW;               // compute threads / wavefronts per workgroup
-    int img_off;                // float offset of the staged image in LDS (behind T and the flags)
-};
-
-// LDS bytes: T + flags as in tpspp_warp_geo.h | the image in whole 1-KB DMA pieces | what out-of-image taps of the last row may read
-inline size_t geo16_lds_bytes(int K, int C, int H, int W)
-{
-    const int pieces = (C * H * W * 2 + 1023) / 1024;
-    return (size_t)(geo_img_off(K, 1) + pieces * 256) * 4 + (size_t)(W + 4) * 2 + 8;
-}
-
-template <int QP> constexpr int geo16_max_threads() { return QP >= 3 ? 768 : 1024; }
+namespace tpspp_geo {
 
 template <int F, int C, int QP, bool AUX>
-__global__ void __launch_bounds__(geo16_max_threads<QP>())
-tps_warp_geo_bf16_kernel(const Geo16Params P)
+__global__ void __launch_bounds__(geo_max_threads<QP>())
+tps_warp_geo_bf16_kernel(const GeoParams P)
 {
     constexpr int K = F + 3;
     const int H = P.H, W = P.W, HW = H * W, img_elems = C * HW;
@@ -102,7 +67,7 @@ tps_warp_geo_bf16_kernel(const Geo16Params P)
         const int lw = wv - NW;
         const int total_bytes = img_elems * 2;
         const int pieces = (total_bytes + 1023) >> 10;
-        const char* src = reinterpret_cast<const char*>(P.in + (size_t)b * img_elems);
+        const char* src = reinterpret_cast<const char*>(static_cast<const unsigned short*>(P.in) + (size_t)b * img_elems);
         // the flag operands live in registers BEFORE the first DMA, the update is inline asm (tpspp_warp_pair.h)
         unsigned fa = (unsigned)(size_t)(sFlag + 1);
         int one = 1;
@@ -176,19 +141,7 @@ tps_warp_geo_bf16_kernel(const Geo16Params P)
 #pragma unroll
         for (int j = 0; j < QP; ++j) {
             float val[4];
-            if constexpr (q == 0) {
-                val[0] = val[1] = val[2] = val[3] = v[j][0];
-            } else if constexpr (q == 1) {                    // P.x flips under the x-mirror
-                val[0] = v[j][1]; val[1] = -v[j][1]; val[2] = v[j][1]; val[3] = -v[j][1];
-            } else if constexpr (q == 2) {                    // P.y flips under the y-mirror
-                val[0] = v[j][2]; val[1] = v[j][2]; val[2] = -v[j][2]; val[3] = -v[j][2];
-            } else {
-                constexpr int k = q - 3;
-                val[0] = v[j][3 + k];
-                val[1] = v[j][3 + perm_x<F>(k)];
-                val[2] = v[j][3 + perm_y<F>(k)];
-                val[3] = v[j][3 + perm_x<F>(perm_y<F>(k))];
-            }
+            mirror_vals<F, q>(v[j], val);
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 gx[j][m] = fmaf(val[m], t.x, gx[j][m]);
@@ -326,4 +279,4 @@ tps_warp_geo_bf16_kernel(const Geo16Params P)
     }
 }
 
-}  // namespace tpspp_geo16
+}  // namespace tpspp_geo

@@ -119,6 +119,26 @@ __device__ __forceinline__ TapsLite make_taps_lite(float gx, float gy, int H, in
     return t;
 }
 
+// (tpspp_warp_geo.h, tpspp_warp_span.h) The table values of a quadrant pixel's four mirror pixels at chain step q, from its packed row
+// v_row = (1, x, y, U_0 .. U_{F-1}): the mirrors negate x / y and permute the control points.
+template <int F, int q>
+__device__ __forceinline__ void mirror_vals(const float* v_row, float (&val)[4])
+{
+    if constexpr (q == 0) {
+        val[0] = val[1] = val[2] = val[3] = v_row[0];
+    } else if constexpr (q == 1) {                            // P.x flips under the x-mirror
+        val[0] = v_row[1]; val[1] = -v_row[1]; val[2] = v_row[1]; val[3] = -v_row[1];
+    } else if constexpr (q == 2) {                            // P.y flips under the y-mirror
+        val[0] = v_row[2]; val[1] = v_row[2]; val[2] = -v_row[2]; val[3] = -v_row[2];
+    } else {
+        constexpr int k = q - 3;
+        val[0] = v_row[3 + k];
+        val[1] = v_row[3 + perm_x<F>(k)];
+        val[2] = v_row[3 + perm_y<F>(k)];
+        val[3] = v_row[3 + perm_x<F>(perm_y<F>(k))];
+    }
+}
+
 constexpr int kPairFlags = 4;   // flag words in front of the staged pair (a multiple of 4: the DMA target stays 16-byte aligned)
 constexpr int kPairLoaders = 3;
 constexpr int kPairAwait = 6;   // image B's requests start when <= 6 of a loader's requests for A are outstanding,

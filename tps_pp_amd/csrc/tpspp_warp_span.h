@@ -33,8 +33,7 @@ namespace tpspp_span {
 using namespace tpspp_dev;
 using tpspp_pair::gchar;
 using tpspp_pair::make_taps_lite;
-using tpspp_pair::perm_x;
-using tpspp_pair::perm_y;
+using tpspp_pair::mirror_vals;
 using tpspp_pair::store16_nt;
 using tpspp_pair::TapsLite;
 using tpspp_pair::v4f;
@@ -250,19 +249,7 @@ tps_warp_span_kernel(const SpanParams P)
         constexpr int q = decltype(qc)::value;
         const float2 t = sT[q];
         float val[4];
-        if constexpr (q == 0) {
-            val[0] = val[1] = val[2] = val[3] = v[0];
-        } else if constexpr (q == 1) {                        // P.x flips under the x-mirror
-            val[0] = v[1]; val[1] = -v[1]; val[2] = v[1]; val[3] = -v[1];
-        } else if constexpr (q == 2) {                        // P.y flips under the y-mirror
-            val[0] = v[2]; val[1] = v[2]; val[2] = -v[2]; val[3] = -v[2];
-        } else {
-            constexpr int k = q - 3;
-            val[0] = v[3 + k];
-            val[1] = v[3 + perm_x<F>(k)];
-            val[2] = v[3 + perm_y<F>(k)];
-            val[3] = v[3 + perm_x<F>(perm_y<F>(k))];
-        }
+        mirror_vals<F, q>(v, val);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             gx[m] = fmaf(val[m], t.x, gx[m]);
