@@ -138,8 +138,12 @@ def test_front_matches_pytorch_cpu(cuda):
 
 
 def test_point_stage_and_dgab_persistent_trips_match_small_batches(cuda):
-    """tpe_points runs one persistent workgroup per CU with two images per trip, the DGAB chain eight wavefronts per
-    workgroup walking 32-row tiles: a batch with several trips and an odd image count gives what slices of it give."""
+    """tpe_points runs one persistent workgroup per CU with two images per trip: N = 1031 is 516 pairs for 256 workgroups,
+    three trips with an odd image at the end, and gives what slices of it give.  The DGAB chain walks 32-row tiles, one per
+    wavefront and trip: at N = 37, C = 64 that is 1184 tiles, 148 workgroups of eight wavefronts against a grid cap of 256
+    (296 of four against 512 for the bf16 chain), so every wavefront makes a SINGLE trip; what this checks for DGAB is that
+    an image's result does not depend on its place in the batch or on the workgroup that takes it.  A second trip needs
+    N * C > 4096: tests/test_gpu_stage_primitives.py::test_dgab_second_trip_gives_what_slices_give runs (67, 64)."""
     torch.manual_seed(6)
     m = TPS_PP().eval().to(cuda)
     N = 1031
