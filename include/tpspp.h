@@ -50,7 +50,9 @@ extern "C" {
                                11: the train pipeline's augmentation kernel, declared in tpspp_augment.h:
                                   tpspp_augment_normalize_fwd;
                                12: no new entry point: tpspp_warp_fwd / tpspp_warp_plan_* accept TPSPP_IO_BF16 on a classic
-                                  call with the prepared table (bf16 images in and out on the in-place kernel) */
+                                  call with the prepared table (bf16 images in and out on the in-place kernel);
+                               (still 12): the CRNN recogniser's entry points are a unit of their own, crnn/tpspp_crnn.h, bound by
+                                  name; they change nothing declared here */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */

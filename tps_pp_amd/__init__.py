@@ -15,6 +15,8 @@ from .nrtr_modality_transformer import NRTRModalityTransform  # noqa: F401
 from .nrtr_head import (NRTREncoder, NRTRDecoder, AttnConvertor, BaseConvertor,  # noqa: F401
                         EncodeDecodeRecognizer, NRTR, TFEncoderLayer, TFDecoderLayer, MultiHeadAttention,
                         PositionwiseFeedForward, PositionalEncoding)
+from .crnn import VeryDeepVgg, BidirectionalLSTM, CRNNDecoder, CTCConvertor, CRNNNet  # noqa: F401
+from .losses import CTCLoss  # noqa: F401
 from .optim import Adam, AdamW, build_optimizer  # noqa: F401
 
 from .ocr_transforms import (PIPELINES, ResizeOCR, NormalizeOCR, OCRBatchPreprocessor,  # noqa: F401
@@ -28,4 +30,5 @@ __all__ = ["PIPELINES", "ResizeOCR", "NormalizeOCR", "OCRBatchPreprocessor", "OC
            "TPS_PP", "Attention_Enhanced_TPS", "ResNetABI_v2_large", "BasicBlock",
            "NRTRModalityTransform", "ENCODERS", "DECODERS", "CONVERTORS", "DETECTORS", "build_encoder",
            "build_decoder", "build_convertor", "build_detector", "NRTREncoder", "NRTRDecoder", "AttnConvertor",
-           "BaseConvertor", "EncodeDecodeRecognizer", "NRTR", "Adam", "AdamW", "build_optimizer"]
+           "BaseConvertor", "EncodeDecodeRecognizer", "NRTR", "VeryDeepVgg", "BidirectionalLSTM", "CRNNDecoder", "CTCConvertor",
+           "CRNNNet", "CTCLoss", "Adam", "AdamW", "build_optimizer"]

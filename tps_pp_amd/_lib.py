@@ -3,6 +3,11 @@ to the `{name: (argtypes, restype)}` of the functions it declares, `headers()` l
 header's names (tests/test_capi_symbols.py holds every header, this table and the shared object to each other).  A new
 entry point goes under the header that declares it; a new header is a new key.
 
+`_EXT_SIGNATURES` is a second table of the same form for the headers in sub-directories of include/ (keys are paths relative
+to include/, `ext_headers()` lists them): tests/test_capi_symbols.py pins `headers()` and the files directly under include/
+to the five headers above, so the CRNN unit is declared, bound and tested beside them (tests/test_crnn_host.py).
+`symbols()` and `lib()` serve both tables.
+
 The product has no fallback: if the library is missing or fails to load, importing an op raises.
 PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
 """
@@ -126,6 +131,14 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_augment_normalize_fwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _f], _i),
 }}
 
+# include/<sub-directory>/<header> -> {function: (argtypes, restype)}
+_EXT_SIGNATURES = {"crnn/tpspp_crnn.h": {     # the CRNN recogniser: rectangular max-pool, LSTM recurrence, CTC greedy decode
+    "tpspp_crnn_maxpool_fwd": ([_f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
+    "tpspp_crnn_lstm_fwd": ([_f, _f, _f, _i, _i, _i, _i, _f], _i),
+    "tpspp_crnn_lstm_plan": ([_i, _i, _i], _i),
+    "tpspp_crnn_ctc_decode": ([_f, _f, _i, _i, _i, _i, _f, _f, _f], _i),
+}}
+
 _lib = None
 
 
@@ -138,9 +151,14 @@ def headers():
     return list(_SIGNATURES)
 
 
+def ext_headers():
+    """Paths, relative to include/, of the headers in its sub-directories (the second table)."""
+    return list(_EXT_SIGNATURES)
+
+
 def symbols(header):
-    """Names include/<header> declares (kept in sync by tests/test_capi_symbols.py)."""
-    return sorted(_SIGNATURES[header])
+    """Names include/<header> declares (kept in sync by tests/test_capi_symbols.py and tests/test_crnn_host.py)."""
+    return sorted(_SIGNATURES[header] if header in _SIGNATURES else _EXT_SIGNATURES[header])
 
 
 def lib():
@@ -152,7 +170,7 @@ def lib():
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for table in _SIGNATURES.values():
+        for table in (*_SIGNATURES.values(), *_EXT_SIGNATURES.values()):
             for name, (argtypes, restype) in table.items():
                 fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
                 fn.argtypes = argtypes

@@ -31,8 +31,8 @@ def sources():
 
 
 def _public_headers():
-    inc = os.path.join(ROOT, "include")
-    return sorted(os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h"))
+    inc = os.path.join(ROOT, "include")      # with its sub-directories (include/crnn/tpspp_crnn.h)
+    return sorted(os.path.join(d, f) for d, _, files in os.walk(inc) for f in files if f.endswith(".h"))
 
 
 def _stale():

@@ -1,0 +1,329 @@
+"""The CRNN recogniser the classic TPS rectifier was written for (reference: configs/_base_/recog_models/crnn_tps.py):
+`CRNNNet` = `TPSPreprocessor` -> `VeryDeepVgg` -> `CRNNDecoder(rnn_flag=True)` (two `BidirectionalLSTM`) ->
+`CTCConvertor`, trained with `CTCLoss` (tps_pp_amd/losses.py).
+
+Mirrors of `backbones/very_deep_vgg.py`, `layers/lstm_layer.py`, `decoders/crnn_decoder.py`, `convertors/ctc.py` and
+`recognizer/crnn.py`: the same registry names, constructor arguments, sub-module names and hence `state_dict` keys.
+
+Which path a call takes is `LocalizationNetwork`'s rule.  `.eval()` on a GPU tensor that carries no gradient runs the HIP
+kernels: the 3x3 convolutions (BatchNorm folded) on `ops.conv2d`, the pools, the LSTM recurrence and the CTC decode on
+the kernels of include/crnn/tpspp_crnn.h, every Linear on `tpspp_mm_f32`; a CPU tensor raises.  `.train()`, or an input
+that requires grad, runs the PyTorch composition of the same layers (`nn.LSTM`, `nn.Linear`, `nn.Conv2d`): the model
+trains through PyTorch plus the HIP warp forward and backward of the preprocessor.
+
+Precision: the VGG and the decoder are exact fp32 in every mode.  `set_compute_dtype` of the recogniser keeps its
+meaning for the preprocessor (its localisation network) and leaves these modules alone: they have no bf16 variant.
+"""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as Fn
+
+from . import ops
+from ._prepared import prepared
+from .nrtr_head import BaseConvertor, EncodeDecodeRecognizer
+from .registry import BACKBONES, CONVERTORS, DECODERS, DETECTORS
+
+
+def _hip_path(module, x):
+    """LocalizationNetwork's rule: the HIP kernels unless the module trains or the input carries gradients."""
+    return not (module.training or (torch.is_grad_enabled() and x.requires_grad))
+
+
+@BACKBONES.register_module()
+class VeryDeepVgg(nn.Module):
+    """`backbones/very_deep_vgg.py`: seven convolutions (BatchNorm after 2, 4, 6), four max-pools, (N, C, 32, W) ->
+    (N, 512, 1, W / 4 + 1).
+
+    `leaky_relu=True` (the reference's default; crnn_tps.py sets False) has no HIP path: the convolution kernel's
+    epilogues are ReLU and GELU, so such a module always takes the PyTorch composition."""
+
+    def __init__(self, leaky_relu=True, input_channels=3, init_cfg=None):
+        super().__init__()
+        self.init_cfg = init_cfg
+        ks, ps = [3, 3, 3, 3, 3, 3, 2], [1, 1, 1, 1, 1, 1, 0]
+        nm = [64, 128, 256, 256, 512, 512, 512]
+        self.channels = nm
+        self.leaky_relu = leaky_relu
+        cnn = nn.Sequential()
+
+        def conv_relu(i, batch_normalization=False):
+            n_in = input_channels if i == 0 else nm[i - 1]
+            cnn.add_module(f"conv{i}", nn.Conv2d(n_in, nm[i], ks[i], 1, ps[i]))
+            if batch_normalization:
+                cnn.add_module(f"batchnorm{i}", nn.BatchNorm2d(nm[i]))
+            cnn.add_module(f"relu{i}", nn.LeakyReLU(0.2, inplace=True) if leaky_relu else nn.ReLU(True))
+
+        conv_relu(0)
+        cnn.add_module("pooling0", nn.MaxPool2d(2, 2))
+        conv_relu(1)
+        cnn.add_module("pooling1", nn.MaxPool2d(2, 2))
+        conv_relu(2, True)
+        conv_relu(3)
+        cnn.add_module("pooling2", nn.MaxPool2d((2, 2), (2, 1), (0, 1)))
+        conv_relu(4, True)
+        conv_relu(5)
+        cnn.add_module("pooling3", nn.MaxPool2d((2, 2), (2, 1), (0, 1)))
+        conv_relu(6, True)
+        self.cnn = cnn
+
+    def init_weights(self):
+        pass
+
+    def out_channels(self):
+        return self.channels[-1]
+
+    def _hip_weights(self):
+        """conv0-5 as they are (bias; BatchNorm of 2 and 4 folded) and conv6, the 2x2 valid convolution, as a 3x3 kernel
+        whose first row and first column are zero: at stride (2, 1) on the two-row map its "same" padding reads rows 0, 1
+        and columns x, x + 1 under the four real taps (`conv6`)."""
+        c = self.cnn
+        bns = {2: c.batchnorm2, 4: c.batchnorm4, 6: c.batchnorm6}
+        convs = [getattr(c, f"conv{i}") for i in range(7)]
+
+        def build():
+            out = []
+            for i, conv in enumerate(convs):
+                w, bn = conv.weight, bns.get(i)
+                if i == 6:
+                    w = Fn.pad(w.detach(), (1, 0, 1, 0))
+                out.append(ops.prep_conv_weight(w, bn=None if bn is None else ops.bn_tensors(bn), conv_bias=conv.bias,
+                                                eps=1e-5 if bn is None else bn.eps))
+            return out
+        return prepared(self, "vgg", convs + list(bns.values()), build)
+
+    @staticmethod
+    def conv6(x, cw):
+        """The 2x2 valid convolution + folded BatchNorm + ReLU of a (N, 512, 2, W) map -> (N, 512, 1, W - 1), a view of
+        the (N, 512, 1, W) map the zero-extended 3x3 kernel gives (its last column reads the right padding)."""
+        if x.shape[2] != 2:
+            raise ValueError(f"VeryDeepVgg: the HIP path needs an image height of 32 (a two-row map before conv6), got "
+                             f"{x.shape[2]} rows")
+        return ops.conv2d([x], cw, (2, 1), True)[:, :, :, :x.shape[3] - 1]
+
+    def forward(self, x):
+        if self.leaky_relu or not _hip_path(self, x):
+            return self.cnn(x)
+        ops.require_gpu(x, "VeryDeepVgg")
+        ops.warn_detached_once(self, "VeryDeepVgg")
+        cw = self._hip_weights()
+        x = x.float().contiguous()
+        x = ops.crnn_maxpool(ops.conv2d([x], cw[0], 1, True), 2, 2, 0)
+        x = ops.crnn_maxpool(ops.conv2d([x], cw[1], 1, True), 2, 2, 0)
+        x = ops.conv2d([ops.conv2d([x], cw[2], 1, True)], cw[3], 1, True)
+        x = ops.crnn_maxpool(x, (2, 2), (2, 1), (0, 1))
+        x = ops.conv2d([ops.conv2d([x], cw[4], 1, True)], cw[5], 1, True)
+        x = ops.crnn_maxpool(x, (2, 2), (2, 1), (0, 1))
+        return self.conv6(x, cw[6])
+
+    def _forward_torch(self, x):
+        """TEST HOOK: the PyTorch composition whatever the mode."""
+        return self.cnn(x)
+
+
+class BidirectionalLSTM(nn.Module):
+    """`layers/lstm_layer.py`: nn.LSTM(nIn, nHidden, bidirectional=True) and a Linear over its 2 nHidden outputs,
+    (T, N, nIn) -> (T, N, nOut).  The HIP path (nHidden = 256) is driven by `CRNNDecoder`, which also chooses the layouts."""
+
+    def __init__(self, nIn, nHidden, nOut):
+        super().__init__()
+        self.rnn = nn.LSTM(nIn, nHidden, bidirectional=True)
+        self.embedding = nn.Linear(nHidden * 2, nOut)
+
+    def _hip_weights(self):
+        """(w_ih of both directions (8 H, nIn), b_ih + b_hh of both (8 H), w_hh of both (2, 4 H, H))."""
+        r = self.rnn
+        return prepared(self, "lstm", [r], lambda: (
+            torch.cat([r.weight_ih_l0, r.weight_ih_l0_reverse]).detach().float().contiguous(),
+            torch.cat([r.bias_ih_l0 + r.bias_hh_l0, r.bias_ih_l0_reverse + r.bias_hh_l0_reverse]).detach().float().contiguous(),
+            torch.stack([r.weight_hh_l0, r.weight_hh_l0_reverse]).detach().float().contiguous()))
+
+    def recurrent_hip(self, x, desc, T, N, images_per_group=0):
+        """The LSTM of the token operand x (`desc` = (batch = T, rows = N, batch stride, row stride, k stride), as
+        `ops.linear_fwd` takes it) -> (T, N, 2 H): one product for the input pre-activations of all tokens and both
+        directions, then the recurrence kernel."""
+        if self.rnn.hidden_size != ops.CRNN_HIDDEN or self.rnn.num_layers != 1:
+            raise ValueError("BidirectionalLSTM: the HIP recurrence serves one layer of 256 hidden units")
+        w_ih, b, w_hh = self._hip_weights()
+        xg = ops.linear_fwd(x, desc, w_ih, b)                                  # (T N, 2 * 4 H)
+        return ops.crnn_lstm(xg.view(T, N, 2, 4 * ops.CRNN_HIDDEN), w_hh, images_per_group)
+
+    def forward(self, input):
+        if not _hip_path(self, input):
+            return self._forward_torch(input)
+        ops.require_gpu(input, "BidirectionalLSTM")
+        x = input.float().contiguous()
+        T, N, K = x.shape
+        rec = self.recurrent_hip(x, (T, N, N * K, K, 1), T, N)
+        emb = self.embedding
+        return ops.linear_fwd(rec, ops._dense(T * N, rec.shape[2]), emb.weight.detach(), emb.bias.detach()).view(T, N, -1)
+
+    def _forward_torch(self, input):
+        recurrent, _ = self.rnn(input)
+        T, b, h = recurrent.size()
+        return self.embedding(recurrent.view(T * b, h)).view(T, b, -1)
+
+
+@DECODERS.register_module()
+class CRNNDecoder(nn.Module):
+    """`decoders/crnn_decoder.py`: (N, C, 1, W) features -> (N, W, num_classes) raw logits, through two
+    `BidirectionalLSTM` (rnn_flag=True) or one 1x1 convolution.  Called as the mirror's decoders are:
+    `decoder(feat, out_enc, targets_dict, img_metas, train_mode)`."""
+
+    def __init__(self, in_channels=None, num_classes=None, rnn_flag=False, init_cfg=None, **kwargs):
+        super().__init__()
+        self.init_cfg = init_cfg
+        self.num_classes = num_classes
+        self.rnn_flag = rnn_flag
+        if rnn_flag:
+            self.decoder = nn.Sequential(BidirectionalLSTM(in_channels, 256, 256), BidirectionalLSTM(256, 256, num_classes))
+        else:
+            self.decoder = nn.Conv2d(in_channels, num_classes, kernel_size=1, stride=1)
+
+    def init_weights(self):
+        pass
+
+    def _forward_torch(self, feat):
+        """crnn_decoder.py:50-63 (einops' 'b c h w -> b c (h w)' is a reshape)."""
+        feat = feat.reshape(feat.size(0), feat.size(1), -1).unsqueeze(2)
+        if self.rnn_flag:
+            x = feat.squeeze(2).permute(2, 0, 1)                       # (W, N, C)
+            for layer in self.decoder:                                  # (Sequential.__call__ would apply each layer's own rule)
+                x = layer._forward_torch(x)
+            return x.permute(1, 0, 2).contiguous()
+        x = self.decoder(feat).permute(0, 3, 1, 2).contiguous()
+        n, w, c, h = x.size()
+        return x.view(n, w, c * h)
+
+    def _forward_hip(self, feat):
+        """No layout pass: the first input projection reads the (W, N, C) tokens out of the NCHW feature map through
+        tpspp_mm_f32's strides (a sliced map included), the last embedding writes (N, W, C) through them."""
+        N, C, H, W = feat.shape
+        if H != 1:
+            raise ValueError(f"CRNNDecoder: feature height must be 1, got {H}")
+        feat = feat.float()
+        if not self.rnn_flag:
+            conv = self.decoder
+            cw = prepared(self, "conv", [conv], lambda: ops.prep_conv_weight(conv.weight, conv_bias=conv.bias))
+            y = ops.conv2d([feat.contiguous()], cw, 1, False)          # (N, num_classes, 1, W)
+            return y.view(N, -1, W).permute(0, 2, 1).contiguous()
+        l0, l1 = self.decoder[0], self.decoder[1]
+        sn, sc, _, sw = feat.stride()
+        rec = l0.recurrent_hip(feat, (W, N, sw, sn, sc), W, N)         # token (t, n, c) = feat[n, c, 0, t]
+        e0 = l0.embedding
+        x = ops.linear_fwd(rec, ops._dense(W * N, rec.shape[2]), e0.weight.detach(), e0.bias.detach())     # (W N, 256)
+        K = x.shape[1]
+        rec = l1.recurrent_hip(x, (W, N, N * K, K, 1), W, N)
+        e1 = l1.embedding
+        O, K = e1.weight.shape
+        out = torch.empty((N, W, O), device=feat.device, dtype=torch.float32)
+        ops.mm(rec, (N * K, K, 1), e1.weight.detach(), (0, K, 1), out, (O, W * O, 1), W, N, O, K, bias=e1.bias.detach())
+        return out
+
+    def forward_train(self, feat, out_enc, targets_dict, img_metas):
+        if not _hip_path(self, feat):
+            return self._forward_torch(feat)
+        ops.require_gpu(feat, "CRNNDecoder")
+        ops.warn_detached_once(self, "CRNNDecoder")
+        return self._forward_hip(feat)
+
+    def forward_test(self, feat, out_enc, img_metas):
+        return self.forward_train(feat, out_enc, None, img_metas)
+
+    def forward(self, feat, out_enc=None, targets_dict=None, img_metas=None, train_mode=True):
+        self.train_mode = train_mode
+        if train_mode:
+            return self.forward_train(feat, out_enc, targets_dict, img_metas)
+        return self.forward_test(feat, out_enc, img_metas)
+
+
+@CONVERTORS.register_module()
+class CTCConvertor(BaseConvertor):
+    """`convertors/ctc.py`: <BLK> is class 0, <UKN> (with_unknown) the last; `tensor2idx` takes the per-position arg-max,
+    collapses runs and drops blanks over the first ceil(T valid_ratio) positions."""
+
+    def __init__(self, dict_type="DICT90", dict_file=None, dict_list=None, with_unknown=True, lower=False, **kwargs):
+        super().__init__(dict_type, dict_file, dict_list)
+        assert isinstance(with_unknown, bool)
+        assert isinstance(lower, bool)
+        self.with_unknown = with_unknown
+        self.lower = lower
+        self.update_dict()
+
+    def update_dict(self):
+        self.blank_idx = 0
+        self.idx2char.insert(0, "<BLK>")
+        self.unknown_idx = None
+        if self.with_unknown:
+            self.idx2char.append("<UKN>")
+            self.unknown_idx = len(self.idx2char) - 1
+        self.char2idx = {ch: i for i, ch in enumerate(self.idx2char)}
+
+    def str2tensor(self, strings):
+        assert isinstance(strings, list) and all(isinstance(s, str) for s in strings)
+        tensors = [torch.IntTensor(index) for index in self.str2idx(strings)]
+        return {"targets": tensors, "flatten_targets": torch.cat(tensors),
+                "target_lengths": torch.IntTensor([len(t) for t in tensors])}
+
+    @staticmethod
+    def _decode_lens(img_metas, T):
+        return [min(T, math.ceil(T * m.get("valid_ratio", 1.0))) for m in img_metas]
+
+    def _scan(self, output, img_metas):
+        """-> (idx (N, T) int with -1 at dropped positions, score (N, T) float32) on the host.  A GPU tensor: arg-max,
+        softmax probability and the scan in one kernel and ONE device->host copy; a CPU tensor: ctc.py:110-129 with
+        torch's softmax and topk."""
+        lens = self._decode_lens(img_metas, output.size(1))
+        output = output.detach()
+        if output.is_cuda:
+            return ops.crnn_ctc_decode(output.float(), lens, self.blank_idx)
+        value, index = Fn.softmax(output, dim=2).topk(1, dim=2)
+        pred, value = index[:, :, 0].numpy(), value[:, :, 0].numpy()
+        prev = np.concatenate([np.full((pred.shape[0], 1), self.blank_idx, pred.dtype), pred[:, :-1]], 1)
+        keep = (pred != prev) & (pred != self.blank_idx) & (np.arange(pred.shape[1])[None, :] < np.asarray(lens)[:, None])
+        return np.where(keep, pred, -1), np.where(keep, value, np.float32(0))
+
+    def tensor2idx(self, output, img_metas, topk=1, return_topk=False):
+        """ctc.py:86-143 -> (indexes, scores), or their top-k lists with `return_topk`.  topk == 1 on a GPU tensor runs
+        the HIP kernel; topk > 1 follows the reference on the host."""
+        assert isinstance(img_metas, list) and all(isinstance(m, dict) for m in img_metas)
+        assert len(img_metas) == output.size(0)
+        assert isinstance(topk, int) and topk >= 1
+        if topk == 1:
+            idx, val = self._scan(output, img_metas)
+            indexes = [row[row >= 0].tolist() for row in idx]
+            scores = [v[row >= 0].astype(np.float64).tolist() for row, v in zip(idx, val)]
+            if return_topk:
+                return [[[i] for i in r] for r in indexes], [[[s] for s in r] for r in scores]
+            return indexes, scores
+        lens = self._decode_lens(img_metas, output.size(1))
+        prob = Fn.softmax(output.detach().float(), dim=2).cpu()
+        batch_value, batch_idx = prob.topk(topk, dim=2)
+        indexes_topk, scores_topk = [], []
+        for b, decode_len in enumerate(lens):
+            pred = batch_idx[b, :, 0].tolist()
+            select, prev = [], self.blank_idx
+            for t in range(decode_len):
+                if pred[t] not in (prev, self.blank_idx):
+                    select.append(t)
+                prev = pred[t]
+            select = torch.LongTensor(select)
+            indexes_topk.append(batch_idx[b].index_select(0, select).numpy().tolist())
+            scores_topk.append(batch_value[b].index_select(0, select).numpy().tolist())
+        if return_topk:
+            return indexes_topk, scores_topk
+        return [[x[0] for x in r] for r in indexes_topk], [[x[0] for x in r] for r in scores_topk]
+
+    def tensor2str(self, output, img_metas=None):
+        """`idx2str(tensor2idx(output, img_metas)[0])` and the scores -> (strings, scores): what `simple_test` needs."""
+        if img_metas is None:
+            img_metas = [{} for _ in range(output.size(0))]
+        indexes, scores = self.tensor2idx(output, img_metas)
+        return self.idx2str(indexes), scores
+
+
+@DETECTORS.register_module()
+class CRNNNet(EncodeDecodeRecognizer):
+    """`recognizer/crnn.py`: the CTC-loss based recogniser."""

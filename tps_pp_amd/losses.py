@@ -7,6 +7,9 @@ Only `EncodeDecodeRecognizer.forward_train` -- the training graph of round 5 -- 
 (`ops.seq_cross_entropy_autograd`).  One function does the work; the two registered classes only fix how outputs and
 targets are aligned.  Everything else under the reference's `losses/` stays out of scope.
 """
+import math
+
+import torch
 import torch.nn as nn
 import torch.nn.functional as Fn
 
@@ -76,3 +79,42 @@ class TFLoss(_SequenceLoss):
 
 def build_loss(cfg):
     return LOSSES.build(cfg)
+
+
+@LOSSES.register_module()
+class CTCLoss(nn.Module):
+    """`losses/ctc_loss.py`: `log_softmax` over the classes and `nn.CTCLoss` on (T, N, C); flattened targets by default,
+    else targets padded with `blank` and input lengths from the valid ratios; target lengths clamped to 1 .. T.
+    -> {'loss_ctc': tensor}.  PyTorch's kernels: there is no HIP path (the `ignore_index` that `EncodeDecodeRecognizer` adds
+    to every loss config is accepted and unused, as in the reference)."""
+
+    def __init__(self, flatten=True, blank=0, reduction="mean", zero_infinity=False, **kwargs):
+        super().__init__()
+        assert isinstance(flatten, bool)
+        assert isinstance(blank, int)
+        assert isinstance(reduction, str)
+        assert isinstance(zero_infinity, bool)
+        self.flatten = flatten
+        self.blank = blank
+        self.ctc_loss = nn.CTCLoss(blank=blank, reduction=reduction, zero_infinity=zero_infinity)
+
+    def forward(self, outputs, targets_dict, img_metas=None):
+        valid_ratios = None
+        if img_metas is not None:
+            valid_ratios = [img_meta.get("valid_ratio", 1.0) for img_meta in img_metas]
+        outputs = torch.log_softmax(outputs, dim=2)
+        bsz, seq_len = outputs.size(0), outputs.size(1)
+        outputs_for_loss = outputs.permute(1, 0, 2).contiguous()          # (T, N, C)
+        if self.flatten:
+            targets = targets_dict["flatten_targets"]
+        else:
+            targets = torch.full(size=(bsz, seq_len), fill_value=self.blank, dtype=torch.long)
+            for idx, tensor in enumerate(targets_dict["targets"]):
+                valid_len = min(tensor.size(0), seq_len)
+                targets[idx, :valid_len] = tensor[:valid_len]
+        target_lengths = torch.clamp(targets_dict["target_lengths"], min=1, max=seq_len).long()
+        input_lengths = torch.full(size=(bsz,), fill_value=seq_len, dtype=torch.long)
+        if not self.flatten and valid_ratios is not None:
+            input_lengths = torch.Tensor([math.ceil(valid_ratio * seq_len) for valid_ratio in valid_ratios]).long()
+        # (the targets follow the logits' device: PyTorch's own GPU kernel wants them there; a no-op on the host)
+        return dict(loss_ctc=self.ctc_loss(outputs_for_loss, targets.to(outputs.device), input_lengths, target_lengths))

@@ -2968,3 +2968,94 @@ def decoder_layer_autograd(x, out_enc, lyr, key_mask=None, valid_len=None, drop_
     x = x + Fn.dropout(a, drop_p, drop_p > 0)
     f = ffn_block_autograd(x, lyr.mlp, lyr.norm3)
     return x + Fn.dropout(f, drop_p, drop_p > 0)
+
+
+# ---- the CRNN recogniser (include/crnn/tpspp_crnn.h, tpspp_crnn.hip) ---------------------------------------------------
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def crnn_maxpool(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
+    """nn.MaxPool2d(kernel, stride, padding) with rectangular stride / padding (`tpspp_crnn_maxpool_fwd`;
+    very_deep_vgg.py:51-60): padding counts as -inf, a NaN in a window gives NaN."""
+    x = _chk("crnn_maxpool input", x, 4)
+    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel), _pair(stride), _pair(padding)
+    N, C, H, W = x.shape
+    if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw:
+        raise ValueError(f"crnn_maxpool: kernel {(kh, kw)} / stride {(sh, sw)} / padding {(ph, pw)} on a {H} x {W} map")
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().tpspp_crnn_maxpool_fwd(_ptr(x), N, C, H, W, kh, kw, sh, sw, ph, pw, _ptr(out), Ho, Wo, _stream(x))
+    _lib.check(rc, "tpspp_crnn_maxpool_fwd")
+    return out
+
+
+CRNN_HIDDEN = 256
+CRNN_LSTM_GROUPS = (4, 8, 16)          # the accepted non-zero images_per_group of tpspp_crnn_lstm_fwd
+
+
+def crnn_lstm_plan(N, images_per_group=0, compute_units=0):
+    """`tpspp_crnn_lstm_plan`: the images per workgroup `crnn_lstm` uses (host only; compute_units 0: the current device's)."""
+    g = _lib.lib().tpspp_crnn_lstm_plan(int(N), int(images_per_group), int(compute_units))
+    _lib.check(min(g, 0), "tpspp_crnn_lstm_plan")
+    return g
+
+
+def crnn_lstm(xg, w_hh, images_per_group=0):
+    """The recurrence of one bidirectional nn.LSTM(., 256) layer with zero initial state (`tpspp_crnn_lstm_fwd`;
+    lstm_layer.py:14): xg (T, N, 2, 1024) input pre-activations of both directions, w_hh (2, 1024, 256) -> (T, N, 512)."""
+    xg, w_hh = _chk("crnn_lstm xg", xg, 4), _chk("crnn_lstm w_hh", w_hh, 3)
+    T, N = xg.shape[0], xg.shape[1]
+    if tuple(xg.shape[2:]) != (2, 4 * CRNN_HIDDEN) or tuple(w_hh.shape) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) \
+            or w_hh.device != xg.device:
+        raise ValueError(f"crnn_lstm: xg (T, N, 2, 1024) and w_hh (2, 1024, 256) on one device, got {tuple(xg.shape)}, "
+                         f"{tuple(w_hh.shape)}")
+    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    with torch.cuda.device(xg.device):
+        rc = _lib.lib().tpspp_crnn_lstm_fwd(_ptr(xg), _ptr(w_hh), _ptr(out), T, N, CRNN_HIDDEN, int(images_per_group),
+                                            _stream(xg))
+    _lib.check(rc, "tpspp_crnn_lstm_fwd")
+    return out
+
+
+def crnn_ctc_decode_device(logits, decode_len, blank=0):
+    """`tpspp_crnn_ctc_decode` into fresh device tensors: (idx (N, T) int32, -1 where the scan of ctc.py:119-129 drops the
+    position; score (N, T) float32, 0 there).  decode_len: (N) int32 on the logits' device."""
+    logits = _chk("crnn_ctc_decode logits", logits, 3)
+    N, T, C = logits.shape
+    decode_len = _chk("crnn_ctc_decode decode_len", decode_len, 1, (torch.int32,))
+    if decode_len.shape[0] != N or decode_len.device != logits.device:
+        raise ValueError("crnn_ctc_decode: decode_len must be (N) on the logits' device")
+    idx = torch.empty((N, T), device=logits.device, dtype=torch.int32)
+    score = torch.empty((N, T), device=logits.device, dtype=torch.float32)
+    if N == 0:
+        return idx, score
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().tpspp_crnn_ctc_decode(_ptr(logits), _ptr(decode_len), N, T, C, int(blank), _ptr(idx), _ptr(score),
+                                              _stream(logits))
+    _lib.check(rc, "tpspp_crnn_ctc_decode")
+    return idx, score
+
+
+def crnn_ctc_decode(logits, decode_len, blank=0):
+    """`tpspp_crnn_ctc_decode` + ONE device->host copy (as `attn_tensor2idx`): (idx (N, T) int32 numpy, score (N, T)
+    float32 numpy).  decode_len: a sequence of N ints (host); it travels in the same buffer as the outputs."""
+    logits = _chk("crnn_ctc_decode logits", logits, 3)
+    N, T, C = logits.shape
+    if len(decode_len) != N:
+        raise ValueError("crnn_ctc_decode: one decode_len per image")
+    # [idx (N*T) | score (N*T) as raw bits | decode_len (N)]: one int32 buffer, one copy back
+    buf = torch.empty((2 * N * T + N,), device=logits.device, dtype=torch.int32)
+    if N == 0:
+        z = buf.cpu().numpy()
+        return z.reshape(0, T), z.view("float32").reshape(0, T)
+    buf[2 * N * T:].copy_(torch.tensor([int(v) for v in decode_len], dtype=torch.int32))
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().tpspp_crnn_ctc_decode(_ptr(logits), buf.data_ptr() + 8 * N * T, N, T, C, int(blank), buf.data_ptr(),
+                                              buf.data_ptr() + 4 * N * T, _stream(logits))
+    _lib.check(rc, "tpspp_crnn_ctc_decode")
+    host = buf[:2 * N * T].cpu().numpy()
+    return host[:N * T].reshape(N, T), host[N * T:].view("float32").reshape(N, T)
