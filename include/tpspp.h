@@ -274,7 +274,9 @@ int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, int H0, int W0
  * cores (exact fp32 products, fp32 accumulation).
  *   src_ptrs[i]   (N, C_i, H_i, W_i); src_dims + 5*i = {C_i, H_i, W_i, uh_i, uw_i}: source i is
  *                 nearest-upsampled by (uh_i, uw_i) on the fly; all sources share the logical size;
- *                 with nsrc > 1 every C_i must be a multiple of 32 (1x1) / 8 (3x3)
+ *                 with nsrc > 1 every C_i must be a multiple of tpspp_conv_chunk_channels(K), 32 (1x1) / 4 (3x3):
+ *                 no kernel's channel chunk straddles two sources (the generic 3x3 kernel takes 8 channels per chunk
+ *                 where every source but the last holds a multiple of 8, and 4 per chunk otherwise)
  *   weight_t      (Cin*KH*KW, Cout) = the PyTorch weight (Cout, Cin, KH, KW) flattened and
  *                 transposed once by the caller (BatchNorm, if any, folded in): generic kernel
  *   weight_tiled  the same values arranged (chunk, tap, channel-in-chunk, cout) with
@@ -297,6 +299,23 @@ int tpspp_conv2d_fwd(const float* const* src_ptrs, const int* src_dims, int nsrc
                      const float* residual, const float* post_scale, const float* post_shift,
                      int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
                      float* out, int Ho, int Wo, tpspp_stream_t stream);
+
+/*
+ * The kernel tpspp_conv2d_fwd launches for these sizes (a host-side query: touches no device, works without one).
+ * Takes what the choice depends on: src_dims and nsrc as above, whether weight_t / weight_tiled are given (0 | 1), and
+ * the sizes; honours bit 0 of tpspp_conv_set_tuning.  Sizes the forward refuses are refused with the same negative code
+ * and the same tpspp_last_error text.  Otherwise a non-negative packed code:
+ *   bits 0-3   family: 0 generic (im2col chunks), 1 tiled, 2 wide (1x1, 128x128 tiles), 3 skinny (1x1, split K)
+ *   bits 4-7   kernel size, 1 or 3
+ *   generic:   bits 8-15  input channels per chunk (32 for 1x1; 8 for 3x3, or 4: see src_dims above)
+ *   skinny:    bits 8-15  wavefronts that split K (4, or 16 for Cin >= 256)
+ *   tiled:     bits 8-11 stride h, 12-15 stride w, 16-19 tile rows TH, 20-27 tile columns TW,
+ *              bit 28 images per tile - 1 (two images share a tile on maps of at most 4x16), bit 29 accumulators per
+ *              wavefront - 1 (one for Cout <= 32, two otherwise)
+ * (N = 0 launches nothing; the code is then the one a non-empty batch of these sizes would be judged by.)
+ */
+int tpspp_conv2d_route(const int* src_dims, int nsrc, int has_weight_t, int has_weight_tiled,
+                       int N, int Cout, int KH, int KW, int sh, int sw, int Ho, int Wo);
 
 /*
  * Backward of tpspp_conv2d_fwd with res_mode = 0 and no post-affine, i.e. of

@@ -43,23 +43,26 @@ CASES = [
     ("stem 3x3 3->32 @32x128 (folded BN)", [(3, 32, 128, 1, 1)], 32, 3, (1, 1), True, 0, 2),
     ("BasicBlock conv2 3x3 s2 + downsample residual", [(64, 32, 128, 1, 1)], 64, 3, (2, 2), True, 2, 2),
     ("localisation conv 3x3 3->64 @32x100 no bias", [(3, 32, 100, 1, 1)], 64, 3, (1, 1), False, 0, 2),
-    ("wide 1x1 64->256 odd pixels", [(64, 7, 9, 1, 1)], 256, 1, (1, 1), False, 0, 2),
+    ("skinny 1x1 64->256 odd pixels", [(64, 7, 9, 1, 1)], 256, 1, (1, 1), False, 0, 2),
     ("Cout not multiple of 64", [(16, 9, 13, 1, 1)], 40, 3, (1, 1), True, 0, 1),
     # 4x16 outputs (last backbone stage): 128-pixel tiles that span two images, odd batch
     ("two-image tile 3x3 64->64 @4x16", [(64, 4, 16, 1, 1)], 64, 3, (1, 1), True, 2, 3),
     ("two-image tile 3x3 s2 32->64 @8x32 -> 4x16", [(32, 8, 32, 1, 1)], 64, 3, (2, 2), True, 0, 5),
-    ("two-image tile 1x1 64->128 @4x16", [(64, 4, 16, 1, 1)], 128, 1, (1, 1), False, 1, 3),
+    ("skinny 1x1 64->128 @4x16 odd batch", [(64, 4, 16, 1, 1)], 128, 1, (1, 1), False, 1, 3),
     ("two-image tile 3x3 @2x16 two sources", [(8, 2, 16, 1, 1), (8, 1, 16, 2, 1)], 64, 3, (1, 1), True, 0, 4),
-    # large 1x1 GEMMs -> 128x128 tiles
+    # large 1x1 GEMMs: 128x128 tiles from 512 workgroups on, the 128x64 tiles below that (the second case), the skinny
+    # kernel below 256 workgroups of 128x64 (the third; `ops.conv2d_route` names the kernel, tests/test_conv_route_host.py
+    # holds these ids to it, tests/test_gpu_conv_routes.py reaches every kernel)
     ("wide 1x1 512->1536 one row of 8192", [(512, 1, 8192, 1, 1)], 1536, 1, (1, 1), False, 0, 1),
-    ("wide 1x1 256->512 gelu+res @16x64 x 8", [(256, 16, 64, 1, 1)], 512, 1, (1, 1), 2, 1, 8),
-    ("wide 1x1 K=40 Cout=132 ragged", [(40, 12, 44, 1, 1)], 132, 1, (1, 1), True, 2, 9),
+    ("tiled 2x64 1x1 256->512 gelu+res @16x64 x 8", [(256, 16, 64, 1, 1)], 512, 1, (1, 1), 2, 1, 8),
+    ("skinny 1x1 K=40 Cout=132 ragged", [(40, 12, 44, 1, 1)], 132, 1, (1, 1), True, 2, 9),
     # few output pixels -> split-K skinny kernel (decoder steps, batches of feature vectors)
     ("skinny 1x1 512->512 one row of 512", [(512, 1, 512, 1, 1)], 512, 1, (1, 1), False, 1, 1),
     ("skinny 1x1 512->92 ragged", [(512, 1, 77, 1, 1)], 92, 1, (1, 1), True, 0, 1),
     ("skinny 1x1 K=100 odd sizes", [(100, 3, 5, 1, 1)], 37, 1, (1, 1), True, 2, 3),
     ("skinny 1x1 K=6", [(6, 1, 40, 1, 1)], 8, 1, (1, 1), False, 0, 2),
-    # at most 32 output channels: the one-accumulator form of the tiled kernel (round 6)
+    # at most 32 output channels: the one-accumulator form of the tiled kernel (round 6; the 1x1 case starts too few
+    # workgroups for it and takes the skinny kernel, as `down0 1x1` above does)
     ("stem 3x3 3->32 @32x128", [(3, 32, 128, 1, 1)], 32, 3, (1, 1), True, 0, 2),
     ("BasicBlock 3x3 32->32 + residual @16x64", [(32, 16, 64, 1, 1)], 32, 3, (1, 1), True, 2, 3),
     ("3x3 s2 32->32 + residual, Cout=24 ragged", [(32, 16, 64, 1, 1)], 24, 3, (2, 2), True, 2, 3),
@@ -71,7 +74,7 @@ CASES = [
     ("downsample 1x1 s2 256->512 @8x32 -> 4x16 (two-image tile, odd batch)", [(256, 8, 32, 1, 1)], 512, 1, (2, 2), False, 0, 5),
     ("downsample 1x1 s2 64->128 @16x64 -> 8x32", [(64, 16, 64, 1, 1)], 128, 1, (2, 2), False, 0, 3),
     ("downsample 1x1 s2 32->32 @32x128 -> 16x64", [(32, 32, 128, 1, 1)], 32, 1, (2, 2), True, 0, 2),
-    ("downsample 1x1 s2 K=40 odd map 7x21 -> 4x11, Cout=36", [(40, 7, 21, 1, 1)], 36, 1, (2, 2), True, 2, 3),
+    ("downsample 1x1 s2 K=40 odd map 7x21 -> 4x11, Cout=36 (two-image tile)", [(40, 7, 21, 1, 1)], 36, 1, (2, 2), True, 2, 3),
 ]
 
 

@@ -16,7 +16,7 @@ _HOST = "reads and writes host memory only"
 _PLAN = "host-side bookkeeping of a prepared call; its launch is tpspp_warp_plan_run, which is swept"
 EXCLUDED = {
     "tpspp_abi_version": _QUERY, "tpspp_last_error": _QUERY, "tpspp_prepared_table_floats": _QUERY,
-    "tpspp_conv_chunk_channels": _QUERY, "tpspp_conv_bf16_chunk_channels": _QUERY,
+    "tpspp_conv_chunk_channels": _QUERY, "tpspp_conv_bf16_chunk_channels": _QUERY, "tpspp_conv2d_route": _QUERY,
     "tpspp_conv2d_bwd_weight_workspace_floats": _QUERY, "tpspp_linear_bwd_weight_workspace_floats": _QUERY,
     "tpspp_plane_ln_bwd_workspace_floats": _QUERY, "tpspp_cbam_bwd_workspace_floats": _QUERY,
     "tpspp_bn_stats_workspace_floats": _QUERY, "tpspp_bn_bwd_reduce_workspace_floats": _QUERY,

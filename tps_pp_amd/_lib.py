@@ -42,6 +42,7 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_warp_plan_run_on": ([_f, _f], _i),
     "tpspp_warp_plan_destroy": ([_f], None),
     "tpspp_conv2d_fwd": ([_f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
+    "tpspp_conv2d_route": ([_f] + [_i] * 11, _i),
     "tpspp_conv2d_bf16_fwd": ([_f, _f, _i, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _f], _i),
     "tpspp_conv2d_bwd_data": ([_f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f], _i),
     "tpspp_conv2d_bwd_weight_workspace_floats": ([_f, _i, _i, _i, _i, _i, _i, _i], ctypes.c_size_t),

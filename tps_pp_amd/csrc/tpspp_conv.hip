@@ -567,16 +567,6 @@ conv1x1_wide_f32_kernel(const ConvParams P)
     }
 }
 
-bool wide_applies(const ConvParams& P, int KH)
-{
-    if (KH != 1 || P.nsrc != 1 || P.sh != 1 || P.sw != 1) return false;
-    if (P.src[0].uh != 1 || P.src[0].uw != 1) return false;
-    const int HoWo = P.Ho * P.Wo;
-    if ((HoWo & 3) || (P.Cout & 3) || HoWo < BM || P.Cout < WBN) return false;
-    const long wgs = (long)((HoWo + BM - 1) / BM) * ((P.Cout + WBN - 1) / WBN) * P.N;
-    return wgs >= 512 && P.N <= 65535 && (P.Cout + WBN - 1) / WBN <= 65535;
-}
-
 void launch_wide(const ConvParams& P, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.Ho * P.Wo + BM - 1) / BM), (unsigned)((P.Cout + WBN - 1) / WBN), (unsigned)P.N);
@@ -823,74 +813,21 @@ conv1x1_skinny_ln_f32_kernel(const ConvParams P, const LnArgs L)
     }
 }
 
-// true when the 128x64 tiling would start fewer workgroups than the chip has CUs
-bool skinny_applies(const ConvParams& P, int KH)
-{
-    if (KH != 1 || P.nsrc != 1 || P.sh != 1 || P.sw != 1) return false;
-    if (P.src[0].uh != 1 || P.src[0].uw != 1) return false;
-    const long big = (long)((P.Ho * P.Wo + BM - 1) / BM) * ((P.Cout + BN - 1) / BN) * P.N;
-    return big < 256 && P.N <= 65535 && (P.Cout + 31) / 32 <= 65535;
-}
-
-void launch_skinny(const ConvParams& P, hipStream_t st)
+void launch_skinny(const ConvParams& P, int nw, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.Ho * P.Wo + 31) / 32), (unsigned)((P.Cout + 31) / 32), (unsigned)P.N);
-    if (P.Cin >= 256) hipLaunchKernelGGL(conv1x1_skinny_f32_kernel<16>, grid, dim3(16 * kWave), 0, st, P);
-    else              hipLaunchKernelGGL(conv1x1_skinny_f32_kernel<4>, grid, dim3(4 * kWave), 0, st, P);
+    if (nw == 16) hipLaunchKernelGGL(conv1x1_skinny_f32_kernel<16>, grid, dim3(16 * kWave), 0, st, P);
+    else          hipLaunchKernelGGL(conv1x1_skinny_f32_kernel<4>, grid, dim3(4 * kWave), 0, st, P);
 }
 
 template <int KH, int SH, int SW, int TH, int TW, int KC, int NI = 1>
-void launch_tiled(const ConvParams& P, hipStream_t st)
+void launch_tiled(const ConvParams& P, int nb, hipStream_t st)
 {
     const int ctiles = (P.Cout + BN - 1) / BN;
     const dim3 grid((unsigned)((P.Wo + TW - 1) / TW), (unsigned)((P.Ho + TH - 1) / TH),
                     (unsigned)(((P.N + NI - 1) / NI) * ctiles));
-    if (P.Cout <= 32) hipLaunchKernelGGL((conv_tiled_f32_kernel<KH, SH, SW, TH, TW, KC, NI, 1>), grid, dim3(kThreads), 0, st, P);
+    if (nb == 1) hipLaunchKernelGGL((conv_tiled_f32_kernel<KH, SH, SW, TH, TW, KC, NI, 1>), grid, dim3(kThreads), 0, st, P);
     else hipLaunchKernelGGL((conv_tiled_f32_kernel<KH, SH, SW, TH, TW, KC, NI>), grid, dim3(kThreads), 0, st, P);
-}
-
-// picks a tile for the output width; returns false when no tiled instantiation fits
-bool launch_tiled_any(const ConvParams& P, int KH, hipStream_t st)
-{
-    if ((P.Cout % 4) != 0) return false;                          // float4 weight rows
-    if ((long)P.N * ((P.Cout + BN - 1) / BN) > 65535) return false;
-#define TPSPP_TILE(KHv, SHv, SWv, THv, TWv, KCv) { launch_tiled<KHv, SHv, SWv, THv, TWv, KCv>(P, st); return true; }
-#define TPSPP_TILE2(KHv, SHv, SWv, THv, TWv, KCv) { launch_tiled<KHv, SHv, SWv, THv, TWv, KCv, 2>(P, st); return true; }
-    // small maps (the last backbone stage: 4x16 outputs): a 128-pixel tile spans TWO images instead of
-    // leaving half of its rows empty
-    const bool small_map = P.Ho <= 4 && P.Wo <= 16 && P.N >= 2;
-    if (KH == 1) {
-        // strided 1x1 (the backbone's downsample branches; round 6): the tiled kernel, staging only the pixels the layer uses
-        // (TileCfg), instead of the im2col kernel -- 256 -> 512 on 8x32 -> 4x16 maps ran at 27 TFLOP/s there
-        if (P.sh == 2 && P.sw == 2) {
-            if (small_map) TPSPP_TILE2(1, 2, 2, 4, 16, 32)
-            if (P.Wo >= 64) TPSPP_TILE(1, 2, 2, 2, 64, 32)
-            if (P.Wo >= 32) TPSPP_TILE(1, 2, 2, 4, 32, 32)
-            TPSPP_TILE(1, 2, 2, 8, 16, 32)
-        }
-        if (P.sh != 1 || P.sw != 1) return false;
-        if (small_map) TPSPP_TILE2(1, 1, 1, 4, 16, 32)
-        if (P.Wo >= 128) TPSPP_TILE(1, 1, 1, 1, 128, 32)
-        if (P.Wo >= 64) TPSPP_TILE(1, 1, 1, 2, 64, 32)
-        if (P.Wo >= 32) TPSPP_TILE(1, 1, 1, 4, 32, 32)
-        TPSPP_TILE(1, 1, 1, 8, 16, 32)
-    }
-    if (small_map && P.sh == 1 && P.sw == 1) TPSPP_TILE2(3, 1, 1, 4, 16, kKC3)
-    if (small_map && P.sh == 2 && P.sw == 2) TPSPP_TILE2(3, 2, 2, 4, 16, kKC3)
-    if (P.sh == 1 && P.sw == 1) {
-        if (P.Wo >= 64) TPSPP_TILE(3, 1, 1, 2, 64, kKC3)
-        if (P.Wo >= 32) TPSPP_TILE(3, 1, 1, 4, 32, kKC3)
-        TPSPP_TILE(3, 1, 1, 8, 16, kKC3)
-    }
-    if (P.sh == 2 && P.sw == 2) {
-        if (P.Wo >= 64) TPSPP_TILE(3, 2, 2, 2, 64, kKC3)
-        if (P.Wo >= 32) TPSPP_TILE(3, 2, 2, 4, 32, kKC3)
-        TPSPP_TILE(3, 2, 2, 8, 16, kKC3)
-    }
-    if (P.sh == 2 && P.sw == 1) TPSPP_TILE(3, 2, 1, 8, 16, kKC3)
-#undef TPSPP_TILE
-#undef TPSPP_TILE2
-    return false;
 }
 
 template <int KH, int KW, int KC>
@@ -898,6 +835,157 @@ void launch_conv(const ConvParams& P, hipStream_t st)
 {
     const dim3 grid((unsigned)((P.Ho * P.Wo + BM - 1) / BM), (unsigned)((P.Cout + BN - 1) / BN), (unsigned)P.N);
     hipLaunchKernelGGL((conv_igemm_f32_kernel<KH, KW, KC>), grid, dim3(kThreads), 0, st, P);
+}
+
+// ---- the route: which kernel a call takes, as a value ------------------------------------------------------------------
+// conv_shape() holds every argument check that depends on sizes alone, conv_route() every dispatch condition and
+// launch_route() one launch per value: tpspp_conv2d_fwd and tpspp_conv2d_route (a host-side query, so that a test can name
+// the kernel it is about to run) go through the same two functions.
+enum { kGeneric = 0, kTiled = 1, kWide = 2, kSkinny = 3 };
+
+struct ConvShape {            // what the dispatch decides on
+    int nsrc;
+    int C[3], H[3], W[3], uh[3], uw[3];
+    int N, Cin, Cout, KH, sh, sw, Hi, Wi, Ho, Wo;
+    bool has_wt, has_tiled;
+};
+
+struct ConvRoute {
+    int family;               // kGeneric / kTiled / kWide / kSkinny
+    int kh;                   // kernel size, 1 or 3
+    int sh, sw, th, tw;       // tiled: the instantiation's strides and output tile
+    int ni, nb;               // tiled: images per tile (1 | 2), accumulators per wavefront (1 | 2)
+    int nw;                   // skinny: wavefronts that split K (4 | 16)
+    int kc;                   // generic: input channels per chunk (32 | 8 | kKC3)
+};
+
+constexpr int kKCG3 = 8;      // channels per chunk of the generic 3x3 kernel ...
+// ... unless a chunk of 8 would straddle two concatenated sources (the kernel takes a whole chunk from the source its first
+// channel lies in): then the same kernel with kKC3 channels per chunk, the granularity the argument check admits
+static_assert(kKCG3 % kKC3 == 0, "a source of a multiple of 8 channels must hold whole chunks of kKC3 as well");
+
+int conv_shape(const int* src_dims, int nsrc, bool has_wt, bool has_tiled, int N, int Cout, int KH, int KW, int sh, int sw,
+               int Ho, int Wo, ConvShape& S)
+{
+    TPSPP_REQUIRE(src_dims && (has_wt || has_tiled), "tpspp_conv2d_fwd: null pointer");
+    TPSPP_REQUIRE(nsrc >= 1 && nsrc <= 3, "tpspp_conv2d_fwd: 1..3 sources");
+    TPSPP_REQUIRE((KH == 1 && KW == 1) || (KH == 3 && KW == 3), "tpspp_conv2d_fwd: kernel must be 1x1 or 3x3");
+    TPSPP_REQUIRE(N >= 0 && Cout > 0 && sh >= 1 && sw >= 1 && Ho > 0 && Wo > 0, "tpspp_conv2d_fwd: bad sizes");
+    TPSPP_REQUIRE(N <= 65535 && (Cout + BN - 1) / BN <= 65535, "tpspp_conv2d_fwd: grid too large");
+    S.nsrc = nsrc;
+    int cin = 0, Hi = -1, Wi = -1;
+    const int KC = (KH == 1) ? 32 : kKC3;
+    for (int i = 0; i < nsrc; ++i) {
+        const int* d = src_dims + 5 * i;                      // C, H, W, uh, uw
+        TPSPP_REQUIRE(d[0] > 0 && d[1] > 0 && d[2] > 0 && d[3] >= 1 && d[4] >= 1, "tpspp_conv2d_fwd: bad source %d", i);
+        TPSPP_REQUIRE(nsrc == 1 || d[0] % KC == 0,
+                      "tpspp_conv2d_fwd: concatenated sources need channel counts that are multiples of %d", KC);
+        S.C[i] = d[0]; S.H[i] = d[1]; S.W[i] = d[2]; S.uh[i] = d[3]; S.uw[i] = d[4];
+        const int lh = d[1] * d[3], lw = d[2] * d[4];
+        TPSPP_REQUIRE(Hi < 0 || (Hi == lh && Wi == lw), "tpspp_conv2d_fwd: sources disagree on the logical size");
+        Hi = lh; Wi = lw;
+        cin += d[0];
+    }
+    S.Cin = cin; S.Cout = Cout; S.N = N; S.KH = KH; S.Hi = Hi; S.Wi = Wi; S.Ho = Ho; S.Wo = Wo; S.sh = sh; S.sw = sw;
+    S.has_wt = has_wt; S.has_tiled = has_tiled;
+    const int ph = (KH - 1) / 2, pw = (KW - 1) / 2;
+    TPSPP_REQUIRE(Ho == (Hi + 2 * ph - KH) / sh + 1 && Wo == (Wi + 2 * pw - KW) / sw + 1,
+                  "tpspp_conv2d_fwd: output size does not match input size / stride ('same' padding)");
+    return TPSPP_OK;
+}
+
+// a single 1x1 stride-1 source at full resolution: a plain GEMM, what the skinny and the wide kernel take
+bool plain_gemm(const ConvShape& S)
+{
+    return S.KH == 1 && S.nsrc == 1 && S.sh == 1 && S.sw == 1 && S.uh[0] == 1 && S.uw[0] == 1;
+}
+
+// true when the 128x64 tiling would start fewer workgroups than the chip has CUs
+bool skinny_applies(const ConvShape& S)
+{
+    if (!plain_gemm(S)) return false;
+    const long big = (long)((S.Ho * S.Wo + BM - 1) / BM) * ((S.Cout + BN - 1) / BN) * S.N;
+    return big < 256 && S.N <= 65535 && (S.Cout + 31) / 32 <= 65535;
+}
+
+bool wide_applies(const ConvShape& S)
+{
+    if (!plain_gemm(S)) return false;
+    const int HoWo = S.Ho * S.Wo;
+    if ((HoWo & 3) || (S.Cout & 3) || HoWo < BM || S.Cout < WBN) return false;
+    const long wgs = (long)((HoWo + BM - 1) / BM) * ((S.Cout + WBN - 1) / WBN) * S.N;
+    return wgs >= 512 && S.N <= 65535 && (S.Cout + WBN - 1) / WBN <= 65535;
+}
+
+// picks a tile for the strides and the output width; false when no tiled instantiation fits
+bool tile_applies(const ConvShape& S, ConvRoute& R)
+{
+    if ((S.Cout % 4) != 0) return false;                          // float4 weight rows
+    if ((long)S.N * ((S.Cout + BN - 1) / BN) > 65535) return false;
+    const bool s11 = S.sh == 1 && S.sw == 1, s22 = S.sh == 2 && S.sw == 2;
+    auto tile = [&](int th, int tw, int ni) {
+        R.sh = S.sh; R.sw = S.sw; R.th = th; R.tw = tw; R.ni = ni;
+        R.nb = S.Cout <= 32 ? 1 : 2;       // at most 32 output channels: the second accumulator would multiply zeros
+        return true;
+    };
+    if (!s11 && !s22)                                             // (2,1): the 3x3 kernel alone, one tile
+        return S.KH == 3 && S.sh == 2 && S.sw == 1 ? tile(8, 16, 1) : false;
+    // small maps (the last backbone stage: 4x16 outputs): a 128-pixel tile spans TWO images instead of
+    // leaving half of its rows empty
+    if (S.Ho <= 4 && S.Wo <= 16 && S.N >= 2) return tile(4, 16, 2);
+    if (S.KH == 1 && s11 && S.Wo >= 128) return tile(1, 128, 1);
+    if (S.Wo >= 64) return tile(2, 64, 1);
+    if (S.Wo >= 32) return tile(4, 32, 1);
+    return tile(8, 16, 1);
+}
+
+int conv_route(const ConvShape& S, bool force_generic, ConvRoute& R)
+{
+    R = ConvRoute{kGeneric, S.KH, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!force_generic) {
+        if (skinny_applies(S)) { R.family = kSkinny; R.nw = S.Cin >= 256 ? 16 : 4; return TPSPP_OK; }
+        if (wide_applies(S)) { R.family = kWide; return TPSPP_OK; }
+        if (S.has_tiled && tile_applies(S, R)) { R.family = kTiled; return TPSPP_OK; }
+    }
+    TPSPP_REQUIRE(S.has_wt, "tpspp_conv2d_fwd: shape needs the generic kernel but weight_t is NULL");
+    R.kc = S.KH == 1 ? 32 : kKCG3;
+    if (S.KH == 3)
+        for (int i = 0; i + 1 < S.nsrc; ++i)
+            if (S.C[i] % kKCG3 != 0) R.kc = kKC3;
+    return TPSPP_OK;
+}
+
+// the 18 tiles: kernel, stride (h, w), tile (h, w), channels per chunk, images per tile; each with one or two accumulators.
+// (strided 1x1 -- the backbone's downsample branches; round 6 -- stages only the pixels the layer uses: TileCfg)
+#define TPSPP_CONV_TILES(X)                                                                                     \
+    X(1, 1, 1, 4, 16, 32, 2) X(1, 1, 1, 1, 128, 32, 1) X(1, 1, 1, 2, 64, 32, 1) X(1, 1, 1, 4, 32, 32, 1)        \
+    X(1, 1, 1, 8, 16, 32, 1)                                                                                    \
+    X(1, 2, 2, 4, 16, 32, 2) X(1, 2, 2, 2, 64, 32, 1) X(1, 2, 2, 4, 32, 32, 1) X(1, 2, 2, 8, 16, 32, 1)         \
+    X(3, 1, 1, 4, 16, kKC3, 2) X(3, 1, 1, 2, 64, kKC3, 1) X(3, 1, 1, 4, 32, kKC3, 1) X(3, 1, 1, 8, 16, kKC3, 1) \
+    X(3, 2, 2, 4, 16, kKC3, 2) X(3, 2, 2, 2, 64, kKC3, 1) X(3, 2, 2, 4, 32, kKC3, 1) X(3, 2, 2, 8, 16, kKC3, 1) \
+    X(3, 2, 1, 8, 16, kKC3, 1)
+
+// one launch per route value; false when the value names no kernel (a defect of conv_route, reported by the caller)
+bool launch_route(const ConvRoute& R, const ConvParams& P, hipStream_t st)
+{
+    switch (R.family) {
+    case kSkinny: launch_skinny(P, R.nw, st); return true;
+    case kWide: launch_wide(P, st); return true;
+    case kTiled:
+#define TPSPP_TILE(KHv, SHv, SWv, THv, TWv, KCv, NIv)                                                       \
+        if (R.kh == KHv && R.sh == SHv && R.sw == SWv && R.th == THv && R.tw == TWv && R.ni == NIv) {       \
+            launch_tiled<KHv, SHv, SWv, THv, TWv, KCv, NIv>(P, R.nb, st);                                   \
+            return true;                                                                                    \
+        }
+        TPSPP_CONV_TILES(TPSPP_TILE)
+#undef TPSPP_TILE
+        return false;
+    default:
+        if (R.kh == 1) launch_conv<1, 1, 32>(P, st);
+        else if (R.kc == kKCG3) launch_conv<3, 3, kKCG3>(P, st);
+        else launch_conv<3, 3, kKC3>(P, st);
+        return true;
+    }
 }
 
 int g_conv_force_generic = 0;
@@ -919,6 +1007,21 @@ TPSPP_EXPORT int tpspp_conv_chunk_channels(int kernel_size)
     return kernel_size == 1 ? 32 : kKC3;
 }
 
+TPSPP_EXPORT int tpspp_conv2d_route(const int* src_dims, int nsrc, int has_weight_t, int has_weight_tiled,
+                                    int N, int Cout, int KH, int KW, int sh, int sw, int Ho, int Wo)
+{
+    ConvShape S;
+    ConvRoute R;
+    if (int rc = conv_shape(src_dims, nsrc, has_weight_t != 0, has_weight_tiled != 0, N, Cout, KH, KW, sh, sw, Ho, Wo, S)) return rc;
+    if (int rc = conv_route(S, g_conv_force_generic != 0, R)) return rc;
+    int code = R.family | (R.kh << 4);
+    if (R.family == kTiled)
+        code |= (R.sh << 8) | (R.sw << 12) | (R.th << 16) | (R.tw << 20) | ((R.ni - 1) << 28) | ((R.nb - 1) << 29);
+    else if (R.family == kSkinny) code |= R.nw << 8;
+    else if (R.family == kGeneric) code |= R.kc << 8;
+    return code;
+}
+
 TPSPP_EXPORT int tpspp_conv2d_fwd(const float* const* src_ptrs, const int* src_dims, int nsrc,
                                   const float* weight_t, const float* weight_tiled, const float* bias,
                                   const float* residual, const float* post_scale, const float* post_shift,
@@ -926,62 +1029,36 @@ TPSPP_EXPORT int tpspp_conv2d_fwd(const float* const* src_ptrs, const int* src_d
                                   float* out, int Ho, int Wo, tpspp_stream_t stream)
 {
     TPSPP_REQUIRE(src_ptrs && src_dims && (weight_t || weight_tiled) && out, "tpspp_conv2d_fwd: null pointer");
-    TPSPP_REQUIRE(nsrc >= 1 && nsrc <= 3, "tpspp_conv2d_fwd: 1..3 sources");
-    TPSPP_REQUIRE((KH == 1 && KW == 1) || (KH == 3 && KW == 3), "tpspp_conv2d_fwd: kernel must be 1x1 or 3x3");
-    TPSPP_REQUIRE(N >= 0 && Cout > 0 && sh >= 1 && sw >= 1 && Ho > 0 && Wo > 0, "tpspp_conv2d_fwd: bad sizes");
     TPSPP_REQUIRE(res_mode >= 0 && res_mode <= 2 && (res_mode == 0) == (residual == nullptr),
                   "tpspp_conv2d_fwd: residual / res_mode mismatch");
-    TPSPP_REQUIRE(N <= 65535 && (Cout + BN - 1) / BN <= 65535, "tpspp_conv2d_fwd: grid too large");
+    TPSPP_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "tpspp_conv2d_fwd: post_scale/post_shift come together");
+    TPSPP_REQUIRE(relu >= 0 && relu <= 2, "tpspp_conv2d_fwd: activation code must be 0 (none), 1 (ReLU) or 2 (GELU)");
+    ConvShape S;
+    if (int rc = conv_shape(src_dims, nsrc, weight_t != nullptr, weight_tiled != nullptr, N, Cout, KH, KW, sh, sw, Ho, Wo, S))
+        return rc;
     ConvParams P;
     P.nsrc = nsrc;
-    int cin = 0, Hi = -1, Wi = -1;
-    const int KC = (KH == 1) ? 32 : kKC3;
     for (int i = 0; i < nsrc; ++i) {
-        const int* d = src_dims + 5 * i;                      // C, H, W, uh, uw
-        TPSPP_REQUIRE(src_ptrs[i] && d[0] > 0 && d[1] > 0 && d[2] > 0 && d[3] >= 1 && d[4] >= 1,
-                      "tpspp_conv2d_fwd: bad source %d", i);
-        TPSPP_REQUIRE(nsrc == 1 || d[0] % KC == 0,
-                      "tpspp_conv2d_fwd: concatenated sources need channel counts that are multiples of %d", KC);
+        TPSPP_REQUIRE(src_ptrs[i], "tpspp_conv2d_fwd: bad source %d", i);
         P.src[i].p = src_ptrs[i];
-        P.src[i].C = d[0]; P.src[i].H = d[1]; P.src[i].W = d[2]; P.src[i].uh = d[3]; P.src[i].uw = d[4];
-        const int lh = d[1] * d[3], lw = d[2] * d[4];
-        TPSPP_REQUIRE(Hi < 0 || (Hi == lh && Wi == lw), "tpspp_conv2d_fwd: sources disagree on the logical size");
-        Hi = lh; Wi = lw;
-        cin += d[0];
+        P.src[i].C = S.C[i]; P.src[i].H = S.H[i]; P.src[i].W = S.W[i]; P.src[i].uh = S.uh[i]; P.src[i].uw = S.uw[i];
     }
     for (int i = nsrc; i < 3; ++i) P.src[i] = P.src[nsrc - 1];
-    P.Cin = cin; P.Cout = Cout; P.N = N; P.Hi = Hi; P.Wi = Wi; P.Ho = Ho; P.Wo = Wo;
+    P.Cin = S.Cin; P.Cout = Cout; P.N = N; P.Hi = S.Hi; P.Wi = S.Wi; P.Ho = Ho; P.Wo = Wo;
     P.sh = sh; P.sw = sw; P.ph = (KH - 1) / 2; P.pw = (KW - 1) / 2;
-    TPSPP_REQUIRE(Ho == (Hi + 2 * P.ph - KH) / sh + 1 && Wo == (Wi + 2 * P.pw - KW) / sw + 1,
-                  "tpspp_conv2d_fwd: output size does not match input size / stride ('same' padding)");
-    TPSPP_REQUIRE((post_scale == nullptr) == (post_shift == nullptr), "tpspp_conv2d_fwd: post_scale/post_shift come together");
-    P.wt = weight_t; P.bias = bias; P.res = residual; P.out = out;
+    P.bias = bias; P.res = residual; P.out = out;
     P.post_scale = post_scale; P.post_shift = post_shift;
-    TPSPP_REQUIRE(relu >= 0 && relu <= 2, "tpspp_conv2d_fwd: activation code must be 0 (none), 1 (ReLU) or 2 (GELU)");
     P.relu = relu; P.res_mode = res_mode;
     if (N == 0) return TPSPP_OK;
-    hipStream_t st = tpspp::as_stream(stream);
-    if (g_conv_force_generic == 0 && skinny_applies(P, KH)) {
-        ConvParams Q = P;
-        Q.wt = weight_t ? weight_t : weight_tiled;         // identical layouts for a 1x1 kernel (k-major)
-        launch_skinny(Q, st);
-        return tpspp::check_launch("tpspp_conv2d_fwd(skinny)");
-    }
-    if (g_conv_force_generic == 0 && wide_applies(P, KH)) {
-        ConvParams Q = P;
-        Q.wt = weight_t ? weight_t : weight_tiled;
-        launch_wide(Q, st);
-        return tpspp::check_launch("tpspp_conv2d_fwd(wide)");
-    }
-    if (weight_tiled && g_conv_force_generic == 0) {
-        ConvParams Q = P;
-        Q.wt = weight_tiled;
-        if (launch_tiled_any(Q, KH, st)) return tpspp::check_launch("tpspp_conv2d_fwd(tiled)");
-    }
-    TPSPP_REQUIRE(weight_t, "tpspp_conv2d_fwd: shape needs the generic kernel but weight_t is NULL");
-    if (KH == 1) launch_conv<1, 1, 32>(P, st);
-    else         launch_conv<3, 3, 8>(P, st);
-    return tpspp::check_launch("tpspp_conv2d_fwd");
+    ConvRoute R;
+    if (int rc = conv_route(S, g_conv_force_generic != 0, R)) return rc;
+    // the generic kernel reads weight_t, the tiled one weight_tiled; for a 1x1 kernel the two layouts are the same
+    // (k-major), so the skinny and the wide kernel take whichever is given
+    P.wt = R.family == kGeneric ? weight_t : R.family == kTiled ? weight_tiled : (weight_t ? weight_t : weight_tiled);
+    TPSPP_REQUIRE(launch_route(R, P, tpspp::as_stream(stream)), "tpspp_conv2d_fwd: the route names no kernel");
+    static const char* const what[] = {"tpspp_conv2d_fwd", "tpspp_conv2d_fwd(tiled)", "tpspp_conv2d_fwd(wide)",
+                                       "tpspp_conv2d_fwd(skinny)"};
+    return tpspp::check_launch(what[R.family]);
 }
 
 TPSPP_EXPORT int tpspp_linear_ln_fwd(const float* x, int K, int M, float eps, const float* w_gamma,

@@ -485,6 +485,32 @@ def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=No
     return out
 
 
+def conv2d_route(srcs, cw, stride=(1, 1)):
+    """The kernel `conv2d(srcs, cw, stride)` launches (`tpspp_conv2d_route`), as a string: `tiled 3x3 s2x2 4x32 ni1 nb2`
+    (output tile, images per tile, accumulators), `generic 3x3 kc8` (channels per chunk), `wide` or `skinny nw16`
+    (wavefronts that split K).  A host-side query: only shapes are read, so the maps and the weights may live on any
+    device, "meta" included; sizes `conv2d` refuses raise the same error."""
+    dims = []
+    for t, uh, uw in _split_sources(srcs):
+        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw)]
+    if not 1 <= len(dims) // 5 <= 3:
+        raise ValueError("conv2d_route: 1..3 sources")
+    N = _split_sources(srcs)[0][0].shape[0]
+    k = cw.kernel
+    sh, sw, Ho, Wo = _conv_out_size(dims[1] * dims[3], dims[2] * dims[4], k, stride)
+    code = _lib.lib().tpspp_conv2d_route(_vp(_int_array(dims)), len(dims) // 5, int(cw.wt is not None),
+                                         int(cw.tiled is not None), N, cw.wt.shape[1], k, k, sh, sw, Ho, Wo)
+    if code < 0:
+        _lib.check(code, "tpspp_conv2d_route")
+    family, kk = code & 15, (code >> 4) & 15
+    if family == 0:
+        return f"generic {kk}x{kk} kc{(code >> 8) & 255}"
+    if family == 1:
+        return (f"tiled {kk}x{kk} s{(code >> 8) & 15}x{(code >> 12) & 15} {(code >> 16) & 15}x{(code >> 20) & 255} "
+                f"ni{((code >> 28) & 1) + 1} nb{((code >> 29) & 1) + 1}")
+    return "wide" if family == 2 else f"skinny nw{(code >> 8) & 255}"
+
+
 # ---- backward of the fused convolution (tpspp_conv_bwd.hip): training the regressor on the HIP kernels -------------
 def _bwd_out_size(who, Hi, Wi, kernel, stride):
     """`_conv_out_size` under the rule of the backward kernels: stride 1 or 2, kernel 1x1 or 3x3."""
