@@ -1018,6 +1018,23 @@ int tpspp_nrtr_decoder_fwd(const float* enc_cm, int N, int C, int T, int d_inner
                            float* out, int* tokens_out, int* status_out, int flags, tpspp_stream_t stream);
 
 /*
+ * Which pipeline and which kernels tpspp_nrtr_decoder_fwd takes for these sizes, flags and this table (same arguments, same
+ * meaning; of the HOST array layer_ptrs only which entries are NULL is read).  A host-side query: nothing is launched, no
+ * device is needed; it is the function the entry point itself dispatches on.  Returns TPSPP_EINVAL on bad arguments, else
+ *   bits 0-1   pipeline: 0 plain (channel-major steps on tpspp_linear_ln_fwd), 1 arranged (token-major steps on the step
+ *              GEMM, a launch per phase), 2 persistent-eligible (ONE launch per decode where the device holds a group of
+ *              clusters, the stream is not capturing and TPSPP_HEAD_NO_PERSIST is unset; else as 1)
+ *   bit 2      keys / values and the self-attention caches are bf16 (TPSPP_HEAD_BF16), else fp32
+ *   bit 3      the per-step products and the key projection are exact fp32, else the three-term bf16 split
+ *   bit 4      (pipeline 1 and 2's launch form) cross-attention with two heads per wavefront, else one
+ *   bits 8-11  pipeline 2: 1 + the persistent kernel's instantiation 0..11 (6 x (T > 64) + 2 x {0 three-term, 1 bf16
+ *              keys / values, 2 exact fp32} + (d_inner == 512)); 0 otherwise
+ * replaces nothing in the reference (it has one path).
+ */
+int tpspp_nrtr_decoder_route(int C, int T, int d_inner, int n_layers, const float* const* layer_ptrs, int layer_ptrs_len,
+                             int num_out, int flags);
+
+/*
  * Layout change between bf16 convolutions and the sampler: in_blocked (N, C/8, HW, 8) bf16 (tpspp_conv2d_bf16_fwd's layout
  * code 2) -> out_nchw (N, C, HW) bf16.  C % 8 == 0, HW % 64 == 0, 16-byte aligned tensors.  Same values.
  * (The bf16 backbone's second stage ends on the persistent blocked kernel; the warp reads channel planes.)

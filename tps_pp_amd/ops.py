@@ -4,6 +4,7 @@ Each function mirrors one PyTorch call site of the reference (cited in the docst
 device pointers + the current HIP stream to libtpspp_hip.so.  Inputs must be fp32 CUDA(HIP) tensors;
 anything else raises -- there is no eager / CPU fallback on purpose.
 """
+import collections
 import ctypes
 
 import torch
@@ -1396,6 +1397,22 @@ def nrtr_decoder(enc_cm, N, T, table, n_layers, d_inner, emb, pos_table, cls_fol
                                       status.data_ptr(), int(flags), _stream(enc_cm))
     _lib.check(rc, "tpspp_nrtr_decoder_fwd")
     return out, tokens, status
+
+
+DecoderRoute = collections.namedtuple("DecoderRoute", "pipeline kv gemm cross persist")
+
+
+def nrtr_decoder_route(C, T, table, n_layers, d_inner, num_out, flags=0):
+    """`tpspp_nrtr_decoder_route`: what `nrtr_decoder` with these sizes, `flags` and this `PtrTable` dispatches to, as
+    `DecoderRoute(pipeline "plain" | "arranged" | "persistent", kv "bf16" | "fp32", gemm "fp32" | "x3", cross 2 | 1 heads
+    per wavefront, persist = the persistent kernel's instantiation 0..11 or None)`.  A host-side query: of the table only
+    which entries are None is read, nothing is launched.  "persistent" means eligible (include/tpspp.h)."""
+    code = _lib.lib().tpspp_nrtr_decoder_route(int(C), int(T), int(d_inner), int(n_layers), table.ptr, len(table),
+                                               int(num_out), int(flags))
+    if code < 0:
+        _lib.check(code, "tpspp_nrtr_decoder_route")
+    return DecoderRoute(("plain", "arranged", "persistent")[code & 3], "bf16" if code & 4 else "fp32",
+                        "fp32" if code & 8 else "x3", 2 if code & 16 else 1, ((code >> 8) & 15) - 1 if code >> 8 else None)
 
 
 DECODER_TIMEOUT_MESSAGE = (
