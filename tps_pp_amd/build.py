@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtpspp_hip.so")
+INCLUDE_DIRS = [os.path.join(ROOT, "include"), os.path.join(ROOT, "include_units")]
 ARCH = "gfx950"
 
 # -ffp-contract=off: hipcc's default (fast) would fuse a*b+c on its own; the parity contract
@@ -31,8 +32,8 @@ def sources():
 
 
 def _public_headers():
-    inc = os.path.join(ROOT, "include")      # with its sub-directories (include/crnn/tpspp_crnn.h)
-    return sorted(os.path.join(d, f) for d, _, files in os.walk(inc) for f in files if f.endswith(".h"))
+    # include/ with its sub-directories (include/crnn/tpspp_crnn.h) and the further units (include_units/)
+    return sorted(os.path.join(d, f) for inc in INCLUDE_DIRS for d, _, files in os.walk(inc) for f in files if f.endswith(".h"))
 
 
 def _stale():
@@ -71,7 +72,7 @@ def _build_locked(force, verbose):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
         _public_headers() + [os.path.abspath(__file__)]
     hdr_t = max(os.path.getmtime(h) for h in headers)
-    cflags = [f for f in FLAGS if f != "-shared"] + ["-I", os.path.join(ROOT, "include"), "-I", CSRC]
+    cflags = [f for f in FLAGS if f != "-shared"] + [a for inc in INCLUDE_DIRS for a in ("-I", inc)] + ["-I", CSRC]
 
     def compile_one(src):
         obj = os.path.join(objdir, os.path.basename(src)[:-4] + ".o")

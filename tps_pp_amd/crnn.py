@@ -9,7 +9,9 @@ Which path a call takes is `LocalizationNetwork`'s rule.  `.eval()` on a GPU ten
 kernels: the 3x3 convolutions (BatchNorm folded) on `ops.conv2d`, the pools, the LSTM recurrence and the CTC decode on
 the kernels of include/crnn/tpspp_crnn.h, every Linear on `tpspp_mm_f32`; a CPU tensor raises.  `.train()`, or an input
 that requires grad, runs the PyTorch composition of the same layers (`nn.LSTM`, `nn.Linear`, `nn.Conv2d`): the model
-trains through PyTorch plus the HIP warp forward and backward of the preprocessor.
+trains through PyTorch plus the HIP warp forward and backward of the preprocessor.  `CRNNDecoder.set_train_backend("hip")`
+(and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
+kernels of include_units/tpspp_crnn_train.h; the VGG, with its pools, keeps training on PyTorch.
 
 Precision: the VGG and the decoder are exact fp32 in every mode.  `set_compute_dtype` of the recogniser keeps its
 meaning for the preprocessor (its localisation network) and leaves these modules alone: they have no bf16 variant.
@@ -24,7 +26,7 @@ import torch.nn.functional as Fn
 from . import ops
 from ._prepared import prepared
 from .nrtr_head import BaseConvertor, EncodeDecodeRecognizer
-from .registry import BACKBONES, CONVERTORS, DECODERS, DETECTORS
+from .registry import BACKBONES, CONVERTORS, DECODERS, DETECTORS, TrainBackendMixin
 
 
 def _hip_path(module, x):
@@ -167,10 +169,16 @@ class BidirectionalLSTM(nn.Module):
 
 
 @DECODERS.register_module()
-class CRNNDecoder(nn.Module):
+class CRNNDecoder(TrainBackendMixin, nn.Module):
     """`decoders/crnn_decoder.py`: (N, C, 1, W) features -> (N, W, num_classes) raw logits, through two
     `BidirectionalLSTM` (rnn_flag=True) or one 1x1 convolution.  Called as the mirror's decoders are:
     `decoder(feat, out_enc, targets_dict, img_metas, train_mode)`."""
+
+    def set_train_backend(self, mode):
+        """ "torch" (default): the training graph is the PyTorch composition; "hip": with rnn_flag and features on the GPU
+        it runs on HIP kernels, forward and backward (`_forward_train_hip`).  A host tensor, rnn_flag=False and the eval
+        path are not affected."""
+        return super().set_train_backend(mode)
 
     def __init__(self, in_channels=None, num_classes=None, rnn_flag=False, init_cfg=None, **kwargs):
         super().__init__()
@@ -222,8 +230,26 @@ class CRNNDecoder(nn.Module):
         ops.mm(rec, (N * K, K, 1), e1.weight.detach(), (0, K, 1), out, (O, W * O, 1), W, N, O, K, bias=e1.bias.detach())
         return out
 
+    def _forward_train_hip(self, feat):
+        """The training graph on HIP kernels: per layer the input projection (`tpspp_mm_f32`; the first reads its tokens
+        out of the NCHW feature map through its strides), the recurrence that keeps its gates
+        (`tpspp_crnn_lstm_train_fwd` / `tpspp_crnn_lstm_bwd`) and the embedding; the last embedding writes (N, W, C)."""
+        N, C, H, W = feat.shape
+        if H != 1:
+            raise ValueError(f"CRNNDecoder: feature height must be 1, got {H}")
+        feat = feat.float()
+        l0, l1 = self.decoder[0], self.decoder[1]
+        sn, sc, _, sw = feat.stride()
+        rec = ops.crnn_bilstm_autograd(feat, (W, N, sw, sn, sc), W, N, l0.rnn)
+        x = ops.linear_autograd(rec, l0.embedding)                      # (W, N, 256)
+        K = x.shape[2]
+        rec = ops.crnn_bilstm_autograd(x, (W, N, N * K, K, 1), W, N, l1.rnn)
+        return ops.linear_nwc_autograd(rec, l1.embedding)
+
     def forward_train(self, feat, out_enc, targets_dict, img_metas):
         if not _hip_path(self, feat):
+            if self.train_backend == "hip" and self.rnn_flag and feat.is_cuda:
+                return self._forward_train_hip(feat)
             return self._forward_torch(feat)
         ops.require_gpu(feat, "CRNNDecoder")
         ops.warn_detached_once(self, "CRNNDecoder")

@@ -6,13 +6,13 @@
 
 #include "crnn/tpspp_crnn.h"
 #include "tpspp_common.h"
+#include "tpspp_crnn_cell.h"
 #include "tpspp_dev.h"
 
 namespace {
 
 using namespace tpspp_dev;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tpspp_crnn_cell;
 
 // ---- max-pooling -----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -41,86 +41,11 @@ crnn_maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, long 
 }
 
 // ---- the LSTM recurrence -----------------------------------------------------------------------------------------------------
-constexpr int kHid = TPSPP_CRNN_HIDDEN;     // units per direction
-constexpr int kGates = 4 * kHid;            // gate columns per direction: i, f, g, o
-constexpr int kRows = 16;                   // image rows of the matrix-core tile
-constexpr int kLd = kHid + 4;               // LDS row stride of h in floats: 16-byte aligned, rows 4 banks apart
-constexpr int kLstmThreads = 512;           // 8 wavefronts, each owns 2 tiles of 16 units with their 4 gates
-
-__device__ __forceinline__ float sigmoid_safe(float x)
-{
-    const float e = expf(-fabsf(x));        // (0, 1]
-    return (x >= 0.0f ? 1.0f : e) / (1.0f + e);
-}
-
-__device__ __forceinline__ float tanh_safe(float x)
-{
-    const float m = expm1f(-2.0f * fabsf(x));   // (-1, 0]
-    return copysignf(-m / (m + 2.0f), x);
-}
-
-// blockIdx.x = 2 * block-of-images + direction.  Lane l of a wavefront holds, as the A operand, h[image l & 15][k] and, as
-// the B operand, w_hh[unit l & 15][k] for k = 16 b + 4 (l >> 4) + m; its accumulators hold images 4 (l >> 4) + r of unit
-// l & 15 -- the same (image, unit) in all four gate tiles, so the cell update needs no exchange and c stays in registers.
+// (the constants, the activations and the body: tpspp_crnn_cell.h, shared with the training kernels)
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_kernel(const float* __restrict__ xg, const float* __restrict__ whh, float* __restrict__ out, int T, int N, int g)
 {
-    __shared__ __attribute__((aligned(16))) float hbuf[2][kRows * kLd];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    const int d = blockIdx.x & 1;
-    const int n0 = (int)(blockIdx.x >> 1) * g;
-    const int col = lane & 15, quad = lane >> 4;
-    for (int i = tid; i < 2 * kRows * kLd; i += kLstmThreads) (&hbuf[0][0])[i] = 0.0f;
-    const float* w = whh + (size_t)d * kGates * kHid;
-    float c[2][4];
-    bool valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        c[0][r] = c[1][r] = 0.0f;
-        valid[r] = 4 * quad + r < g && n0 + 4 * quad + r < N;
-    }
-    int cur = 0;
-    __syncthreads();
-    for (int s = 0; s < T; ++s) {
-        const int t = d ? T - 1 - s : s;
-        const float* hrow = &hbuf[cur][col * kLd + 4 * quad];
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int u = (2 * wave + ut) * 16 + col;
-            f32x4 acc[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* x = xg + (((size_t)t * N + (valid[r] ? n0 + 4 * quad + r : 0)) * 2 + d) * kGates + u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q][r] = valid[r] ? x[q * kHid] : 0.0f;
-            }
-            const float* wr = w + (size_t)u * kHid + 4 * quad;
-            // (h is read from LDS again per tile: 16 rows of A held in registers next to the weight loads in flight spill)
-#pragma unroll 4
-            for (int b = 0; b < 16; ++b) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(hrow + 16 * b);
-                f32x4 bv[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) bv[q] = *reinterpret_cast<const f32x4*>(wr + (size_t)q * kHid * kHid + 16 * b);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[q][m], acc[q], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float gi = sigmoid_safe(acc[0][r]), gf = sigmoid_safe(acc[1][r]);
-                const float gg = tanh_safe(acc[2][r]), go = sigmoid_safe(acc[3][r]);
-                c[ut][r] = gf * c[ut][r] + gi * gg;
-                const float h = go * tanh_safe(c[ut][r]);
-                hbuf[cur ^ 1][(4 * quad + r) * kLd + u] = h;        // rows past the block: xg = 0 keeps c = h = 0
-                if (valid[r]) out[((size_t)t * N + n0 + 4 * quad + r) * (2 * kHid) + d * kHid + u] = h;
-            }
-        }
-        __syncthreads();            // h of this step is complete before any wavefront reads it; the other copy is free
-        cur ^= 1;
-    }
+    lstm_recurrence<false>(xg, whh, out, nullptr, nullptr, T, N, g);
 }
 
 // ---- CTC greedy decode -----------------------------------------------------------------------------------------------------
@@ -158,8 +83,6 @@ crnn_ctc_decode_kernel(const float* __restrict__ logits, const int* __restrict__
         prev = am;
     }
 }
-
-bool lstm_group_ok(int g) { return g == 4 || g == 8 || g == 16; }
 
 int lstm_plan(int N, int images_per_group, int cus)
 {

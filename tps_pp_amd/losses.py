@@ -82,11 +82,12 @@ def build_loss(cfg):
 
 
 @LOSSES.register_module()
-class CTCLoss(nn.Module):
+class CTCLoss(TrainBackendMixin, nn.Module):
     """`losses/ctc_loss.py`: `log_softmax` over the classes and `nn.CTCLoss` on (T, N, C); flattened targets by default,
     else targets padded with `blank` and input lengths from the valid ratios; target lengths clamped to 1 .. T.
-    -> {'loss_ctc': tensor}.  PyTorch's kernels: there is no HIP path (the `ignore_index` that `EncodeDecodeRecognizer` adds
-    to every loss config is accepted and unused, as in the reference)."""
+    -> {'loss_ctc': tensor}.  PyTorch's kernels, or with `set_train_backend("hip")` and logits on the GPU the kernels of
+    include_units/tpspp_crnn_train.h (the `ignore_index` that `EncodeDecodeRecognizer` adds to every loss config is accepted
+    and unused, as in the reference)."""
 
     def __init__(self, flatten=True, blank=0, reduction="mean", zero_infinity=False, **kwargs):
         super().__init__()
@@ -98,10 +99,48 @@ class CTCLoss(nn.Module):
         self.blank = blank
         self.ctc_loss = nn.CTCLoss(blank=blank, reduction=reduction, zero_infinity=zero_infinity)
 
+    def set_train_backend(self, mode):
+        """ "torch" (default): `log_softmax` + `nn.CTCLoss`; "hip": `tpspp_crnn_ctc_loss_fwd` / `_bwd` on the raw logits
+        when they are on the GPU (logits on the host keep PyTorch's)."""
+        return super().set_train_backend(mode)
+
+    def _lengths(self, targets_dict, bsz, seq_len, valid_ratios):
+        """(target lengths, input lengths) as the reference computes them: int64 on the host."""
+        target_lengths = torch.clamp(targets_dict["target_lengths"], min=1, max=seq_len).long()
+        input_lengths = torch.full(size=(bsz,), fill_value=seq_len, dtype=torch.long)
+        if not self.flatten and valid_ratios is not None:
+            input_lengths = torch.Tensor([math.ceil(valid_ratio * seq_len) for valid_ratio in valid_ratios]).long()
+        return target_lengths, input_lengths
+
+    def _forward_hip(self, outputs, targets_dict, valid_ratios):
+        """The same loss from the raw logits on HIP kernels.  Targets are padded to the longest clamped length; flattened
+        targets are cut at the running sums of the clamped lengths, which is how `nn.CTCLoss` reads them."""
+        from . import ops
+        bsz, seq_len = outputs.size(0), outputs.size(1)
+        target_lengths, input_lengths = self._lengths(targets_dict, bsz, seq_len, valid_ratios)
+        lens = target_lengths.tolist()
+        padded = torch.full((bsz, max(lens, default=0)), self.blank, dtype=torch.int32)
+        if self.flatten:
+            flat = targets_dict["flatten_targets"].cpu()
+            if sum(lens) > flat.numel():
+                raise ValueError(f"CTCLoss: the target lengths add up to {sum(lens)}, flatten_targets holds {flat.numel()}")
+            start = 0
+            for idx, n in enumerate(lens):
+                padded[idx, :n] = flat[start:start + n]
+                start += n
+        else:
+            for idx, tensor in enumerate(targets_dict["targets"]):
+                valid_len = min(tensor.size(0), seq_len, padded.size(1))
+                padded[idx, :valid_len] = tensor[:valid_len]
+        return ops.crnn_ctc_loss_autograd(outputs.float(), padded, target_lengths, input_lengths, self.blank,
+                                          self.ctc_loss.reduction, self.ctc_loss.zero_infinity)
+
     def forward(self, outputs, targets_dict, img_metas=None):
         valid_ratios = None
         if img_metas is not None:
             valid_ratios = [img_meta.get("valid_ratio", 1.0) for img_meta in img_metas]
+        if self.train_backend == "hip" and outputs.is_cuda:
+            return dict(loss_ctc=self._forward_hip(outputs, targets_dict, valid_ratios))
         outputs = torch.log_softmax(outputs, dim=2)
         bsz, seq_len = outputs.size(0), outputs.size(1)
         outputs_for_loss = outputs.permute(1, 0, 2).contiguous()          # (T, N, C)
@@ -112,9 +151,6 @@ class CTCLoss(nn.Module):
             for idx, tensor in enumerate(targets_dict["targets"]):
                 valid_len = min(tensor.size(0), seq_len)
                 targets[idx, :valid_len] = tensor[:valid_len]
-        target_lengths = torch.clamp(targets_dict["target_lengths"], min=1, max=seq_len).long()
-        input_lengths = torch.full(size=(bsz,), fill_value=seq_len, dtype=torch.long)
-        if not self.flatten and valid_ratios is not None:
-            input_lengths = torch.Tensor([math.ceil(valid_ratio * seq_len) for valid_ratio in valid_ratios]).long()
+        target_lengths, input_lengths = self._lengths(targets_dict, bsz, seq_len, valid_ratios)
         # (the targets follow the logits' device: PyTorch's own GPU kernel wants them there; a no-op on the host)
         return dict(loss_ctc=self.ctc_loss(outputs_for_loss, targets.to(outputs.device), input_lengths, target_lengths))

@@ -3102,3 +3102,274 @@ def crnn_ctc_decode(logits, decode_len, blank=0):
     _lib.check(rc, "tpspp_crnn_ctc_decode")
     host = buf[:2 * N * T].cpu().numpy()
     return host[:N * T].reshape(N, T), host[N * T:].view("float32").reshape(N, T)
+
+
+# ---- training of the CRNN decoder and the CTC loss (include_units/tpspp_crnn_train.h, tpspp_crnn_train.hip) --------------
+def _lstm_operand(who, name, t, shape_tail, T=None, N=None):
+    t = _chk(f"{who} {name}", t, 2 + len(shape_tail))
+    if tuple(t.shape[2:]) != tuple(shape_tail) or (T is not None and tuple(t.shape[:2]) != (T, N)):
+        raise ValueError(f"{who}: {name} must be (T, N, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}")
+    return t
+
+
+def crnn_lstm_train_fwd(xg, w_hh, images_per_group=0):
+    """`tpspp_crnn_lstm_train_fwd`: `crnn_lstm` (the same bits) that keeps what `crnn_lstm_bwd` reads ->
+    (out (T, N, 512), gates (T, N, 2, 1024) after their activations, cell (T, N, 2, 256))."""
+    who = "crnn_lstm_train_fwd"
+    xg = _lstm_operand(who, "xg", xg, (2, 4 * CRNN_HIDDEN))
+    w_hh = _chk(f"{who} w_hh", w_hh, 3)
+    if tuple(w_hh.shape) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) or w_hh.device != xg.device:
+        raise ValueError(f"{who}: w_hh must be (2, 1024, 256) on xg's device, got {tuple(w_hh.shape)}")
+    T, N = xg.shape[0], xg.shape[1]
+    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    gates = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    cell = torch.empty((T, N, 2, CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    if N == 0:
+        return out, gates, cell
+    with torch.cuda.device(xg.device):
+        rc = _lib.lib().tpspp_crnn_lstm_train_fwd(_ptr(xg), _ptr(w_hh), _ptr(out), _ptr(gates), _ptr(cell), T, N, CRNN_HIDDEN,
+                                                  int(images_per_group), _stream(xg))
+    _lib.check(rc, "tpspp_crnn_lstm_train_fwd")
+    return out, gates, cell
+
+
+def crnn_lstm_bwd(d_out, gates, cell, w_hh_t, images_per_group=0, direction_major=False):
+    """`tpspp_crnn_lstm_bwd`: the backward through time.  d_out (T, N, 512), gates and cell of `crnn_lstm_train_fwd`, w_hh_t
+    (2, 256, 1024) the per-direction transpose of w_hh -> d_xg (T, N, 2, 1024), the gradient of the pre-activations; with
+    `direction_major` -> (d_xg, its copy as (2, T, N, 1024): what `crnn_lstm_bwd_w_hh` reads)."""
+    who = "crnn_lstm_bwd"
+    gates = _lstm_operand(who, "gates", gates, (2, 4 * CRNN_HIDDEN))
+    T, N = gates.shape[0], gates.shape[1]
+    d_out = _lstm_operand(who, "d_out", d_out, (2 * CRNN_HIDDEN,), T, N)
+    cell = _lstm_operand(who, "cell", cell, (2, CRNN_HIDDEN), T, N)
+    w_hh_t = _chk(f"{who} w_hh_t", w_hh_t, 3)
+    if tuple(w_hh_t.shape) != (2, CRNN_HIDDEN, 4 * CRNN_HIDDEN) or len({t.device for t in (d_out, gates, cell, w_hh_t)}) != 1:
+        raise ValueError(f"{who}: w_hh_t must be (2, 256, 1024), all operands on one device, got {tuple(w_hh_t.shape)}")
+    d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
+    d_dir = torch.empty((2, T, N, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32) if direction_major else None
+    if N > 0:
+        with torch.cuda.device(gates.device):
+            rc = _lib.lib().tpspp_crnn_lstm_bwd(_ptr(d_out), _ptr(gates), _ptr(cell), _ptr(w_hh_t), _ptr(d_xg), _ptr(d_dir), T, N,
+                                                CRNN_HIDDEN, int(images_per_group), _stream(gates))
+        _lib.check(rc, "tpspp_crnn_lstm_bwd")
+    return (d_xg, d_dir) if direction_major else d_xg
+
+
+def crnn_lstm_bwd_w_hh(d_xg_dir, out):
+    """d w_hh (2, 1024, 256) = sum_t da_t[d]^T h_{t -+ 1}[d] on `tpspp_linear_bwd_weight` (fixed split-K, bitwise
+    reproducible): dy is the direction-major d_xg_dir (2, T, N, 1024) of `crnn_lstm_bwd`, shifted by one step -- dense rows
+    --, x the shifted view of out (T, N, 512) read through its row stride.  The step whose previous h is h_0 = 0 drops
+    out, so T = 1 gives zeros.  (tpspp_mm_f32 over shifted views of the (T, N, 2, 1024) d_xg needs no copy but reads its k
+    operand at a stride of 2048 floats: scripts/bench_crnn_train.py measures both.)"""
+    T, N = d_xg_dir.shape[1], d_xg_dir.shape[2]
+    H, G = CRNN_HIDDEN, 4 * CRNN_HIDDEN
+    if T < 2 or N == 0:
+        return torch.empty((2, G, H), device=d_xg_dir.device, dtype=torch.float32).zero_()
+    M = (T - 1) * N
+    pairs = ((d_xg_dir[0, 1:], out[:-1, :, :H]), (d_xg_dir[1, :-1], out[1:, :, H:]))
+    return torch.stack([linear_bwd_weight(dy.reshape(M, G), x, (1, M, 0, 2 * H, 1), G, H, True, False)[0] for dy, x in pairs])
+
+
+class _BiLstmFunction(torch.autograd.Function):
+    """One bidirectional nn.LSTM layer with zero initial state.  Saves the tokens, the concatenated weights, the output and
+    the recurrence's gates and cell states; the input projection's result is not kept."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih0, w_ih1, w_hh0, w_hh1, b_ih0, b_hh0, b_ih1, b_hh1, cfg):
+        desc, T, N, group = cfg
+        w_ih = torch.cat([w_ih0, w_ih1]).float().contiguous()
+        b = torch.cat([b_ih0 + b_hh0, b_ih1 + b_hh1]).float().contiguous()
+        w_hh = torch.stack([w_hh0, w_hh1]).float().contiguous()
+        xg = linear_fwd(x, desc, w_ih, b).view(T, N, 2, 4 * CRNN_HIDDEN)
+        out, gates, cell = crnn_lstm_train_fwd(xg, w_hh, group)
+        ctx.save_for_backward(x, w_ih, w_hh, out, gates, cell)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        x, w_ih, w_hh, out, gates, cell = ctx.saved_tensors
+        desc, T, N, group = ctx.cfg
+        need = ctx.needs_input_grad
+        H, K = CRNN_HIDDEN, w_ih.shape[1]
+        w_hh_t = torch.stack([transpose2d(w_hh[0]), transpose2d(w_hh[1])])
+        d_xg, d_dir = crnn_lstm_bwd(d_out.float().contiguous(), gates, cell, w_hh_t, group, direction_major=True)
+        dy = d_xg.view(T * N, 8 * H)
+        dw_ih, db = linear_bwd_weight(dy, x, desc, 8 * H, K, any(need[1:3]), any(need[5:9]))
+        dx = None
+        if need[0]:
+            dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+            if x.dim() == 4:                                         # tokens of an NCHW map: (t, n, c) = x[n, c, 0, t]
+                sn, sc, _, sw = dx.stride()
+                linear_bwd_data(dy, w_ih, dx, (T, N, sw, sn, sc))
+            else:
+                linear_bwd_data(dy, w_ih, dx, (T, N, N * K, K, 1))
+        dw_hh = crnn_lstm_bwd_w_hh(d_dir, out) if any(need[3:5]) else (None, None)
+        gw = (None, None) if dw_ih is None else (dw_ih[:4 * H], dw_ih[4 * H:])
+        # (b_ih and b_hh of a direction receive the same values in tensors of their own: autograd may keep a gradient it is
+        # handed as the parameter's .grad, and two parameters must not share one)
+        gb = (None,) * 4 if db is None else (db[:4 * H], db[:4 * H].clone(), db[4 * H:], db[4 * H:].clone())
+        return (dx, gw[0], gw[1], dw_hh[0], dw_hh[1], *gb, None)
+
+
+def crnn_bilstm_autograd(x, desc, T, N, lstm, images_per_group=0):
+    """The bidirectional nn.LSTM(K, 256) `lstm` with zero initial state on the token operand x (`desc` = (T, N, batch stride,
+    row stride, k stride) as `linear_fwd` takes it: a dense (T, N, K) tensor, or the (N, K, 1, T) feature map read in place)
+    -> (T, N, 512), differentiable in x and in all eight parameters of the layer: input projection and its weight / data
+    gradients on `tpspp_mm_f32` / `tpspp_linear_bwd_weight`, the recurrence on `tpspp_crnn_lstm_train_fwd` / `_bwd`, d w_hh
+    on `tpspp_mm_f32` over shifted views."""
+    who = "crnn_bilstm_autograd"
+    _chk_gpu(f"{who} x", x)
+    if x.dtype != torch.float32:
+        raise TypeError(f"{who}: x must be float32, got {x.dtype}")
+    if lstm.hidden_size != CRNN_HIDDEN or lstm.num_layers != 1 or not lstm.bidirectional or not lstm.bias:
+        raise ValueError(f"{who}: one bidirectional layer of {CRNN_HIDDEN} hidden units with biases")
+    K = lstm.input_size
+    if x.dim() == 4:
+        if x.shape[2] != 1 or (x.shape[3], x.shape[0], x.shape[1]) != (T, N, K):
+            raise ValueError(f"{who}: a feature map must be (N, K, 1, T) = ({N}, {K}, 1, {T}), got {tuple(x.shape)}")
+    elif tuple(x.shape) != (T, N, K) or not x.is_contiguous():
+        raise ValueError(f"{who}: x must be a dense ({T}, {N}, {K}) tensor or an (N, K, 1, T) feature map, got {tuple(x.shape)}")
+    return _BiLstmFunction.apply(x, lstm.weight_ih_l0, lstm.weight_ih_l0_reverse, lstm.weight_hh_l0, lstm.weight_hh_l0_reverse,
+                                 lstm.bias_ih_l0, lstm.bias_hh_l0, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse,
+                                 (tuple(int(v) for v in desc), int(T), int(N), int(images_per_group)))
+
+
+class _LinearNwcFunction(torch.autograd.Function):
+    """nn.Linear on (W, N, K) tokens whose result is written as (N, W, O): no layout pass in either direction."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        W, N, K = x.shape
+        O = w.shape[0]
+        ctx.save_for_backward(x, w)
+        y = torch.empty((N, W, O), device=x.device, dtype=torch.float32)
+        return mm(x, (N * K, K, 1), w, (0, K, 1), y, (O, W * O, 1), W, N, O, K, bias=b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        W, N, K = x.shape
+        O = w.shape[0]
+        gy = gy.float().contiguous().view(N * W, O)                  # rows (n, w): x[w, n] through its strides
+        desc = (N, W, K, N * K, 1)
+        dw, db = linear_bwd_weight(gy, x, desc, O, K, need[1], need[2])
+        dx = linear_bwd_data(gy, w, torch.empty_like(x), desc) if need[0] else None
+        return dx, dw, db
+
+
+def linear_nwc_autograd(x, lin):
+    """nn.Linear `lin` on dense (W, N, K) tokens -> (N, W, O), differentiable: `CRNNDecoder`'s last embedding."""
+    x = _chk("linear_nwc_autograd x", x, 3)
+    if x.shape[-1] != lin.weight.shape[1]:
+        raise ValueError(f"linear_nwc_autograd: input width {x.shape[-1]} against weight {tuple(lin.weight.shape)}")
+    return _LinearNwcFunction.apply(x, lin.weight, lin.bias)
+
+
+_CTC_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+CTC_MAX_CLASSES, CTC_MAX_TARGET = 1024, 1024
+
+
+def crnn_ctc_loss_workspace_floats(N, T, Lmax):
+    return int(_lib.lib().tpspp_crnn_ctc_loss_workspace_floats(int(N), int(T), int(Lmax)))
+
+
+def _ctc_operands(who, logits, targets, target_len, input_len):
+    logits = _chk(f"{who} logits", logits, 3)
+    N = logits.shape[0]
+    dev = logits.device
+    if not isinstance(targets, torch.Tensor) or targets.is_floating_point() or targets.dim() != 2 or targets.shape[0] != N:
+        raise ValueError(f"{who}: targets must be ({N}, Lmax) integers")
+    out = [logits, targets.to(device=dev, dtype=torch.int32).contiguous()]
+    for name, t in (("target_len", target_len), ("input_len", input_len)):
+        if not isinstance(t, torch.Tensor) or t.is_floating_point() or tuple(t.shape) != (N,):
+            raise ValueError(f"{who}: {name} must be ({N}) integers")
+        out.append(t.to(device=dev, dtype=torch.int32).contiguous())
+    return out
+
+
+def crnn_ctc_loss_fwd(logits, targets, target_len, input_len, blank=0, zero_infinity=False, reduction=0):
+    """`tpspp_crnn_ctc_loss_fwd` on raw logits (N, T, C), padded int32 targets (N, Lmax) and int32 lengths (N), all on the
+    device -> (loss (N), lse (N, T), reduced (1) | None, ws): lse and ws are what `crnn_ctc_loss_bwd` reads."""
+    N, T, C = logits.shape
+    Lmax = targets.shape[1]
+    dev = logits.device
+    loss = torch.empty((N,), device=dev, dtype=torch.float32)
+    lse = torch.empty((N, T), device=dev, dtype=torch.float32)
+    red = torch.empty((1,), device=dev, dtype=torch.float32) if reduction else None
+    n = crnn_ctc_loss_workspace_floats(N, T, Lmax)
+    ws = _ws(n, dev)
+    if N == 0 and reduction:                   # the library returns before any launch
+        red.fill_(float("nan") if reduction == 1 else 0.0)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_crnn_ctc_loss_fwd(_ptr(logits), _ptr(targets), _ptr(target_len), _ptr(input_len), N, T, C, Lmax,
+                                                int(blank), int(bool(zero_infinity)), reduction, _ptr(loss), _ptr(lse),
+                                                _ptr(red), _ptr(ws), n, _stream(logits))
+    _lib.check(rc, "tpspp_crnn_ctc_loss_fwd")
+    return loss, lse, red, ws
+
+
+def crnn_ctc_loss_bwd(g, logits, targets, target_len, input_len, lse, ws, blank=0, zero_infinity=False, reduction=0):
+    """`tpspp_crnn_ctc_loss_bwd`: d_logits (N, T, C) dense, exact zeros from each image's input length on."""
+    N, T, C = logits.shape
+    d = torch.empty((N, T, C), device=logits.device, dtype=torch.float32)
+    with torch.cuda.device(logits.device):
+        rc = _lib.lib().tpspp_crnn_ctc_loss_bwd(_ptr(g), _ptr(logits), _ptr(targets), _ptr(target_len), _ptr(input_len),
+                                                _ptr(lse), _ptr(ws), N, T, C, targets.shape[1], int(blank),
+                                                int(bool(zero_infinity)), reduction, _ptr(d), _stream(logits))
+    _lib.check(rc, "tpspp_crnn_ctc_loss_bwd")
+    return d
+
+
+class _CtcLossFunction(torch.autograd.Function):
+    """Saves the logits, the targets and lengths, the per-position log-sum-exp and the alpha table."""
+
+    @staticmethod
+    def forward(ctx, logits, targets, target_len, input_len, cfg):
+        blank, zero_infinity, reduction = cfg
+        loss, lse, red, ws = crnn_ctc_loss_fwd(logits, targets, target_len, input_len, blank, zero_infinity, reduction)
+        ctx.save_for_backward(logits, targets, target_len, input_len, lse, ws)
+        ctx.cfg = cfg
+        return red.view(()) if reduction else loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        logits, targets, target_len, input_len, lse, ws = ctx.saved_tensors
+        if logits.shape[0] == 0:
+            return torch.zeros_like(logits), None, None, None, None
+        d = crnn_ctc_loss_bwd(g.float().contiguous().view(-1), logits, targets, target_len, input_len, lse, ws, *ctx.cfg)
+        return d, None, None, None, None
+
+
+def crnn_ctc_loss_autograd(logits, targets, target_len, input_len, blank=0, reduction="mean", zero_infinity=False):
+    """`F.ctc_loss(log_softmax(logits, 2).permute(1, 0, 2), ...)` on HIP kernels from the raw logits (N, T, C): a scalar for
+    "mean" / "sum", (N) for "none".  targets (N, Lmax) padded, target_len and input_len (N): integers on the host or the
+    device; lengths are clamped to 0 .. Lmax and 0 .. T.  Targets on the host are checked here, where they originate: one
+    outside 0 .. C - 1 or equal to blank (within its image's length) raises."""
+    who = "crnn_ctc_loss_autograd"
+    if reduction not in _CTC_REDUCTIONS:
+        raise ValueError(f'{who}: reduction must be "none", "mean" or "sum", got {reduction!r}')
+    if isinstance(logits, torch.Tensor) and logits.dim() == 3:
+        N, T, C = logits.shape
+        if not 2 <= C <= CTC_MAX_CLASSES or not 0 <= int(blank) < C or T < 1:
+            raise ValueError(f"{who}: 2 to {CTC_MAX_CLASSES} classes, blank among them, at least one position; got "
+                             f"{tuple(logits.shape)}, blank {blank}")
+    if isinstance(targets, torch.Tensor) and targets.dim() == 2:
+        if targets.shape[1] > CTC_MAX_TARGET:
+            raise ValueError(f"{who}: at most {CTC_MAX_TARGET} target positions, got {targets.shape[1]}")
+        if not targets.is_cuda and isinstance(target_len, torch.Tensor) and not target_len.is_cuda and targets.numel():
+            used = torch.arange(targets.shape[1])[None, :] < target_len.reshape(-1, 1)
+            bad = used & ((targets < 0) | (targets >= logits.shape[2]) | (targets == int(blank)))
+            if bad.any():
+                n, j = (int(v) for v in bad.nonzero()[0])
+                raise ValueError(f"{who}: target {int(targets[n, j])} of image {n}, position {j}: outside 0 .. "
+                                 f"{logits.shape[2] - 1} or the blank {int(blank)}")
+    logits, targets, target_len, input_len = _ctc_operands(who, logits, targets, target_len, input_len)
+    return _CtcLossFunction.apply(logits, targets, target_len, input_len,
+                                  (int(blank), bool(zero_infinity), _CTC_REDUCTIONS[reduction]))
