@@ -2,6 +2,9 @@
 
 Rows: the rectifier; the VGG; each BiLSTM layer split into its input projection (tpspp_mm_f32) and its recurrence
 (tpspp_crnn_lstm_fwd); the two embedding Linears; the CTC decode with its device->host copy; the whole `simple_test`.
+Then, for each precision mode (fp32 = compute_dtype None, the control; "bf16x3"; torch.bfloat16): the VGG alone, each of its
+seven convolutions (TFLOP/s) and four pools (GB/s) through the calls the VGG makes, and `simple_test` whole; and the
+agreement of each reduced mode's decisions with the exact fp32 kernels on 256 images (printed, not a bar).
 Two comparison columns, neither of them a pass bar:
   * `torch.nn.LSTM` on the same GPU against projection + recurrence of the same layer (the library fuses the two, so the
     recurrence alone has no counterpart);
@@ -82,6 +85,84 @@ def main():
     def hip_tail(rect):
         return conv.tensor2str(dec(m.backbone(rect), None, None, None, train_mode=False), metas)
 
+    # ---- the precision modes: the VGG alone, each of its layers and pools, simple_test whole ------------
+    MODES = (("fp32", None), ("bf16x3", "bf16x3"), ("bf16", torch.bfloat16))
+    POOLS = {0: (2, 2, 0), 1: (2, 2, 0), 3: ((2, 2), (2, 1), (0, 1)), 5: ((2, 2), (2, 1), (0, 1))}
+    vgg = m.backbone
+    work = {}                                               # row name -> (FLOP, bytes moved) per call
+
+    def in_mode(mode, f, whole=False):
+        """f() with the VGG (whole: the model, through its public switch) in `mode`; the default mode afterwards."""
+        def call():
+            if whole:
+                m.set_compute_dtype(mode)
+            else:
+                vgg.compute_dtype = mode
+            try:
+                return f()
+            finally:
+                m.set_compute_dtype(None)
+        return call
+
+    def numel(t):
+        return t.t.numel() if isinstance(t, ops.Blocked) else t.numel()
+
+    def nbytes(t):
+        return numel(t) * (t.t if isinstance(t, ops.Blocked) else t).element_size()
+
+    def layer_ops(mode):
+        """[(name, fn(x), is_conv)] of the VGG's eleven steps in `mode`, the calls `VeryDeepVgg.forward` makes."""
+        steps = []
+        if mode is None:
+            cw = vgg._hip_weights()
+            for i in range(7):
+                steps.append((f"conv{i}", (lambda x, i=i: ops.conv2d([x], cw[i], (2, 1) if i == 6 else 1, True)), True))
+                if i in POOLS:
+                    steps.append((f"pool{len([s for s in steps if not s[2]])}", (lambda x, i=i: ops.crnn_maxpool(x, *POOLS[i])), False))
+            return steps
+        x3 = mode == "bf16x3"
+        cw, dt = vgg._hip_weights_bf16(x3), torch.float32 if x3 else torch.bfloat16
+        for i in range(6):
+            steps.append((f"conv{i}", (lambda x, i=i: ops.conv2d_bf16([x], cw[i], 1, True, out_dtype=dt, out_blocked=True)), True))
+            if i in POOLS:
+                steps.append((f"pool{len([s for s in steps if not s[2]])}", (lambda x, i=i: ops.crnn_maxpool_blocked(x, *POOLS[i])), False))
+        steps.append(("conv6", lambda x: ops.conv2d_bf16([x], cw[6], (2, 1), True, out_dtype=torch.float32), True))
+        return steps
+
+    mode_rows = {}
+    with torch.no_grad():
+        for label, mode in MODES:
+            mode_rows[f"VGG, {label}"] = (in_mode(mode, lambda: vgg(rot(rects))), False)
+            steps = layer_ops(mode)
+            ins = [[r] for r in rects]                      # per buffer: the inputs of the eleven steps
+            for name, fn, is_conv in steps:
+                for b in range(B):
+                    ins[b].append(fn(ins[b][-1]))
+            for k, (name, fn, is_conv) in enumerate(steps):
+                xin, out = ins[0][k], ins[0][k + 1]
+                key = f"  {name}, {label}"
+                if is_conv:
+                    cin, (n_, cout, ho, wo) = xin.shape[1], out.shape
+                    taps, wo = (4, wo - 1) if name == "conv6" else (9, wo)       # conv6 is the 2x2 valid convolution
+                    work[key] = (2.0 * n_ * cout * ho * wo * cin * taps, 0)
+                else:
+                    work[key] = (0, nbytes(xin) + nbytes(out))
+                mode_rows[key] = ((lambda fn=fn, k=k, ins=ins: fn(rot(ins)[k])), False)
+            mode_rows[f"simple_test (whole model), {label}"] = (in_mode(mode, lambda: m.simple_test(rot(imgs), metas), True), True)
+        # decisions of the reduced modes against the exact fp32 kernels on 256 images (random-init weights, synthetic images)
+        agreement = {}
+        k256 = min(256, N)
+        x256, metas256 = imgs[0][:k256], metas[:k256]
+
+        def decide():
+            lg = dec(vgg(m.preprocessor(x256)), None, None, None, train_mode=False)
+            return lg.argmax(2).cpu(), conv.tensor2str(lg, metas256)[0]
+        am0, str0 = decide()
+        for label, mode in MODES[1:]:
+            am, strs = in_mode(mode, decide, True)()
+            agreement[label] = dict(images=k256, greedy_string_agreement=sum(a == b for a, b in zip(strs, str0)) / k256,
+                                    per_position_argmax_agreement=float((am == am0).float().mean()))
+
     rows = {
         "rectifier (TPSPreprocessor)": (lambda: m.preprocessor(rot(imgs)), False),
         "VGG (VeryDeepVgg)": (lambda: m.backbone(rot(rects)), False),
@@ -101,6 +182,7 @@ def main():
         "VGG + decoder + decode, PyTorch composition": (lambda: torch_tail(rot(rects)), True),
         "simple_test (whole model)": (lambda: m.simple_test(rot(imgs), metas), True),
     }
+    rows.update(mode_rows)
 
     def region(f, host):
         e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -126,8 +208,17 @@ def main():
     table = []
     for k, v in ms.items():
         row = dict(stage=k, ms=statistics.median(v), ms_min=min(v), ms_max=max(v), clock="host" if rows[k][1] else "device")
+        rate = ""
+        if k in work:                                       # a layer of the VGG: its arithmetic or its traffic
+            flop, moved = work[k]
+            if flop:
+                row["tflops"] = flop / (row["ms"] * 1e-3) / 1e12
+                rate = f", {row['tflops']:.1f} TFLOP/s"
+            else:
+                row["gb_per_s"] = moved / (row["ms"] * 1e-3) / 1e9
+                rate = f", {row['gb_per_s']:.0f} GB/s"
         table.append(row)
-        print(f"{k:50s} {row['ms']:9.3f} ms / batch (min {row['ms_min']:.3f} max {row['ms_max']:.3f}, {row['clock']} clock)",
+        print(f"{k:50s} {row['ms']:9.3f} ms / batch (min {row['ms_min']:.3f} max {row['ms_max']:.3f}, {row['clock']} clock{rate})",
               flush=True)
     med = {r["stage"]: r["ms"] for r in table}
     result = dict(bench="crnn", batch=N, T=int(T), reps=a.reps, regions=a.regions, buffers=B, images_per_group=plan,
@@ -137,7 +228,12 @@ def main():
                   lstm1_hip_over_torch=(med["lstm1 input projection 256 -> 2x1024"] + med["lstm1 recurrence"]) /
                   med["lstm1 torch.nn.LSTM (projection + recurrence)"],
                   tail_hip_over_torch=med["VGG + decoder + decode, HIP"] / med["VGG + decoder + decode, PyTorch composition"],
-                  images_per_s=N / med["simple_test (whole model)"] * 1e3)
+                  images_per_s=N / med["simple_test (whole model)"] * 1e3,
+                  images_per_s_by_mode={label: N / med[f"simple_test (whole model), {label}"] * 1e3 for label, _ in MODES},
+                  agreement_with_fp32_kernels=agreement)
+    for label, ag in agreement.items():
+        print(f"{label} against the exact fp32 kernels, {ag['images']} images (random-init weights): greedy strings equal "
+              f"{ag['greedy_string_agreement']:.4f}, per-position arg-max equal {ag['per_position_argmax_agreement']:.4f}", flush=True)
     print(f"planner: {plan} images per workgroup, {result['workgroups']} workgroups; HIP / torch: lstm0 "
           f"{result['lstm0_hip_over_torch']:.2f}, lstm1 {result['lstm1_hip_over_torch']:.2f}, VGG + decoder + decode "
           f"{result['tail_hip_over_torch']:.2f}; simple_test {result['images_per_s']:.0f} images / s", flush=True)

@@ -151,6 +151,8 @@ _UNIT_SIGNATURES = {"include_units/tpspp_crnn_train.h": {     # the CRNN decoder
     "tpspp_crnn_ctc_loss_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
     "tpspp_crnn_ctc_loss_fwd": ([_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
     "tpspp_crnn_ctc_loss_bwd": ([_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f], _i),
+}, "include_units/tpspp_crnn_bf16.h": {      # VeryDeepVgg's reduced modes: the max-pools on blocked bf16 / fp32 maps
+    "tpspp_crnn_maxpool_blk_fwd": ([_f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
 }}
 
 _lib = None

@@ -13,8 +13,13 @@ trains through PyTorch plus the HIP warp forward and backward of the preprocesso
 (and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
 kernels of include_units/tpspp_crnn_train.h; the VGG, with its pools, keeps training on PyTorch.
 
-Precision: the VGG and the decoder are exact fp32 in every mode.  `set_compute_dtype` of the recogniser keeps its
-meaning for the preprocessor (its localisation network) and leaves these modules alone: they have no bf16 variant.
+Precision: `set_compute_dtype` of the recogniser (None | "bf16x3" | torch.bfloat16) means for the VGG what it means for
+the NRTR backbone, and keeps its meaning for the preprocessor (its localisation network).  None, the default, is the
+exact fp32 path.  In a reduced mode the seven convolutions run on the bf16 matrix cores (`ops.conv2d_bf16`: plain bf16
+operands and maps, or the three-term split on fp32 maps), the feature maps stay in the blocked layout from conv0's output
+to conv6's input, and the four pools run on it (include_units/tpspp_crnn_bf16.h); the features leave as fp32.  The decoder
+stays exact fp32 in every mode -- the LSTM recurrence, its input projections, the embeddings and the CTC decode --, as
+NRTR's per-step projections do.
 """
 import math
 
@@ -26,6 +31,7 @@ import torch.nn.functional as Fn
 from . import ops
 from ._prepared import prepared
 from .nrtr_head import BaseConvertor, EncodeDecodeRecognizer
+from .precision import default_compute_dtype
 from .registry import BACKBONES, CONVERTORS, DECODERS, DETECTORS, TrainBackendMixin
 
 
@@ -40,7 +46,13 @@ class VeryDeepVgg(nn.Module):
     (N, 512, 1, W / 4 + 1).
 
     `leaky_relu=True` (the reference's default; crnn_tps.py sets False) has no HIP path: the convolution kernel's
-    epilogues are ReLU and GELU, so such a module always takes the PyTorch composition."""
+    epilogues are ReLU and GELU, so such a module always takes the PyTorch composition.
+
+    `compute_dtype` (not in the reference; `precision.default_compute_dtype()` when constructed) selects the arithmetic
+    of the HIP path: None the exact fp32 kernels; "bf16x3" fp32 maps and every convolution as the three-term bf16 split;
+    torch.bfloat16 bf16 operands and bf16 maps.  In the reduced modes the maps stay in the blocked layout between the
+    layers (`_forward_hip_bf16`).  `.train()`, an input that requires grad and `leaky_relu=True` take the PyTorch
+    composition whatever it says."""
 
     def __init__(self, leaky_relu=True, input_channels=3, init_cfg=None):
         super().__init__()
@@ -49,6 +61,7 @@ class VeryDeepVgg(nn.Module):
         nm = [64, 128, 256, 256, 512, 512, 512]
         self.channels = nm
         self.leaky_relu = leaky_relu
+        self.compute_dtype = default_compute_dtype()   # None: exact fp32; "bf16x3" / torch.bfloat16: `_forward_hip_bf16`
         cnn = nn.Sequential()
 
         def conv_relu(i, batch_normalization=False):
@@ -96,6 +109,24 @@ class VeryDeepVgg(nn.Module):
             return out
         return prepared(self, "vgg", convs + list(bns.values()), build)
 
+    def _hip_weights_bf16(self, x3):
+        """`_hip_weights` for the bf16 matrix cores: the same folding in fp32 (bias; BatchNorm of 2, 4, 6; conv6
+        zero-extended to 3x3), then rounded to bf16 or, `x3`, split into the hi and lo slabs of the three-term product."""
+        c = self.cnn
+        bns = {2: c.batchnorm2, 4: c.batchnorm4, 6: c.batchnorm6}
+        convs = [getattr(c, f"conv{i}") for i in range(7)]
+
+        def build():
+            out = []
+            for i, conv in enumerate(convs):
+                w, bn = conv.weight, bns.get(i)
+                if i == 6:
+                    w = Fn.pad(w.detach(), (1, 0, 1, 0))
+                out.append(ops.prep_conv_weight_bf16(w, bn=None if bn is None else ops.bn_tensors(bn), conv_bias=conv.bias,
+                                                     eps=1e-5 if bn is None else bn.eps, x3=x3))
+            return out
+        return prepared(self, "vgg_bf16x3" if x3 else "vgg_bf16", convs + list(bns.values()), build)
+
     @staticmethod
     def conv6(x, cw):
         """The 2x2 valid convolution + folded BatchNorm + ReLU of a (N, 512, 2, W) map -> (N, 512, 1, W - 1), a view of
@@ -110,6 +141,8 @@ class VeryDeepVgg(nn.Module):
             return self.cnn(x)
         ops.require_gpu(x, "VeryDeepVgg")
         ops.warn_detached_once(self, "VeryDeepVgg")
+        if self.compute_dtype is not None:
+            return self._forward_hip_bf16(x, self.compute_dtype == "bf16x3")
         cw = self._hip_weights()
         x = x.float().contiguous()
         x = ops.crnn_maxpool(ops.conv2d([x], cw[0], 1, True), 2, 2, 0)
@@ -119,6 +152,27 @@ class VeryDeepVgg(nn.Module):
         x = ops.conv2d([ops.conv2d([x], cw[4], 1, True)], cw[5], 1, True)
         x = ops.crnn_maxpool(x, (2, 2), (2, 1), (0, 1))
         return self.conv6(x, cw[6])
+
+    def _forward_hip_bf16(self, x, x3):
+        """The reduced modes: every convolution on `tpspp_conv2d_bf16_fwd` -- plain bf16 operands and bf16 maps, or, `x3`,
+        the three-term split on fp32 maps --, the maps blocked (`Blocked` / `Blocked32`) from conv0's output to conv6's
+        input, the pools on `tpspp_crnn_maxpool_blk_fwd`; no NCHW copy of an intermediate map.  The image is taken as it
+        comes, fp32 or bf16 NCHW; the result is fp32 (N, 512, 1, W / 4 + 1) as in the exact mode."""
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()
+        cw = self._hip_weights_bf16(x3)
+        dt = torch.float32 if x3 else torch.bfloat16
+
+        def conv(t, i):
+            return ops.conv2d_bf16([t], cw[i], 1, True, out_dtype=dt, out_blocked=True)
+        x = ops.crnn_maxpool_blocked(conv(x.contiguous(), 0), 2, 2, 0)
+        x = ops.crnn_maxpool_blocked(conv(x, 1), 2, 2, 0)
+        x = ops.crnn_maxpool_blocked(conv(conv(x, 2), 3), (2, 2), (2, 1), (0, 1))
+        x = ops.crnn_maxpool_blocked(conv(conv(x, 4), 5), (2, 2), (2, 1), (0, 1))
+        if x.shape[2] != 2:
+            raise ValueError(f"VeryDeepVgg: the HIP path needs an image height of 32 (a two-row map before conv6), got "
+                             f"{x.shape[2]} rows")
+        return ops.conv2d_bf16([x], cw[6], (2, 1), True, out_dtype=torch.float32)[:, :, :, :x.shape[3] - 1]
 
     def _forward_torch(self, x):
         """TEST HOOK: the PyTorch composition whatever the mode."""

@@ -683,7 +683,9 @@ class EncodeDecodeRecognizer(nn.Module):
         """One switch for the precision of the wide matrix products of every stage (not in the reference: its modules
         are fp32).  None: the exact fp32 kernels; "bf16x3": fp32 tensors, three-term bf16 split (still within the
         1e-4 bar); torch.bfloat16: bf16 operands / feature maps / encoder keys and values (control points, TPS solve,
-        grid, LayerNorms, softmaxes and the decoder's per-step projections stay fp32 in every mode)."""
+        grid, LayerNorms, softmaxes and the decoder's per-step projections stay fp32 in every mode).  For `CRNNNet` the
+        backbone is `VeryDeepVgg`, whose convolutions and pools follow the mode; its `CRNNDecoder` (LSTM recurrence, input
+        projections, embeddings) and the CTC decode stay exact fp32 in every mode."""
         if mode not in (None, "bf16x3", torch.bfloat16):
             raise ValueError('set_compute_dtype: None, "bf16x3" or torch.bfloat16')
         self.backbone.compute_dtype = mode

@@ -3034,6 +3034,27 @@ def crnn_maxpool(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
     return out
 
 
+def crnn_maxpool_blocked(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
+    """`crnn_maxpool` on a `Blocked` (bf16) or `Blocked32` (fp32) map -> the same class (`tpspp_crnn_maxpool_blk_fwd`,
+    include_units/tpspp_crnn_bf16.h): the bits `F.max_pool2d` gives on the NCHW view."""
+    if not isinstance(x, Blocked):
+        raise TypeError("crnn_maxpool_blocked: expected a Blocked or Blocked32 map")
+    _chk_gpu("crnn_maxpool_blocked input", x.t)
+    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel), _pair(stride), _pair(padding)
+    N, C, H, W = x.shape
+    if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw:
+        raise ValueError(f"crnn_maxpool_blocked: kernel {(kh, kw)} / stride {(sh, sw)} / padding {(ph, pw)} on a {H} x {W} map")
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    out = type(x)(torch.empty((N, C // 8, Ho, Wo, 8), device=x.device, dtype=x.dtype))
+    if N == 0:          # an empty batch has no device pointer to hand over
+        return out
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().tpspp_crnn_maxpool_blk_fwd(x.data_ptr(), _layout_code(x), N, C, H, W, kh, kw, sh, sw, ph, pw,
+                                                   out.data_ptr(), Ho, Wo, _stream(x.t))
+    _lib.check(rc, "tpspp_crnn_maxpool_blk_fwd")
+    return out
+
+
 CRNN_HIDDEN = 256
 CRNN_LSTM_GROUPS = (4, 8, 16)          # the accepted non-zero images_per_group of tpspp_crnn_lstm_fwd
 
