@@ -51,8 +51,8 @@ extern "C" {
                                   tpspp_augment_normalize_fwd;
                                12: no new entry point: tpspp_warp_fwd / tpspp_warp_plan_* accept TPSPP_IO_BF16 on a classic
                                   call with the prepared table (bf16 images in and out on the in-place kernel);
-                               (still 12): the CRNN recogniser's entry points are a unit of their own, crnn/tpspp_crnn.h, bound by
-                                  name; they change nothing declared here */
+                               (still 12): the CRNN recogniser's entry points, declared in tpspp_crnn.h, tpspp_crnn_train.h and
+                                  tpspp_crnn_bf16.h, are bound by name; they change nothing declared here */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */

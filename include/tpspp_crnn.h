@@ -2,11 +2,10 @@
  * tpspp_crnn.h -- the CRNN recogniser behind the classic TPS rectifier (configs/_base_/recog_models/crnn_tps.py):
  * what VeryDeepVgg, CRNNDecoder(rnn_flag=True) and CTCConvertor need beyond the entry points of tpspp.h.
  *
- * A second ABI unit next to tpspp.h (whose types, return codes and conventions apply): device pointers, no allocation,
- * no host synchronisation, work enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error();
- * every argument is checked before anything is launched.  It lives in a sub-directory of include/ and is bound by a table
- * of its own (tps_pp_amd/_lib.py: _EXT_SIGNATURES, ext_headers()): INTEGRATION.md says why.  TPSPP_ABI_VERSION is not
- * raised by it: a library that lacks one of these symbols fails to bind by name.
+ * tpspp.h's types, return codes and conventions apply: device pointers, no allocation, no host synchronisation, work
+ * enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error(); every argument is checked
+ * before anything is launched.  TPSPP_ABI_VERSION is not raised by it: a library that lacks one of these symbols fails to
+ * bind by name.
  *
  * replaces: nn.MaxPool2d(2, 2) and nn.MaxPool2d((2, 2), (2, 1), (0, 1))     backbones/very_deep_vgg.py:51-60
  *           the recurrence of nn.LSTM(nIn, 256, bidirectional=True)        layers/lstm_layer.py:10,14
@@ -20,7 +19,7 @@
 #ifndef TPSPP_CRNN_H_
 #define TPSPP_CRNN_H_
 
-#include "../tpspp.h"
+#include "tpspp.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,13 +1,12 @@
 /*
- * tpspp_crnn_bf16.h -- what VeryDeepVgg needs, beyond tpspp.h and crnn/tpspp_crnn.h, to run in the reduced-precision
+ * tpspp_crnn_bf16.h -- what VeryDeepVgg needs, beyond tpspp.h and tpspp_crnn.h, to run in the reduced-precision
  * configurations (compute_dtype "bf16x3" or torch.bfloat16): its max-pools on the blocked layouts the bf16 convolutions
  * (tpspp_conv2d_bf16_fwd) exchange, so that the feature maps stay blocked from conv0's output to conv6's input.
  *
- * A further ABI unit (tpspp.h's types, return codes and conventions apply): device pointers, no allocation, no host
- * synchronisation, work enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error(); every
- * argument is checked before anything is launched.  It lives in include_units/ and is bound by the units' table
- * (tps_pp_amd/_lib.py: _UNIT_SIGNATURES, unit_headers()).  TPSPP_ABI_VERSION is not raised by it: a library that lacks one
- * of these symbols fails to bind by name.
+ * tpspp.h's types, return codes and conventions apply: device pointers, no allocation, no host synchronisation, work
+ * enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error(); every argument is checked
+ * before anything is launched.  TPSPP_ABI_VERSION is not raised by it: a library that lacks one of these symbols fails to
+ * bind by name.
  *
  * replaces: nn.MaxPool2d(2, 2) and nn.MaxPool2d((2, 2), (2, 1), (0, 1))     backbones/very_deep_vgg.py:51-60
  * when the module runs in a reduced mode.  The convolutions of those modes are tpspp_conv2d_bf16_fwd (tpspp.h).
@@ -22,7 +21,7 @@ extern "C" {
 #endif
 
 /*
- * tpspp_crnn_maxpool_fwd (crnn/tpspp_crnn.h) on a blocked map: in (N, C / 8, H, W, 8) -> out (N, C / 8, Ho, Wo, 8), the eight
+ * tpspp_crnn_maxpool_fwd (tpspp_crnn.h) on a blocked map: in (N, C / 8, H, W, 8) -> out (N, C / 8, Ho, Wo, 8), the eight
  * channels of a group next to each other per pixel.  `layout` is tpspp_conv2d_bf16_fwd's code: 2 bf16, 3 fp32; `out` has
  * the layout of `in`.  C must be a multiple of 8; both pointers 16-byte aligned.
  *   Ho = (H + 2 ph - kh) / sh + 1, Wo = (W + 2 pw - kw) / sw + 1 (integer division; both must be >= 1 and equal the Ho, Wo

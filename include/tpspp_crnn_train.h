@@ -1,13 +1,12 @@
 /*
  * tpspp_crnn_train.h -- the training kernels of the CRNN recogniser's recurrent half: what CRNNDecoder(rnn_flag=True)
- * and CTCLoss need, beyond tpspp.h and crnn/tpspp_crnn.h, to run forward and backward on this library
+ * and CTCLoss need, beyond tpspp.h and tpspp_crnn.h, to run forward and backward on this library
  * (CRNNDecoder.set_train_backend("hip"), CTCLoss.set_train_backend("hip")).
  *
- * A further ABI unit (tpspp.h's types, return codes and conventions apply): device pointers, no allocation, no host
- * synchronisation, work enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error(); every
- * argument is checked before anything is launched.  It lives in include_units/ and is bound by a table of its own
- * (tps_pp_amd/_lib.py: _UNIT_SIGNATURES, unit_headers()): INTEGRATION.md says why.  TPSPP_ABI_VERSION is not raised by it:
- * a library that lacks one of these symbols fails to bind by name.
+ * tpspp.h's types, return codes and conventions apply: device pointers, no allocation, no host synchronisation, work
+ * enqueued on `stream`, 0 or a negative TPSPP_E* code with a message in tpspp_last_error(); every argument is checked
+ * before anything is launched.  TPSPP_ABI_VERSION is not raised by it: a library that lacks one of these symbols fails to
+ * bind by name.
  *
  * replaces: the autograd of nn.LSTM(nIn, 256, bidirectional=True)'s recurrence      layers/lstm_layer.py:10,14
  *           torch.log_softmax + nn.CTCLoss, forward and backward                    losses/ctc_loss.py:50-71
@@ -26,7 +25,7 @@ extern "C" {
 #endif
 
 /*
- * tpspp_crnn_lstm_fwd (crnn/tpspp_crnn.h: same operands, arithmetic, work division, planner and limits; `out` has the same
+ * tpspp_crnn_lstm_fwd (tpspp_crnn.h: same operands, arithmetic, work division, planner and limits; `out` has the same
  * bits) that also stores, per step, image, direction d and unit u, what the backward reads:
  *   gates (T, N, 2, 4 hidden): sigma(a_i), sigma(a_f), tanh(a_g), sigma(a_o) at [t][n][d][q hidden + u], q = 0..3;
  *   cell  (T, N, 2, hidden):   c_t.

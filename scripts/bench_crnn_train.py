@@ -1,5 +1,5 @@
 """Training the CRNN recogniser's recurrent half: `CRNNDecoder` + `CTCLoss`, forward and backward, at a batch of features
-(N, 512, 1, 26) with targets, train backend "hip" (include_units/tpspp_crnn_train.h) against "torch" (nn.LSTM, nn.Linear,
+(N, 512, 1, 26) with targets, train backend "hip" (include/tpspp_crnn_train.h) against "torch" (nn.LSTM, nn.Linear,
 log_softmax + nn.CTCLoss) on the same GPU.  Neither ratio is a pass bar; the default backend stays "torch".
 
 Rows: decoder + loss forward + backward under each backend; the parts of the HIP step on their own -- the training

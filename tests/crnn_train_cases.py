@@ -1,6 +1,6 @@
 """Cases shared by tests/test_crnn_train_host.py and tests/test_gpu_crnn_train.py (a helper module, not a test file): the CTC
 case table and a float64 restatement of the arithmetic that tpspp_crnn_ctc_loss_fwd / _bwd implement
-(include_units/tpspp_crnn_train.h), written from the header's formulas."""
+(include/tpspp_crnn_train.h), written from the header's formulas."""
 import numpy as np
 import torch
 import torch.nn.functional as F

@@ -14,14 +14,19 @@ from tps_pp_amd import _lib, build
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
 HEADER = os.path.join(INCLUDE, "tpspp.h")
-HEADERS = ("tpspp.h", "tpspp_train_attn.h", "tpspp_train_dec.h", "tpspp_train_opt.h", "tpspp_augment.h")
-# the training headers' name sets, pinned here as data (include/tpspp.h's list is long and grows: the header is its record)
+HEADERS = ("tpspp.h", "tpspp_train_attn.h", "tpspp_train_dec.h", "tpspp_train_opt.h", "tpspp_augment.h", "tpspp_crnn.h",
+           "tpspp_crnn_train.h", "tpspp_crnn_bf16.h")
+# the smaller headers' name sets, pinned here as data (include/tpspp.h's list is long and grows: the header is its record)
 PINNED = {
     "tpspp_train_attn.h": {"tpspp_attn_train_fwd", "tpspp_attn_train_bwd", "tpspp_attn_dropout_mask"},
     "tpspp_train_dec.h": {"tpspp_attn_train_fwd_ex", "tpspp_attn_train_bwd_ex", "tpspp_embed_pos_fwd",
                           "tpspp_embed_bwd_workspace_floats", "tpspp_embed_bwd", "tpspp_seq_ce_fwd", "tpspp_seq_ce_bwd"},
     "tpspp_train_opt.h": {"tpspp_mt_adam", "tpspp_mt_sumsq", "tpspp_mt_norm_finish", "tpspp_mt_zero"},
     "tpspp_augment.h": {"tpspp_augment_normalize_fwd"},
+    "tpspp_crnn.h": {"tpspp_crnn_maxpool_fwd", "tpspp_crnn_lstm_fwd", "tpspp_crnn_lstm_plan", "tpspp_crnn_ctc_decode"},
+    "tpspp_crnn_train.h": {"tpspp_crnn_lstm_train_fwd", "tpspp_crnn_lstm_bwd", "tpspp_crnn_ctc_loss_workspace_floats",
+                           "tpspp_crnn_ctc_loss_fwd", "tpspp_crnn_ctc_loss_bwd"},
+    "tpspp_crnn_bf16.h": {"tpspp_crnn_maxpool_blk_fwd"},
 }
 RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void": None, "const char*": ctypes.c_char_p}
 
@@ -50,6 +55,14 @@ def lib():
 def test_binding_table_lists_the_headers():
     assert tuple(_lib.headers()) == HEADERS
     assert sorted(n for n in os.listdir(INCLUDE) if n.endswith(".h")) == sorted(HEADERS)
+    assert not [n for n in os.listdir(INCLUDE) if os.path.isdir(os.path.join(INCLUDE, n))]
+    assert all(os.path.join(INCLUDE, h) in build._public_headers() for h in HEADERS)
+
+
+def test_symbols_of_an_unknown_header_raise():
+    for name in ("no_such_header.h", "include/tpspp.h"):      # keys are file names, not paths
+        with pytest.raises(KeyError):
+            _lib.symbols(name)
 
 
 @pytest.mark.parametrize("header", HEADERS)

@@ -1,6 +1,5 @@
 """Host side (no GPU) of the CRNN recogniser: the mirrors' state-dict keys and PyTorch paths against the reference's outputs
-(tests/golden/crnn_tps.npz), both config dicts, the second ABI unit (include/crnn/tpspp_crnn.h) held to its binding table and
-to the shared object as tests/test_capi_symbols.py holds the five headers, the argument checks of every entry point (host
+(tests/golden/crnn_tps.npz), both config dicts, the argument checks of every entry point of include/tpspp_crnn.h (host
 pointers: nothing is launched) and the LSTM launch planner restated from a case table."""
 import ctypes
 import json
@@ -17,10 +16,7 @@ from tps_pp_amd import _lib, build, build_detector
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import crnn_cases as CC  # noqa: E402
-from test_capi_symbols import HEADERS, INCLUDE, RESTYPES, declarations, header_functions  # noqa: E402
 
-CRNN_HEADER = "crnn/tpspp_crnn.h"
-PINNED = {"tpspp_crnn_maxpool_fwd", "tpspp_crnn_lstm_fwd", "tpspp_crnn_lstm_plan", "tpspp_crnn_ctc_decode"}
 TOL = 1e-6
 
 
@@ -157,28 +153,7 @@ def test_train_mode_forward_builds_a_graph_on_the_host():
     assert all(p.grad is not None for p in m.parameters())
 
 
-# ---- the second ABI unit -----------------------------------------------------------------------------------------------
-def test_crnn_header_binding_and_shared_object_agree(lib):
-    assert _lib.ext_headers() == [CRNN_HEADER] and tuple(_lib.headers()) == HEADERS       # the five stay the five
-    decl = declarations(os.path.join(INCLUDE, CRNN_HEADER))
-    assert set(decl) == set(_lib.symbols(CRNN_HEADER)) == PINNED
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name, (ret, nargs) in decl.items():
-        assert hasattr(raw, name), f"{name} missing from libtpspp_hip.so"
-        fn = getattr(lib, name)
-        assert len(fn.argtypes) == nargs, f"{name}: header has {nargs} parameters, binding {len(fn.argtypes)}"
-        assert fn.restype is RESTYPES[ret], f"{name}: header returns {ret}, binding {fn.restype}"
-    for h in HEADERS:
-        assert not set(decl) & set(header_functions(os.path.join(INCLUDE, h))), h
-        assert not set(decl) & set(_lib.symbols(h)), h
-    # every header file below include/ is one of the two tables' keys
-    found = sorted(os.path.relpath(os.path.join(d, f), INCLUDE) for d, _, fs in os.walk(INCLUDE) for f in fs if f.endswith(".h"))
-    assert found == sorted(list(HEADERS) + [CRNN_HEADER])
-    assert os.path.join(INCLUDE, CRNN_HEADER) in build._public_headers()
-    # the unit adds names only: the library's ABI number is the five headers' (tests/test_warp_bf16_host.py pins it)
-    assert lib.tpspp_abi_version() == _lib.ABI_VERSION
-
-
+# ---- the entry points of include/tpspp_crnn.h ----------------------------------------------------------------------------
 def host(n, ctype=ctypes.c_float):
     buf = (ctype * n)()
     return buf, ctypes.cast(buf, ctypes.c_void_p).value
@@ -255,7 +230,7 @@ PLAN_CASES = [
 
 
 def plan(N, g, cus):
-    """The planner of include/crnn/tpspp_crnn.h restated: -> (images per workgroup, branch)."""
+    """The planner of include/tpspp_crnn.h restated: -> (images per workgroup, branch)."""
     if N < 0 or g not in (0, 4, 8, 16):
         return -22, "refused"
     if g:

@@ -1,8 +1,6 @@
-"""Host side (no GPU) of the CRNN decoder's and the CTC loss's HIP training paths: every ABI unit outside include/
-(`_lib.unit_headers()`, include_units/) held to its binding table and to the shared object -- generically, so that a further
-unit needs no change here --, the argument checks of the new entry points (host pointers: nothing is launched), the
-workspace query restated, the backend switch, and the gradient formula the CTC kernels implement restated in float64
-against autograd."""
+"""Host side (no GPU) of the CRNN decoder's and the CTC loss's HIP training paths: the argument checks of the entry points of
+include/tpspp_crnn_train.h (host pointers: nothing is launched), the workspace query restated, the backend switch, and the
+gradient formula the CTC kernels implement restated in float64 against autograd."""
 import ctypes
 import os
 import sys
@@ -16,12 +14,9 @@ import tps_pp_amd
 from tps_pp_amd import _lib, build, build_detector
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import crnn_cases as CC  # noqa: E402
-from test_capi_symbols import HEADERS, INCLUDE, RESTYPES, declarations  # noqa: E402
 
-UNITS = os.path.join(ROOT, "include_units")
 TOL = 1e-6
 
 
@@ -36,43 +31,7 @@ def G():
     return np.load(os.path.join(HERE, "golden", "crnn_tps.npz"))
 
 
-# ---- the units -----------------------------------------------------------------------------------------------------------
-def test_unit_headers_bindings_and_shared_object_agree(lib):
-    units = _lib.unit_headers()
-    assert units and len(set(units)) == len(units)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    others = {h: set(declarations(os.path.join(INCLUDE, h))) | set(_lib.symbols(h)) for h in list(HEADERS) + _lib.ext_headers()}
-    assert len(others) == 6
-    seen = {}
-    for unit in units:
-        path = os.path.join(ROOT, unit)
-        assert os.path.isfile(path) and path in build._public_headers(), unit
-        decl = declarations(path)
-        assert decl, f"no declarations parsed from {unit}"
-        assert set(decl) == set(_lib.symbols(unit)), unit
-        for name, (ret, nargs) in decl.items():
-            assert hasattr(raw, name), f"{name} missing from libtpspp_hip.so"
-            fn = getattr(lib, name)
-            assert len(fn.argtypes) == nargs, f"{name}: header has {nargs} parameters, binding {len(fn.argtypes)}"
-            assert fn.restype is RESTYPES[ret], f"{name}: header returns {ret}, binding {fn.restype}"
-            assert name not in seen, f"{name} is declared by {seen.get(name)} and {unit}"
-            seen[name] = unit
-        for h, names in others.items():
-            assert not set(decl) & names, (unit, h)
-    # every header file below include_units/ is a key of the table
-    found = sorted(os.path.relpath(os.path.join(d, f), ROOT) for d, _, fs in os.walk(UNITS) for f in fs if f.endswith(".h"))
-    assert found == sorted(units)
-    assert lib.tpspp_abi_version() == _lib.ABI_VERSION         # a unit adds names only
-
-
-def test_the_other_tables_are_unchanged():
-    assert tuple(_lib.headers()) == HEADERS
-    assert _lib.ext_headers() == ["crnn/tpspp_crnn.h"]
-    assert not set(_lib.unit_headers()) & (set(_lib.headers()) | set(_lib.ext_headers()))
-    with pytest.raises(KeyError):
-        _lib.symbols("no_such_header.h")
-
-
+# ---- the entry points of include/tpspp_crnn_train.h ----------------------------------------------------------------------
 def host(n, ctype=ctypes.c_float):
     buf = (ctype * n)()
     return buf, ctypes.cast(buf, ctypes.c_void_p).value

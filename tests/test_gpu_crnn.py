@@ -1,4 +1,4 @@
-"""-m gpu: the CRNN recogniser's kernels (include/crnn/tpspp_crnn.h) and modules (tps_pp_amd/crnn.py).
+"""-m gpu: the CRNN recogniser's kernels (include/tpspp_crnn.h) and modules (tps_pp_amd/crnn.py).
 
 Every kernel output is allocated through tests/guarded_alloc.py: nothing is written outside it and every element of it is
 written.  Comparisons against float64 use the project's bar, restated unchanged in tests/test_gpu_train_primitives.py

@@ -1,5 +1,5 @@
 """-m gpu: VeryDeepVgg in its reduced-precision modes (compute_dtype "bf16x3" / torch.bfloat16): the max-pools on blocked maps
-(include_units/tpspp_crnn_bf16.h), the seven convolutions at the VGG's own shapes on `tpspp_conv2d_bf16_fwd`, and the module.
+(include/tpspp_crnn_bf16.h), the seven convolutions at the VGG's own shapes on `tpspp_conv2d_bf16_fwd`, and the module.
 
 Every kernel output is allocated through tests/guarded_alloc.py: nothing is written outside it and every element of it is
 written.  The convolutions' bars are those of tests/test_gpu_conv_bf16.py, restated: operands rounded to bf16 on both sides,

@@ -1,4 +1,4 @@
-"""-m gpu: the HIP training paths of the CRNN decoder and the CTC loss (include_units/tpspp_crnn_train.h, tps_pp_amd/crnn.py,
+"""-m gpu: the HIP training paths of the CRNN decoder and the CTC loss (include/tpspp_crnn_train.h, tps_pp_amd/crnn.py,
 tps_pp_amd/losses.py).
 
 Every entry point runs inside tests/guarded_alloc.py: inputs, outputs, saved tensors and workspaces lie between guard bands

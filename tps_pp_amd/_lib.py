@@ -1,19 +1,8 @@
 """ctypes binding of libtpspp_hip.so.  The C ABI is the headers under include/; `_SIGNATURES` maps each header's file name
 to the `{name: (argtypes, restype)}` of the functions it declares, `headers()` lists them and `symbols(header)` gives one
 header's names (tests/test_capi_symbols.py holds every header, this table and the shared object to each other).  A new
-entry point goes under the header that declares it; a new header is a new key.
-
-`_EXT_SIGNATURES` is a second table of the same form for the headers in sub-directories of include/ (keys are paths relative
-to include/, `ext_headers()` lists them): tests/test_capi_symbols.py pins `headers()` and the files directly under include/
-to the five headers above, so the CRNN unit is declared, bound and tested beside them (tests/test_crnn_host.py).
-`_UNIT_SIGNATURES` is a third table of the same form for the units outside include/ (keys are paths relative to the
-repository root, `unit_headers()` lists them): tests/test_crnn_host.py closes include/ and `ext_headers()`, so a further unit
-is a header under include_units/ and a key here, held to the same rules generically by tests/test_crnn_train_host.py.
-`symbols()` and `lib()` serve all three tables.
-
-The product has no fallback: if the library is missing or fails to load, importing an op raises.
-PyTorch is used only for device memory and streams -- tensors cross this boundary as raw pointers.
-"""
+entry point goes under the header that declares it; a new header is a new key.  There is no fallback: if the library is
+missing or fails to load, `lib()` raises.  Tensors cross this boundary as raw pointers."""
 import ctypes
 import os
 
@@ -134,24 +123,18 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_mt_zero": ([_f, _i, _f, _i, _i, _i, _f], _i),
 }, "tpspp_augment.h": {         # the train pipeline's resize + augmentation + normalisation kernel
     "tpspp_augment_normalize_fwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _i, _f, _f, _i, _i, _f], _i),
-}}
-
-# include/<sub-directory>/<header> -> {function: (argtypes, restype)}
-_EXT_SIGNATURES = {"crnn/tpspp_crnn.h": {     # the CRNN recogniser: rectangular max-pool, LSTM recurrence, CTC greedy decode
+}, "tpspp_crnn.h": {            # the CRNN recogniser: rectangular max-pool, LSTM recurrence, CTC greedy decode
     "tpspp_crnn_maxpool_fwd": ([_f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
     "tpspp_crnn_lstm_fwd": ([_f, _f, _f, _i, _i, _i, _i, _f], _i),
     "tpspp_crnn_lstm_plan": ([_i, _i, _i], _i),
     "tpspp_crnn_ctc_decode": ([_f, _f, _i, _i, _i, _i, _f, _f, _f], _i),
-}}
-
-# <path from the repository root> -> {function: (argtypes, restype)}
-_UNIT_SIGNATURES = {"include_units/tpspp_crnn_train.h": {     # the CRNN decoder's and the CTC loss's training kernels
+}, "tpspp_crnn_train.h": {      # the CRNN decoder's and the CTC loss's training kernels
     "tpspp_crnn_lstm_train_fwd": ([_f, _f, _f, _f, _f, _i, _i, _i, _i, _f], _i),
     "tpspp_crnn_lstm_bwd": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f], _i),
     "tpspp_crnn_ctc_loss_workspace_floats": ([_i, _i, _i], ctypes.c_size_t),
     "tpspp_crnn_ctc_loss_fwd": ([_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
     "tpspp_crnn_ctc_loss_bwd": ([_f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _f, _f], _i),
-}, "include_units/tpspp_crnn_bf16.h": {      # VeryDeepVgg's reduced modes: the max-pools on blocked bf16 / fp32 maps
+}, "tpspp_crnn_bf16.h": {       # VeryDeepVgg's reduced modes: the max-pools on blocked bf16 / fp32 maps
     "tpspp_crnn_maxpool_blk_fwd": ([_f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
 }}
 
@@ -167,23 +150,9 @@ def headers():
     return list(_SIGNATURES)
 
 
-def ext_headers():
-    """Paths, relative to include/, of the headers in its sub-directories (the second table)."""
-    return list(_EXT_SIGNATURES)
-
-
-def unit_headers():
-    """Paths, relative to the repository root, of the units' headers outside include/ (the third table)."""
-    return list(_UNIT_SIGNATURES)
-
-
 def symbols(header):
-    """Names the header declares (kept in sync by tests/test_capi_symbols.py, tests/test_crnn_host.py and
-    tests/test_crnn_train_host.py)."""
-    for table in (_SIGNATURES, _EXT_SIGNATURES, _UNIT_SIGNATURES):
-        if header in table:
-            return sorted(table[header])
-    raise KeyError(header)
+    """Names the header declares (kept in sync by tests/test_capi_symbols.py)."""
+    return sorted(_SIGNATURES[header])
 
 
 def lib():
@@ -195,7 +164,7 @@ def lib():
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -m tps_pp_amd.build`). There is no CPU or PyTorch fallback.")
         L = ctypes.CDLL(LIB_PATH)
-        for table in (*_SIGNATURES.values(), *_EXT_SIGNATURES.values(), *_UNIT_SIGNATURES.values()):
+        for table in _SIGNATURES.values():
             for name, (argtypes, restype) in table.items():
                 fn = getattr(L, name)      # AttributeError if the ABI lost a symbol
                 fn.argtypes = argtypes

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libtpspp_hip.so")
-INCLUDE_DIRS = [os.path.join(ROOT, "include"), os.path.join(ROOT, "include_units")]
+INCLUDE_DIRS = [os.path.join(ROOT, "include")]
 ARCH = "gfx950"
 
 # -ffp-contract=off: hipcc's default (fast) would fuse a*b+c on its own; the parity contract
@@ -32,8 +32,7 @@ def sources():
 
 
 def _public_headers():
-    # include/ with its sub-directories (include/crnn/tpspp_crnn.h) and the further units (include_units/)
-    return sorted(os.path.join(d, f) for inc in INCLUDE_DIRS for d, _, files in os.walk(inc) for f in files if f.endswith(".h"))
+    return sorted(os.path.join(inc, f) for inc in INCLUDE_DIRS for f in os.listdir(inc) if f.endswith(".h"))
 
 
 def _stale():

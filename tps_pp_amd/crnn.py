@@ -7,17 +7,17 @@ Mirrors of `backbones/very_deep_vgg.py`, `layers/lstm_layer.py`, `decoders/crnn_
 
 Which path a call takes is `LocalizationNetwork`'s rule.  `.eval()` on a GPU tensor that carries no gradient runs the HIP
 kernels: the 3x3 convolutions (BatchNorm folded) on `ops.conv2d`, the pools, the LSTM recurrence and the CTC decode on
-the kernels of include/crnn/tpspp_crnn.h, every Linear on `tpspp_mm_f32`; a CPU tensor raises.  `.train()`, or an input
+the kernels of include/tpspp_crnn.h, every Linear on `tpspp_mm_f32`; a CPU tensor raises.  `.train()`, or an input
 that requires grad, runs the PyTorch composition of the same layers (`nn.LSTM`, `nn.Linear`, `nn.Conv2d`): the model
 trains through PyTorch plus the HIP warp forward and backward of the preprocessor.  `CRNNDecoder.set_train_backend("hip")`
 (and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
-kernels of include_units/tpspp_crnn_train.h; the VGG, with its pools, keeps training on PyTorch.
+kernels of include/tpspp_crnn_train.h; the VGG, with its pools, keeps training on PyTorch.
 
 Precision: `set_compute_dtype` of the recogniser (None | "bf16x3" | torch.bfloat16) means for the VGG what it means for
 the NRTR backbone, and keeps its meaning for the preprocessor (its localisation network).  None, the default, is the
 exact fp32 path.  In a reduced mode the seven convolutions run on the bf16 matrix cores (`ops.conv2d_bf16`: plain bf16
 operands and maps, or the three-term split on fp32 maps), the feature maps stay in the blocked layout from conv0's output
-to conv6's input, and the four pools run on it (include_units/tpspp_crnn_bf16.h); the features leave as fp32.  The decoder
+to conv6's input, and the four pools run on it (include/tpspp_crnn_bf16.h); the features leave as fp32.  The decoder
 stays exact fp32 in every mode -- the LSTM recurrence, its input projections, the embeddings and the CTC decode --, as
 NRTR's per-step projections do.
 """

@@ -1,10 +1,10 @@
-// The CRNN recogniser's kernels (include/crnn/tpspp_crnn.h): rectangular max-pooling, the recurrence of a bidirectional
+// The CRNN recogniser's kernels (include/tpspp_crnn.h): rectangular max-pooling, the recurrence of a bidirectional
 // LSTM layer and the CTC greedy decode.
 // Replaces: nn.MaxPool2d in backbones/very_deep_vgg.py:51-60, nn.LSTM's recurrence in layers/lstm_layer.py:10,14 and
 // F.softmax + topk(1) + the collapse scan of convertors/ctc.py:110-137 (reference).
 #include <climits>
 
-#include "crnn/tpspp_crnn.h"
+#include "tpspp_crnn.h"
 #include "tpspp_common.h"
 #include "tpspp_crnn_cell.h"
 #include "tpspp_dev.h"

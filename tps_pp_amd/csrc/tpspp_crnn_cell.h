@@ -3,7 +3,7 @@
 // body is one template: Save = false is tpspp_crnn_lstm_fwd as it always was, Save = true also stores what the backward
 // through time reads.  The two instantiations perform the same operations on h, c and out, in the same order.
 #pragma once
-#include "crnn/tpspp_crnn.h"
+#include "tpspp_crnn.h"
 #include "tpspp_dev.h"
 
 namespace tpspp_crnn_cell {

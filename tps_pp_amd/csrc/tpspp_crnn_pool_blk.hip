@@ -1,4 +1,4 @@
-// Max-pooling on the blocked feature maps the bf16 convolutions exchange (include_units/tpspp_crnn_bf16.h): (N, C/8, H, W, 8)
+// Max-pooling on the blocked feature maps the bf16 convolutions exchange (include/tpspp_crnn_bf16.h): (N, C/8, H, W, 8)
 // in bf16 (layout code 2) or fp32 (code 3), so that VeryDeepVgg's maps stay blocked between its convolutions in the reduced
 // modes.  Memory-bound: one thread per (image, channel group, output pixel), a window position is one 16-byte load (bf16) or
 // two (fp32), the result as many 16-byte stores; consecutive lanes take consecutive output columns, i.e. consecutive

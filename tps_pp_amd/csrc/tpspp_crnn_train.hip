@@ -1,8 +1,8 @@
-// The training kernels of the CRNN recogniser's recurrent half (include_units/tpspp_crnn_train.h): the LSTM recurrence that
+// The training kernels of the CRNN recogniser's recurrent half (include/tpspp_crnn_train.h): the LSTM recurrence that
 // keeps its gates and cell states, its backward through time, and the CTC loss forward and backward on raw logits.
 // Replaces: the autograd of nn.LSTM's recurrence in layers/lstm_layer.py:10,14 and torch.log_softmax + nn.CTCLoss of
 // losses/ctc_loss.py:50-71 (reference).
-#include "crnn/tpspp_crnn.h"
+#include "tpspp_crnn.h"
 #include "tpspp_crnn_train.h"
 #include "tpspp_common.h"
 #include "tpspp_crnn_cell.h"

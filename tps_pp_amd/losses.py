@@ -86,7 +86,7 @@ class CTCLoss(TrainBackendMixin, nn.Module):
     """`losses/ctc_loss.py`: `log_softmax` over the classes and `nn.CTCLoss` on (T, N, C); flattened targets by default,
     else targets padded with `blank` and input lengths from the valid ratios; target lengths clamped to 1 .. T.
     -> {'loss_ctc': tensor}.  PyTorch's kernels, or with `set_train_backend("hip")` and logits on the GPU the kernels of
-    include_units/tpspp_crnn_train.h (the `ignore_index` that `EncodeDecodeRecognizer` adds to every loss config is accepted
+    include/tpspp_crnn_train.h (the `ignore_index` that `EncodeDecodeRecognizer` adds to every loss config is accepted
     and unused, as in the reference)."""
 
     def __init__(self, flatten=True, blank=0, reduction="mean", zero_infinity=False, **kwargs):

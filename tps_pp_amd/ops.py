@@ -3013,7 +3013,7 @@ def decoder_layer_autograd(x, out_enc, lyr, key_mask=None, valid_len=None, drop_
     return x + Fn.dropout(f, drop_p, drop_p > 0)
 
 
-# ---- the CRNN recogniser (include/crnn/tpspp_crnn.h, tpspp_crnn.hip) ---------------------------------------------------
+# ---- the CRNN recogniser (include/tpspp_crnn.h, tpspp_crnn.hip) ---------------------------------------------------
 def _pair(v):
     return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
 
@@ -3036,7 +3036,7 @@ def crnn_maxpool(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
 
 def crnn_maxpool_blocked(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
     """`crnn_maxpool` on a `Blocked` (bf16) or `Blocked32` (fp32) map -> the same class (`tpspp_crnn_maxpool_blk_fwd`,
-    include_units/tpspp_crnn_bf16.h): the bits `F.max_pool2d` gives on the NCHW view."""
+    include/tpspp_crnn_bf16.h): the bits `F.max_pool2d` gives on the NCHW view."""
     if not isinstance(x, Blocked):
         raise TypeError("crnn_maxpool_blocked: expected a Blocked or Blocked32 map")
     _chk_gpu("crnn_maxpool_blocked input", x.t)
@@ -3125,7 +3125,7 @@ def crnn_ctc_decode(logits, decode_len, blank=0):
     return host[:N * T].reshape(N, T), host[N * T:].view("float32").reshape(N, T)
 
 
-# ---- training of the CRNN decoder and the CTC loss (include_units/tpspp_crnn_train.h, tpspp_crnn_train.hip) --------------
+# ---- training of the CRNN decoder and the CTC loss (include/tpspp_crnn_train.h, tpspp_crnn_train.hip) --------------
 def _lstm_operand(who, name, t, shape_tail, T=None, N=None):
     t = _chk(f"{who} {name}", t, 2 + len(shape_tail))
     if tuple(t.shape[2:]) != tuple(shape_tail) or (T is not None and tuple(t.shape[:2]) != (T, N)):
