@@ -52,7 +52,9 @@ extern "C" {
                                12: no new entry point: tpspp_warp_fwd / tpspp_warp_plan_* accept TPSPP_IO_BF16 on a classic
                                   call with the prepared table (bf16 images in and out on the in-place kernel);
                                (still 12): the CRNN recogniser's entry points, declared in tpspp_crnn.h, tpspp_crnn_train.h and
-                                  tpspp_crnn_bf16.h, are bound by name; they change nothing declared here */
+                                  tpspp_crnn_bf16.h, are bound by name; they change nothing declared here;
+                               (still 12): the classic rectifier's training kernels tpspp_bn_pool2x2_fwd / _bwd_reduce
+                                  (+ _workspace_floats) / _bwd_data and tpspp_global_avgpool_bwd, bound by name */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -569,6 +571,60 @@ int tpspp_bn_bwd_data(const float* dy, const float* y, int relu, const float* za
                       const float* mean_b, const float* rstd_b, const float* gamma_b, const float* sum_dr_xb, int train_b,
                       float* dzb, const float* sum_dr, float* dres, int dres_mode, int N, int C, int HW,
                       tpspp_stream_t stream);
+
+/*
+ * BatchNorm + ReLU + MaxPool2d(2, 2) in one pass, forward and backward, and the backward of AdaptiveAvgPool2d(1) (still ABI
+ * 12, bound by name; the classic rectifier's train backend "hip", tpspp_bn_pool_train.hip).  ops.bn_pool_autograd composes
+ * a pooled layer of the localisation network from tpspp_conv2d_fwd (relu = 0), tpspp_bn_train_stats / _eval_stats, the
+ * entry points below and tpspp_conv2d_bwd_weight / _bwd_data (relu = 0).  Conventions of the block above: fp32 NCHW,
+ * N*C*H*W < 2^31, C <= 65535, every argument checked before any launch, N == 0 returns 0 and launches nothing, no
+ * allocation, no host synchronisation, no atomics.
+ *   a(v) = relu((v - mean_c) (gamma_c rstd_c) + beta_c), tpspp_bn_apply_fwd's expression bit for bit.
+ *   A 2x2 window is scanned row by row from its first element with ATen's rule (v replaces m if v > m or v != v); the
+ *   selected element is the last one that replaced m: the first of equal maxima wins, a NaN wins.
+ * No selector and no activated full-resolution map is stored: both backward passes read z anyway and repeat the scan.
+ */
+
+/*
+ * p (N, C, H/2, W/2) = the scan of a(z) over each window; H, W >= 2, an odd last row / column belongs to no window.  The
+ * bits of tpspp_maxpool2x2_fwd(tpspp_bn_apply_fwd(z, ..., relu = 1)).
+ * replaces: nn.BatchNorm2d + nn.ReLU(True) + nn.MaxPool2d(2, 2)   preprocessor/tps_preprocessor.py:101-128
+ */
+int tpspp_bn_pool2x2_fwd(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta, int N,
+                         int C, int H, int W, float* p, tpspp_stream_t stream);
+
+/* Floats of workspace tpspp_bn_pool2x2_bwd_reduce needs: S * C * 2, S = ceil(N*H*W / 4096) (0 for non-positive sizes). */
+size_t tpspp_bn_pool2x2_bwd_reduce_workspace_floats(int N, int C, int H, int W);
+
+/*
+ * dr[n][c][y][x] = dp[n][c][y/2][x/2] where (y, x) is its window's selected element and a(z) > 0 there, +0 elsewhere (the
+ * uncovered odd row / column included); per channel over all M = N*H*W positions
+ *   sum_dr = sum dr,  sum_dr_x = sum dr xhat   (xhat = (z - mean) rstd): the beta and gamma gradients.
+ * Fixed split as tpspp_bn_bwd_reduce: S slices from the sizes alone (slice s holds the channel's windows 1024 s .. 1024 s +
+ * 1023), partials in ws (ws_floats >= tpspp_bn_pool2x2_bwd_reduce_workspace_floats(...), checked), added in slice order
+ * in fp64 by a second launch.
+ * replaces: the autograd of nn.MaxPool2d, nn.ReLU and nn.BatchNorm2d (weight, bias)   preprocessor/tps_preprocessor.py:101-128
+ */
+int tpspp_bn_pool2x2_bwd_reduce(const float* dp, const float* z, const float* mean, const float* rstd, const float* gamma,
+                                const float* beta, int N, int C, int H, int W, float* sum_dr, float* sum_dr_x, float* ws,
+                                size_t ws_floats, tpspp_stream_t stream);
+
+/*
+ * dz (N, C, H, W), every element written:
+ *   train = 1 (batch statistics):   dz = gamma rstd (dr - sum_dr / M - xhat sum_dr_x / M)
+ *   train = 0 (running statistics): dz = gamma rstd dr; sum_dr and sum_dr_x may be NULL (required with train = 1, checked)
+ * A zero dp gives dz == +0 bit for bit in both modes.
+ * replaces: the autograd of nn.MaxPool2d, nn.ReLU and nn.BatchNorm2d (input)   preprocessor/tps_preprocessor.py:101-128
+ */
+int tpspp_bn_pool2x2_bwd_data(const float* dp, const float* z, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, const float* sum_dr, const float* sum_dr_x, int train, int N, int C, int H,
+                              int W, float* dz, tpspp_stream_t stream);
+
+/*
+ * dx[n][c][:][:] = g[n][c] / (float)(H*W)   (g (N, C), dx (N, C, H, W))
+ * replaces: the autograd of nn.AdaptiveAvgPool2d(1)   preprocessor/tps_preprocessor.py:101-128
+ */
+int tpspp_global_avgpool_bwd(const float* g, int N, int C, int H, int W, float* dx, tpspp_stream_t stream);
 
 
 

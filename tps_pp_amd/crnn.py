@@ -11,7 +11,9 @@ the kernels of include/tpspp_crnn.h, every Linear on `tpspp_mm_f32`; a CPU tenso
 that requires grad, runs the PyTorch composition of the same layers (`nn.LSTM`, `nn.Linear`, `nn.Conv2d`): the model
 trains through PyTorch plus the HIP warp forward and backward of the preprocessor.  `CRNNDecoder.set_train_backend("hip")`
 (and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
-kernels of include/tpspp_crnn_train.h; the VGG, with its pools, keeps training on PyTorch.
+kernels of include/tpspp_crnn_train.h, and `TPSPreprocessor.set_train_backend("hip")` the preprocessor's localisation network
+onto HIP kernels (`CRNNNet.set_train_backend("torch", preprocessor="hip", decoder="hip", loss="hip")` sets all three); the VGG,
+with its pools, keeps training on PyTorch.
 
 Precision: `set_compute_dtype` of the recogniser (None | "bf16x3" | torch.bfloat16) means for the VGG what it means for
 the NRTR backbone, and keeps its meaning for the preprocessor (its localisation network).  None, the default, is the

@@ -21,6 +21,7 @@
 // Replaces (reference, mmocr/models/textrecog/): nn.BatchNorm2d (training mode, running statistics), the residual add and
 // nn.ReLU of backbones/resnet_v2_large.py and layers/conv_layer.py:12-33, forward and autograd.
 #include "tpspp_common.h"
+#include "tpspp_dev.h"
 
 #include <math.h>
 
@@ -42,22 +43,7 @@ __device__ __forceinline__ unsigned chan_off(unsigned m, unsigned C, unsigned HW
     return (n * C + c) * HW + (m - n * HW);
 }
 
-// deterministic sums over the 256 threads of a workgroup (butterfly within the wavefront, then the four wavefronts in order)
-template <int K>
-__device__ __forceinline__ void block_sums(float (&v)[K], float (*red)[4])
-{
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float s = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
-        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-    __syncthreads();
-}
+using tpspp_dev::block_sums;
 
 // ------------------------------------------------------------------------------------------------------------------
 // statistics: slice s of channel c -> ws[(s * C + c) * 3 + {0, 1, 2}] = (count, mean, M2)

@@ -72,6 +72,24 @@ __device__ __forceinline__ float wave_max(float v)
     return v;
 }
 
+// deterministic sums over the 256 threads of a workgroup (butterfly within the wavefront, then the four wavefronts in
+// order); red: K x 4 floats of LDS.  Every thread ends with the same bits.
+template <int K>
+__device__ __forceinline__ void block_sums(float (&v)[K], float (*red)[4])
+{
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float s = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s = s + __shfl_xor(s, o, 64);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+    __syncthreads();
+}
+
 __device__ __forceinline__ float sigmoidf(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 }  // namespace tpspp_dev

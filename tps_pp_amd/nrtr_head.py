@@ -698,17 +698,20 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
-    def set_train_backend(self, mode, backbone=None, encoder=None, decoder=None, loss=None):
+    def set_train_backend(self, mode, backbone=None, encoder=None, decoder=None, loss=None, preprocessor=None):
         """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
         "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).
         backbone: None leaves the backbone's train backend as it is; "torch" or "hip" sets it as well
         (ResNetABI_v2_large.set_train_backend).  encoder, decoder, loss: the same for the encoder
         (NRTREncoder.set_train_backend), the decoder (NRTRDecoder.set_train_backend) and the loss
-        (losses._SequenceLoss.set_train_backend).  No effect on the eval path."""
+        (losses._SequenceLoss.set_train_backend).  preprocessor: the same for the classic rectifier in front of the
+        backbone (TPSPreprocessor.set_train_backend: its localisation network's training graph).  No effect on the eval
+        path."""
         if mode not in ("torch", "hip", "hip_all"):
             raise ValueError(f'set_train_backend: "torch", "hip" or "hip_all", got {mode!r}')
         parts = (("backbone", backbone, self.backbone), ("encoder", encoder, self.encoder),
-                 ("decoder", decoder, self.decoder), ("loss", loss, self.loss))
+                 ("decoder", decoder, self.decoder), ("loss", loss, self.loss),
+                 ("preprocessor", preprocessor, self.preprocessor))
         for name, val, part in parts:                        # a call that fails changes nothing: every check comes first
             if val is not None:
                 if val not in ("torch", "hip"):

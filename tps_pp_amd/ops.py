@@ -2401,6 +2401,193 @@ def bn_block_autograd(x, blk, cws=None, name="block"):
                                   blk.bn2.bias, wd, gd, bd, (tuple(cws), (kst1, kst2, kstd), (s1, s2, sd)))
 
 
+# ---- BatchNorm + ReLU + MaxPool2d(2, 2) in one pass (tpspp_bn_pool_train.hip): training the classic rectifier's
+# localisation network (TPSPreprocessor.set_train_backend("hip")) -----------------------------------------------------------
+def _bn_pool_args(who, z, stats, gamma, beta):
+    """z (N, C, H, W) with H, W >= 2 and its per-channel (mean, rstd, gamma, beta), checked."""
+    z = _chk(f"{who} z", z, 4)
+    N, C, H, W = z.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"{who}: a 2x2 window needs H, W >= 2, got {tuple(z.shape)}")
+    vecs = [_chk_vec(who, n, t, C, z.device) for n, t in zip(("mean", "rstd", "gamma", "beta"), (*stats, gamma, beta))]
+    return z, (N, C, H, W), vecs
+
+
+def _chk_pooled_grad(who, dp, dims, dev):
+    N, C, H, W = dims
+    dp = _chk(f"{who} dp", dp, 4)
+    if tuple(dp.shape) != (N, C, H // 2, W // 2) or dp.device != dev:
+        raise ValueError(f"{who}: dp must be {(N, C, H // 2, W // 2)} on {dev}, got {tuple(dp.shape)} on {dp.device}")
+    return dp
+
+
+def bn_pool2x2_fwd(z, stats, gamma, beta):
+    """maxpool2x2(relu(gamma (z - mean) rstd + beta)) as one kernel (`tpspp_bn_pool2x2_fwd`): (N, C, H/2, W/2) with the bits
+    of `maxpool2x2(bn_apply(z, stats, gamma, beta, relu=True))`; the activated map is never written."""
+    who = "bn_pool2x2_fwd"
+    z, (N, C, H, W), vecs = _bn_pool_args(who, z, stats, gamma, beta)
+    p = torch.empty((N, C, H // 2, W // 2), device=z.device, dtype=torch.float32)
+    with torch.cuda.device(z.device):
+        rc = _lib.lib().tpspp_bn_pool2x2_fwd(_ptr(z), *[_ptr(t) for t in vecs], N, C, H, W, _ptr(p), _stream(z))
+    _lib.check(rc, "tpspp_bn_pool2x2_fwd")
+    return p
+
+
+def bn_pool2x2_bwd_reduce_workspace_floats(N, C, H, W):
+    """Floats of workspace `bn_pool2x2_bwd_reduce` needs: 2 per channel and slice of 4096 elements of N*H*W."""
+    return int(_lib.lib().tpspp_bn_pool2x2_bwd_reduce_workspace_floats(int(N), int(C), int(H), int(W)))
+
+
+def bn_pool2x2_bwd_reduce(dp, z, stats, gamma, beta):
+    """(sum dr, sum dr xhat) per channel (`tpspp_bn_pool2x2_bwd_reduce`), dr = dp at each window's selected element where
+    the activation is positive and 0 elsewhere: the beta and gamma gradients.  Fixed split, bitwise reproducible."""
+    who = "bn_pool2x2_bwd_reduce"
+    z, (N, C, H, W), vecs = _bn_pool_args(who, z, stats, gamma, beta)
+    dev = z.device
+    dp = _chk_pooled_grad(who, dp, (N, C, H, W), dev)
+    sdr = torch.empty((C,), device=dev, dtype=torch.float32)
+    sx = torch.empty((C,), device=dev, dtype=torch.float32)
+    nws = bn_pool2x2_bwd_reduce_workspace_floats(N, C, H, W)
+    ws = _ws(nws, dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_pool2x2_bwd_reduce(_ptr(dp), _ptr(z), *[_ptr(t) for t in vecs], N, C, H, W, _ptr(sdr),
+                                                    _ptr(sx), _ptr(ws), nws, _stream(dp))
+    _lib.check(rc, "tpspp_bn_pool2x2_bwd_reduce")
+    return sdr, sx
+
+
+def bn_pool2x2_bwd_data(dp, z, stats, gamma, beta, sums=None, train=True):
+    """dz (N, C, H, W) of `bn_pool2x2_fwd` (`tpspp_bn_pool2x2_bwd_data`).  sums = `bn_pool2x2_bwd_reduce`'s pair, needed
+    with train=True (batch statistics); train=False (running statistics): dz = gamma rstd dr."""
+    who = "bn_pool2x2_bwd_data"
+    z, (N, C, H, W), vecs = _bn_pool_args(who, z, stats, gamma, beta)
+    dev = z.device
+    dp = _chk_pooled_grad(who, dp, (N, C, H, W), dev)
+    sdr = sx = None
+    if train:
+        if sums is None:
+            raise ValueError("bn_pool2x2_bwd_data: a training-mode BatchNorm needs the sums of bn_pool2x2_bwd_reduce")
+        sdr, sx = (_chk_vec(who, n, t, C, dev) for n, t in zip(("sum_dr", "sum_dr_x"), sums))
+    dz = torch.empty_like(z)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().tpspp_bn_pool2x2_bwd_data(_ptr(dp), _ptr(z), *[_ptr(t) for t in vecs], _ptr(sdr), _ptr(sx),
+                                                  int(bool(train)), N, C, H, W, _ptr(dz), _stream(dp))
+    _lib.check(rc, "tpspp_bn_pool2x2_bwd_data")
+    return dz
+
+
+def global_avgpool_bwd(g, hw):
+    """Backward of `global_avgpool` (`tpspp_global_avgpool_bwd`): g (N, C) -> (N, C, H, W) = g / (H W), hw = (H, W)."""
+    g = _chk("global_avgpool_bwd g", g, 2)
+    N, C = g.shape
+    H, W = int(hw[0]), int(hw[1])
+    dx = torch.empty((N, C, H, W), device=g.device, dtype=torch.float32)
+    with torch.cuda.device(g.device):
+        rc = _lib.lib().tpspp_global_avgpool_bwd(_ptr(g), N, C, H, W, _ptr(dx), _stream(g))
+    _lib.check(rc, "tpspp_global_avgpool_bwd")
+    return dx
+
+
+class _BnPoolFunction(torch.autograd.Function):
+    """p = maxpool2x2(relu(bn(conv(x) + bias))): HIP forward (`conv2d`, `bn_train_stats` / `bn_eval_stats`,
+    `bn_pool2x2_fwd`) and backward (`bn_pool2x2_bwd_reduce`, `bn_pool2x2_bwd_data`, `conv2d_bwd_weight`, `conv2d_bwd_data`).
+    Saves x, w, z and the per-channel vectors; neither the activated map nor a selector (the backward rescans z)."""
+
+    @staticmethod
+    def forward(ctx, x, w, cb, g, b, cfg):
+        cw, (k, st), spec = cfg
+        x = x.float().contiguous()
+        z = conv2d([x], cw, st, relu=False)
+        mean, rstd = _bn_stats_of(z, spec)
+        p = bn_pool2x2_fwd(z, (mean, rstd), g, b)
+        ctx.cfg = (k, st, spec[0], cb is not None)
+        ctx.save_for_backward(x, w, z, mean, rstd, g, b)
+        return p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gp):
+        k, st, train, has_bias = ctx.cfg
+        x, w, z, mean, rstd, g, b = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gp = gp.float().contiguous()
+        need_z = need[0] or need[1] or (has_bias and need[2])
+        dx = dw = dcb = dg = db = None
+        sums = None
+        if (train and need_z) or need[3] or need[4]:
+            sums = bn_pool2x2_bwd_reduce(gp, z, (mean, rstd), g, b)
+            dg = sums[1] if need[3] else None
+            db = sums[0] if need[4] else None
+        if need_z:
+            dz = bn_pool2x2_bwd_data(gp, z, (mean, rstd), g, b, sums, train)
+            if need[1] or (has_bias and need[2]):
+                dw, dcb = conv2d_bwd_weight([x], dz, k, st, relu=False, want_weight=need[1], want_bias=has_bias and need[2])
+            if need[0]:
+                dx = conv2d_bwd_data(dz, w, [x], st, relu=False)[0]
+        return dx, dw, dcb, dg, db, None
+
+
+def bn_pool_autograd(x, conv, bn, cw=None, name="pooled layer"):
+    """maxpool2x2(relu(bn(conv(x)))) -- a pooled layer of the classic rectifier's localisation network -- inside an autograd
+    graph on the HIP kernels, the BatchNorm, the ReLU and the pool as one pass forward and backward.  conv, bn, cw and the
+    handling of `needs_input_grad` as `bn_stem_autograd`: the BatchNorm follows its own mode (.training: batch statistics,
+    running statistics and num_batches_tracked updated on the device; .eval(): running statistics)."""
+    _chk_gpu(name, x)
+    kst = _conv_spec(conv, f"{name} conv", bias_ok=True)
+    spec = _bn_spec(bn, f"{name} bn")
+    if cw is None:
+        cw = prep_conv_weight_device(conv.weight, conv.bias)
+    return _BnPoolFunction.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, (cw, kst, spec))
+
+
+class _GlobalAvgPoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = tuple(x.shape[2:])
+        return global_avgpool(x.float())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return global_avgpool_bwd(g.float().contiguous(), ctx.hw)
+
+
+def global_avgpool_autograd(x):
+    """nn.AdaptiveAvgPool2d(1) -> (N, C) inside an autograd graph: `global_avgpool` and `global_avgpool_bwd`."""
+    return _GlobalAvgPoolFunction.apply(_chk("global_avgpool_autograd x", x, 4))
+
+
+class _TwoLinearFunction(torch.autograd.Function):
+    """fc2(relu(fc1(x))) for x (N, K) on `tpspp_mm_f32`, backward on `_two_linear_bwd` (the `_TpePointsFunction` pattern)."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2):
+        x = x.float().contiguous()
+        N, K = x.shape
+        h = linear_fwd(x, _dense(N, K), w1, b1, epi=1)
+        y = linear_fwd(h, _dense(N, w1.shape[0]), w2, b2)
+        ctx.save_for_backward(x, h, w1, w2)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, h, w1, w2 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if not any(need[:5]):
+            return (None,) * 5
+        return tuple(_two_linear_bwd(gy.float().contiguous(), h, w2, x, _dense(*x.shape), w1, need[:5], act=ACT_RELU))
+
+
+def two_linear_autograd(x, fc1, fc2):
+    """fc2(relu(fc1(x))) of two nn.Linear layers on x (N, K), differentiable, on the HIP GEMM kernels."""
+    x = _chk("two_linear_autograd x", x, 2)
+    if x.shape[1] != fc1.in_features or fc2.in_features != fc1.out_features:
+        raise ValueError(f"two_linear_autograd: x {tuple(x.shape)} does not fit Linear({fc1.in_features}, "
+                         f"{fc1.out_features}) -> Linear({fc2.in_features}, {fc2.out_features})")
+    return _TwoLinearFunction.apply(x, *_lin(fc1), *_lin(fc2))
+
+
 # ---- training graph of the NRTR encoder (NRTREncoder.set_train_backend("hip"), tpspp_attn_train.hip) -------------------
 # Scaled-dot-product attention with the valid_ratio key mask and dropout on the probabilities, forward and backward
 # (include/tpspp_train_attn.h; every autograd path calls the `_ex` entry points of include/tpspp_train_dec.h, which add a

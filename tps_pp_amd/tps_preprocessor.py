@@ -9,7 +9,11 @@ localization_fc1.0.*`, `LocalizationNetwork.localization_fc2.*`, `GridGenerator.
 What differs is underneath: `GridGenerator.build_P_prime` + `F.grid_sample` (`:71-83`) run as ONE
 hand-written HIP kernel (`tps_pp_amd/csrc/tpspp_warp.hip` through the C ABI of `include/tpspp.h`), and
 the localisation network's convolutions (BatchNorm folded), pooling and FCs run on the hand-written
-fp32 MFMA conv / pooling kernels when the module is in eval mode on a GPU.
+fp32 MFMA conv / pooling kernels when the module is in eval mode on a GPU.  In the graph-building
+forward (`.train()`, or an input that carries gradients) the warp runs on the HIP forward / backward
+kernels and the localisation network on PyTorch's layers ("torch", the default) or, with
+`set_train_backend("hip")`, on HIP kernels forward and backward (`LocalizationNetwork._forward_train_hip`,
+`tps_pp_amd/csrc/tpspp_bn_pool_train.hip`).
 There is no PyTorch / CPU fallback for the rectification path: CPU tensors raise.
 """
 import numpy as np
@@ -17,9 +21,9 @@ import torch
 import torch.nn as nn
 
 from . import constants, ops
-from ._prepared import prepared
+from ._prepared import invalidate_prepared, prepared
 from .precision import default_compute_dtype
-from .registry import PREPROCESSOR
+from .registry import PREPROCESSOR, TrainBackendMixin
 
 
 class BasePreprocessor(nn.Module):
@@ -101,8 +105,32 @@ class LocalizationNetwork(nn.Module):
         x = ops.linear(x, fc1, relu=True)
         return ops.linear(x, fc2, relu=False).view(n, self.num_fiducial, 2)
 
+    def _train_cw(self, i):
+        """The forward's weight layouts of convolution `self.conv[i]`, cached and rebuilt on the device when the parameter
+        changes (`_prepared`, which also names the blind spot `invalidate_train_cache()` is for)."""
+        w = self.conv[i].weight
+        return prepared(self, ("train", i), [w], lambda: ops.prep_conv_weight_device(w))
+
+    def invalidate_train_cache(self):
+        """Drop the cached weight layouts of this module's HIP paths (needed only after edits through `param.data`)."""
+        return invalidate_prepared(self)
+
+    def _forward_train_hip(self, batch_img):
+        """`_forward_torch` on the HIP kernels inside an autograd graph (TPSPreprocessor.set_train_backend("hip")): the three
+        pooled layers each one `ops.bn_pool_autograd` (convolution, then BatchNorm + ReLU + max-pool in one pass), the
+        fourth `ops.bn_stem_autograd`, `ops.global_avgpool_autograd`, and the two FCs on the fp32 GEMM.  Exact fp32
+        whatever `compute_dtype` says; every BatchNorm follows its own mode."""
+        ops.require_gpu(batch_img, "LocalizationNetwork")
+        n = batch_img.size(0)
+        x = batch_img.float().contiguous()
+        for i in (0, 4, 8):
+            x = ops.bn_pool_autograd(x, self.conv[i], self.conv[i + 1], self._train_cw(i), name=f"conv.{i}")
+        x = ops.bn_stem_autograd(x, self.conv[12], self.conv[13], self._train_cw(12), name="conv.12")
+        x = ops.global_avgpool_autograd(x)
+        return ops.two_linear_autograd(x, self.localization_fc1[0], self.localization_fc2).view(n, self.num_fiducial, 2)
+
     def _forward_torch(self, batch_img):
-        """TEST HOOK, never called by forward(): plain PyTorch composition of the same layers."""
+        """The "torch" train backend and the tests' reference: plain PyTorch composition of the same layers."""
         n = batch_img.size(0)
         feat = self.conv(batch_img).view(n, -1)
         return self.localization_fc2(self.localization_fc1(feat)).view(n, self.num_fiducial, 2)
@@ -146,7 +174,7 @@ class GridGenerator(nn.Module):
 
 
 @PREPROCESSOR.register_module()
-class TPSPreprocessor(BasePreprocessor):
+class TPSPreprocessor(TrainBackendMixin, BasePreprocessor):
     """Rectification network of RARE (TPS-based STN), `tps_preprocessor.py:24-85`.
 
     Args:
@@ -198,6 +226,13 @@ class TPSPreprocessor(BasePreprocessor):
         self.train_io_dtype = dtype
         return self
 
+    def set_train_backend(self, mode):
+        """Which kernels the localisation network runs on in the graph-building forward (`.train()`, or an input that
+        carries gradients): "torch" (default) -- the PyTorch composition of its layers; "hip" --
+        `LocalizationNetwork._forward_train_hip`, HIP forward and backward for every layer.  The warp is on the HIP
+        kernels either way.  Touches neither the parameters, the buffers, the state_dict nor the eval path."""
+        return super().set_train_backend(mode)
+
     def rectify(self, batch_img, batch_C_prime, want_grid=False, want_idx=False):
         """The hot path alone: control points -> rectified image (fused HIP kernel).  A bfloat16 image gives a bfloat16
         result (needs the prepared table, i.e. a mirror-symmetric P_hat and a geometry that has one)."""
@@ -215,18 +250,22 @@ class TPSPreprocessor(BasePreprocessor):
         if self.training or (torch.is_grad_enabled() and batch_img.requires_grad):
             # training graph, or an eval-mode module whose input carries gradients
             # (saliency / adversarial gradients w.r.t. the image: the reference is differentiable in eval mode too):
-            # HIP warp forward + backward; the localisation network is the plain PyTorch composition (fp32) so that
-            # autograd reaches its parameters.  Plain eval inference takes the HIP kernels (no autograd graph).
+            # HIP warp forward + backward; the localisation network (fp32) is the plain PyTorch composition or, on the
+            # "hip" train backend, its HIP training graph: autograd reaches its parameters either way.  Plain eval
+            # inference takes the HIP kernels (no autograd graph).
             ops.require_gpu(batch_img, "TPSPreprocessor")
-            if not getattr(self, "_logged_autograd", False):
+            hip = self.train_backend == "hip"
+            if not hip and not getattr(self, "_logged_autograd", False):
                 import logging
                 logging.getLogger("tps_pp_amd").warning(
                     "TPSPreprocessor.train(): localisation network as a PyTorch composition (library kernels, fp32); "
-                    "warp forward / backward on the HIP kernels. Call .eval() for the all-HIP inference path.")
+                    "warp forward / backward on the HIP kernels. Call .eval() for the all-HIP inference path, "
+                    "set_train_backend(\"hip\") for the localisation network's HIP training graph.")
                 self._logged_autograd = True
             gg = self.GridGenerator
             P_hat_t, flags = gg.prepared_table()
-            ctrl = self.LocalizationNetwork._forward_torch(batch_img.float())
+            loc = self.LocalizationNetwork
+            ctrl = loc._forward_train_hip(batch_img) if hip else loc._forward_torch(batch_img.float())
             io = self.train_io_dtype
             return ops.warp_autograd(batch_img.float() if io is None else batch_img.to(io), ctrl.float(), gg.inv_delta_C, gg.P_hat,
                                      self.rectified_img_size, P_hat_t=P_hat_t, table_flags=flags)
