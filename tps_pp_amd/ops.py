@@ -1,8 +1,13 @@
-"""Tensor-level wrappers of the C ABI (include/tpspp.h).
+"""Tensor-level wrappers of the C ABI (the headers under include/, bound by `_lib`).
 
 Each function mirrors one PyTorch call site of the reference (cited in the docstring) and hands raw
-device pointers + the current HIP stream to libtpspp_hip.so.  Inputs must be fp32 CUDA(HIP) tensors;
-anything else raises -- there is no eager / CPU fallback on purpose.
+device pointers + the current HIP stream to libtpspp_hip.so.  Inputs must be CUDA(HIP) tensors of the
+dtype each wrapper names -- float32, bfloat16 on the bf16 paths, integer tokens and lengths; anything
+else raises -- there is no eager / CPU fallback on purpose.
+
+Every launch goes through `_call(name, on, *args)`: the device guard and the stream both come from `on`,
+so a wrapper works on a tensor of a device that is not the current one.  The function is looked up by
+name on every call (nothing is cached), so whatever stands in for the library sees each call.
 """
 import collections
 import ctypes
@@ -21,6 +26,25 @@ def _stream(t):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _marshal(args):
+    """The arguments as ctypes takes them: a tensor becomes its device pointer, everything else (None: NULL) stays."""
+    return [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+
+
+def _call(name, on, *args):
+    """One launch of the entry point `name` on the device of `on` (a tensor or a torch.device), which is made current
+    for the call, and on that device's current stream, appended as the last argument; raises on a non-zero status."""
+    dev = on.device if isinstance(on, torch.Tensor) else on
+    with torch.cuda.device(dev):
+        rc = getattr(_lib.lib(), name)(*_marshal(args), torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, name)
+
+
+def _query(name, *ints):
+    """A host-side query of integers (`*_workspace_floats`, `*_chunk_channels`, ...): no tensors, no stream, no device."""
+    return int(getattr(_lib.lib(), name)(*map(int, ints)))
+
+
 def _vp(arr):
     return ctypes.cast(arr, ctypes.c_void_p)
 
@@ -37,6 +61,11 @@ def _int_array(values, ctype=ctypes.c_int):
 def _ws(n, device):
     """The float32 workspace of a `*_workspace_floats` query (at least one element, so that its pointer is never NULL)."""
     return torch.empty((max(n, 1),), device=device, dtype=torch.float32)
+
+
+def _ws_n(n, device):
+    """(`_ws(n, device)`, n): the two arguments a kernel with a workspace takes."""
+    return _ws(n, device), n
 
 
 def _chk_gpu(who, t):
@@ -89,9 +118,7 @@ def solve_T(inv_delta_C, ctrl):
     if two != 2 or tuple(inv_delta_C.shape) != (F + 3, F + 3):
         raise ValueError("solve_T: shape mismatch")
     T = torch.empty((N, F + 3, 2), device=ctrl.device, dtype=torch.float32)
-    with torch.cuda.device(ctrl.device):
-        rc = _lib.lib().tpspp_solve_T(_ptr(inv_delta_C), _ptr(ctrl), N, F, _ptr(T), _stream(ctrl))
-    _lib.check(rc, "tpspp_solve_T")
+    _call("tpspp_solve_T", ctrl, inv_delta_C, ctrl, N, F, T)
     return T
 
 
@@ -110,10 +137,7 @@ def build_grid(P_hat, T, P_xy=None, score=None):
     if P_hat.shape[1] != (F if P_xy is not None else F + 3):
         raise ValueError("build_grid: P_hat has the wrong number of columns")
     grid = torch.empty((N, n, 2), device=T.device, dtype=torch.float32)
-    with torch.cuda.device(T.device):
-        rc = _lib.lib().tpspp_build_grid(_ptr(P_hat), P_hat.shape[1], _ptr(P_xy), _ptr(score),
-                                         _ptr(T), N, n, F, _ptr(grid), _stream(T))
-    _lib.check(rc, "tpspp_build_grid")
+    _call("tpspp_build_grid", T, P_hat, P_hat.shape[1], P_xy, score, T, N, n, F, grid)
     return grid
 
 
@@ -127,10 +151,7 @@ def grid_sample(inp, grid, return_idx=False):
     Ho, Wo = int(grid.shape[1]), int(grid.shape[2])
     out = torch.empty((N, C, Ho, Wo), device=inp.device, dtype=torch.float32)
     idx = torch.empty((N, Ho * Wo, 2), device=inp.device, dtype=torch.int32) if return_idx else None
-    with torch.cuda.device(inp.device):
-        rc = _lib.lib().tpspp_grid_sample(_ptr(inp), _ptr(grid), N, C, H, W, Ho, Wo, _ptr(out),
-                                          _ptr(idx), _stream(inp))
-    _lib.check(rc, "tpspp_grid_sample")
+    _call("tpspp_grid_sample", inp, inp, grid, N, C, H, W, Ho, Wo, out, idx)
     return (out, idx) if return_idx else out
 
 
@@ -139,9 +160,7 @@ def transpose_p_hat(P_hat):
     P_hat = _chk("P_hat", P_hat, 2)
     n, cols = P_hat.shape
     out = torch.empty((cols, n), device=P_hat.device, dtype=torch.float32)
-    with torch.cuda.device(P_hat.device):
-        rc = _lib.lib().tpspp_transpose_p_hat(_ptr(P_hat), cols, n, cols, _ptr(out), _stream(P_hat))
-    _lib.check(rc, "tpspp_transpose_p_hat")
+    _call("tpspp_transpose_p_hat", P_hat, P_hat, cols, n, cols, out)
     return out
 
 
@@ -165,13 +184,11 @@ def prepare_mirror_table(P_hat, out_hw):
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
     if n != Ho * Wo:
         raise ValueError("prepare_mirror_table: P_hat must have Ho * Wo rows")
-    total = int(_lib.lib().tpspp_prepared_table_floats(Ho, Wo, cols - 3)) if cols > 3 else 0
+    total = _query("tpspp_prepared_table_floats", Ho, Wo, cols - 3) if cols > 3 else 0
     if total == 0:
         return transpose_p_hat(P_hat), 0
     buf = torch.empty((total,), device=P_hat.device, dtype=torch.float32)
-    with torch.cuda.device(P_hat.device):
-        rc = _lib.lib().tpspp_prepare_mirror_table(_ptr(P_hat), cols, Ho, Wo, cols - 3, _ptr(buf), _stream(P_hat))
-    _lib.check(rc, "tpspp_prepare_mirror_table")
+    _call("tpspp_prepare_mirror_table", P_hat, P_hat, cols, Ho, Wo, cols - 3, buf)
     return buf[:cols * n].view(cols, n), TABLE_PACKED | TABLE_SPAN
 
 
@@ -182,7 +199,7 @@ def _chk_table(who, P_hat, P_hat_t, n, out_hw, table_flags):
     if tuple(P_hat_t.shape) != (P_hat.shape[1], n) or P_hat_t.device != P_hat.device:
         raise ValueError(f"{who}: P_hat_t must be P_hat transposed, on the same device")
     if int(table_flags) & TABLE_PACKED:
-        need = int(_lib.lib().tpspp_prepared_table_floats(int(out_hw[0]), int(out_hw[1]), P_hat.shape[1] - 3))
+        need = _query("tpspp_prepared_table_floats", out_hw[0], out_hw[1], P_hat.shape[1] - 3)
         base = P_hat_t._base
         if need == 0 or base is None or base.numel() < need or base.data_ptr() != P_hat_t.data_ptr():
             raise ValueError(f"{who}: TABLE_PACKED needs the P_hat_t that prepare_mirror_table() returned")
@@ -206,8 +223,7 @@ def table_mirror_symmetry(P_hat_host, out_hw, F):
                              else P_hat_host, dtype=np.float32)
     if a.ndim != 2 or a.shape[0] != out_hw[0] * out_hw[1]:
         return 0
-    return int(_lib.lib().tpspp_table_mirror_symmetry(a.ctypes.data, a.shape[1], int(out_hw[0]),
-                                                      int(out_hw[1]), int(F)))
+    return _query("tpspp_table_mirror_symmetry", a.ctypes.data, a.shape[1], out_hw[0], out_hw[1], F)
 
 
 def _chk_score(who, score, N, n, F):
@@ -402,7 +418,7 @@ def prep_conv_weight(weight, bn=None, conv_bias=None, eps=1e-5, src_channels=Non
     w, b, ps, pb = _fold_bn(weight, bn, conv_bias, eps, post_bn)
     cout, cin, kh, kw = w.shape
     wt = w.reshape(cout, -1).t().contiguous()
-    kc = int(_lib.lib().tpspp_conv_chunk_channels(int(kh)))
+    kc = _query("tpspp_conv_chunk_channels", kh)
     tiled = None
     if src_channels is None or len(src_channels) == 1 or all(c % kc == 0 for c in src_channels):
         nch = (cin + kc - 1) // kc
@@ -478,11 +494,8 @@ def conv2d(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out=No
     if N == 0:          # an empty batch has no device pointer to hand over
         return out
     ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_fwd(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(weight_t), _ptr(cw.tiled), _ptr(bias),
-                                         _ptr(residual), _ptr(cw.post_scale), _ptr(cw.post_shift), int(res_mode),
-                                         int(relu), N, Cout, kernel, kernel, sh, sw, _ptr(out), Ho, Wo, _stream(ts[0]))
-    _lib.check(rc, "tpspp_conv2d_fwd")
+    _call("tpspp_conv2d_fwd", ts[0], _vp(ptrs), _vp(dim_arr), len(ts), weight_t, cw.tiled, bias, residual, cw.post_scale,
+          cw.post_shift, int(res_mode), int(relu), N, Cout, kernel, kernel, sh, sw, out, Ho, Wo)
     return out
 
 
@@ -545,14 +558,12 @@ def prep_conv_weight_device(weight, bias=None, src_channels=None):
     cout, cin, kh, kw = w.shape
     if kh != kw or kh not in (1, 3):
         raise ValueError("prep_conv_weight_device: kernel must be 1x1 or 3x3")
-    kc = int(_lib.lib().tpspp_conv_chunk_channels(int(kh)))
+    kc = _query("tpspp_conv_chunk_channels", kh)
     wt = torch.empty((cin * kh * kw, cout), device=w.device, dtype=torch.float32)
     tiled = None
     if src_channels is None or len(src_channels) == 1 or all(c % kc == 0 for c in src_channels):
         tiled = torch.empty(((cin + kc - 1) // kc, kh * kw, kc, cout), device=w.device, dtype=torch.float32)
-    with torch.cuda.device(w.device):
-        rc = _lib.lib().tpspp_conv2d_prep_weight(_ptr(w), cout, cin, kh, kw, _ptr(wt), _ptr(tiled), _stream(w))
-    _lib.check(rc, "tpspp_conv2d_prep_weight")
+    _call("tpspp_conv2d_prep_weight", w, w, cout, cin, kh, kw, wt, tiled)
     b = None if bias is None else _chk("bias", bias.detach(), 1)
     return ConvWeight(wt, tiled, b, kh)
 
@@ -575,10 +586,8 @@ def conv2d_bwd_data(dy, weight, srcs, stride=(1, 1), y=None, relu=True, need=Non
     if N == 0 or not any(need):
         return outs
     ptrs, dim_arr = _ptr_array(outs), _int_array(dims)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bwd_data(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(w), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, kh, kw,
-                                              sh, sw, Ho, Wo, _stream(dy))
-    _lib.check(rc, "tpspp_conv2d_bwd_data")
+    _call("tpspp_conv2d_bwd_data", dy, _vp(ptrs), _vp(dim_arr), len(ts), w, dy, y, int(bool(relu)), N, cout, kh, kw, sh, sw,
+          Ho, Wo)
     return outs
 
 
@@ -586,8 +595,8 @@ def conv2d_bwd_weight_workspace_floats(srcs_dims, N, Cout, kernel, Ho, Wo):
     """Floats of workspace `conv2d_bwd_weight` needs (`tpspp_conv2d_bwd_weight_workspace_floats`): srcs_dims the flat
     {C, H, W, uh, uw} per source; 0 for N = 0.  The split-K slice count behind it depends on the shapes only."""
     dim_arr = _int_array(srcs_dims)
-    return int(_lib.lib().tpspp_conv2d_bwd_weight_workspace_floats(_vp(dim_arr), len(srcs_dims) // 5, N, Cout, kernel,
-                                                                    kernel, Ho, Wo))
+    return _query("tpspp_conv2d_bwd_weight_workspace_floats", ctypes.addressof(dim_arr), len(srcs_dims) // 5, N, Cout,
+                  kernel, kernel, Ho, Wo)
 
 
 def conv2d_bwd_weight(srcs, dy, kernel, stride=(1, 1), y=None, relu=True, want_weight=True, want_bias=True):
@@ -612,11 +621,8 @@ def conv2d_bwd_weight(srcs, dy, kernel, stride=(1, 1), y=None, relu=True, want_w
     nws = conv2d_bwd_weight_workspace_floats(dims, N, cout, int(kernel), Ho, Wo)
     ws = torch.empty((nws,), device=dev, dtype=torch.float32)
     ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bwd_weight(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(dy), _ptr(y), int(bool(relu)), N, cout, int(kernel),
-                                                int(kernel), sh, sw, Ho, Wo, _ptr(dw), _ptr(db), _ptr(ws), nws,
-                                                _stream(dy))
-    _lib.check(rc, "tpspp_conv2d_bwd_weight")
+    _call("tpspp_conv2d_bwd_weight", dy, _vp(ptrs), _vp(dim_arr), len(ts), dy, y, int(bool(relu)), N, cout, int(kernel),
+          int(kernel), sh, sw, Ho, Wo, dw, db, ws, nws)
     return dw, db
 
 
@@ -692,7 +698,7 @@ def prep_conv_weight_bf16(weight, bn=None, conv_bias=None, eps=1e-5, post_bn=Non
     ConvWeightBf16.  Same folding rules as `prep_conv_weight`.  x3: the "bf16x3" split (hi and lo slabs per chunk)."""
     w, b, ps, pb = _fold_bn(weight, bn, conv_bias, eps, post_bn)
     cout, cin, kh, kw = w.shape
-    kc = int(_lib.lib().tpspp_conv_bf16_chunk_channels(int(kh)))
+    kc = _query("tpspp_conv_bf16_chunk_channels", kh)
     ct, nch = (cout + 63) // 64, (cin + kc - 1) // kc
     wp = torch.zeros((ct * 64, nch * kc, kh, kw), device=w.device, dtype=torch.float32)
     wp[:cout, :cin] = w
@@ -737,9 +743,7 @@ class Blocked:
         if not self.t.is_cuda or (h * w) % 64:
             raise _lib.TpsppError("Blocked.nchw_hip: needs a GPU tensor with H * W a multiple of 64 (no CPU fallback)")
         out = torch.empty((n, c, h, w), device=self.t.device, dtype=torch.bfloat16)
-        with torch.cuda.device(self.t.device):
-            rc = _lib.lib().tpspp_blocked_to_nchw_bf16(self.t.data_ptr(), n, c, h * w, out.data_ptr(), _stream(self.t))
-        _lib.check(rc, "tpspp_blocked_to_nchw_bf16")
+        _call("tpspp_blocked_to_nchw_bf16", self.t, self.t, n, c, h * w, out)
         out._tpspp_blocked = self
         return out
 
@@ -801,14 +805,10 @@ def conv2d_bf16(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, o
         return out
     ptrs, dim_arr = _ptr_array(ts), _int_array(dims)
     first = ts[0].keep if isinstance(ts[0], _BlkView) else ts[0]
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_conv2d_bf16_fwd(_vp(ptrs), _vp(dim_arr), len(ts), _ptr(cw.arranged), _ptr(cw.bias),
-                                              residual.data_ptr() if residual is not None else None, res_code,
-                                              _ptr(cw.post_scale), _ptr(cw.post_shift), int(res_mode), int(relu),
-                                              N, Cout, kernel, kernel, sh, sw, out.data_ptr(),
-                                              (3 if cw.x3 else 2) if out_blocked else int(out_dtype == torch.float32), Ho, Wo, int(cw.x3),
-                                              _stream(first))
-    _lib.check(rc, "tpspp_conv2d_bf16_fwd")
+    _call("tpspp_conv2d_bf16_fwd", first, _vp(ptrs), _vp(dim_arr), len(ts), cw.arranged, cw.bias,
+          residual.data_ptr() if residual is not None else None, res_code, cw.post_scale, cw.post_shift, int(res_mode),
+          int(relu), N, Cout, kernel, kernel, sh, sw, out.data_ptr(),
+          (3 if cw.x3 else 2) if out_blocked else int(out_dtype == torch.float32), Ho, Wo, int(cw.x3))
     return out
 
 
@@ -859,12 +859,8 @@ def dgab(x, y, dw):
         raise ValueError("dgab: needs x (N, C, 16, 64) and y (N, C, 32)")
     out = torch.empty_like(x)
     scratch = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_dgab_fwd(_ptr(x), _ptr(y), _ptr(dw.ln1_w), _ptr(dw.ln1_b), _ptr(dw.mw_t),
-                                       _ptr(dw.mh_t), _ptr(dw.proj_slab), _ptr(dw.proj_b), _ptr(dw.ln2_w),
-                                       _ptr(dw.ln2_b), _ptr(dw.fc1_slab), _ptr(dw.fc1_b), _ptr(dw.fc2_slab),
-                                       _ptr(dw.fc2_b), _ptr(scratch), _ptr(out), N, C, _stream(x))
-    _lib.check(rc, "tpspp_dgab_fwd")
+    _call("tpspp_dgab_fwd", x, x, y, dw.ln1_w, dw.ln1_b, dw.mw_t, dw.mh_t, dw.proj_slab, dw.proj_b, dw.ln2_w, dw.ln2_b,
+          dw.fc1_slab, dw.fc1_b, dw.fc2_slab, dw.fc2_b, scratch, out, N, C)
     return out
 
 
@@ -908,12 +904,8 @@ def dgab_bf16(x, y, dw):
         raise ValueError("dgab_bf16: needs x (N, C, 16, 64) and y (N, C, 32)")
     out = torch.empty_like(x)
     scratch = torch.empty(x.shape, device=x.device, dtype=torch.float32 if dw.x3 else torch.bfloat16)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_dgab_bf16_fwd(_ptr(x), _ptr(y), _ptr(dw.ln1_w), _ptr(dw.ln1_b), _ptr(dw.mw_t),
-                                            _ptr(dw.mh_t), _ptr(dw.proj_slab), _ptr(dw.proj_b), _ptr(dw.ln2_w),
-                                            _ptr(dw.ln2_b), _ptr(dw.fc1_slab), _ptr(dw.fc1_b), _ptr(dw.fc2_slab),
-                                            _ptr(dw.fc2_b), _ptr(scratch), _ptr(out), N, C, int(dw.x3), _stream(x))
-    _lib.check(rc, "tpspp_dgab_bf16_fwd")
+    _call("tpspp_dgab_bf16_fwd", x, x, y, dw.ln1_w, dw.ln1_b, dw.mw_t, dw.mh_t, dw.proj_slab, dw.proj_b, dw.ln2_w, dw.ln2_b,
+          dw.fc1_slab, dw.fc1_b, dw.fc2_slab, dw.fc2_b, scratch, out, N, C, int(dw.x3))
     return out
 
 
@@ -942,14 +934,8 @@ def score(de_feat, p, sw, scale, x3=False):
         raise ValueError("score: needs de_feat (N, 64, H, W) and p (N, 32, 128)")
     n = H * W
     out = torch.empty((N, 32, n), device=de_feat.device, dtype=torch.float32)
-    with torch.cuda.device(de_feat.device):
-        if x3:
-            rc = _lib.lib().tpspp_score_x3_fwd(_ptr(de_feat), _ptr(sw.w1_x3), _ptr(sw.b1), _ptr(sw.w2_x3),
-                                               _ptr(sw.b2), _ptr(p), float(scale), _ptr(out), N, n, _stream(de_feat))
-        else:
-            rc = _lib.lib().tpspp_score_fwd(_ptr(de_feat), _ptr(sw.w1_slab), _ptr(sw.b1), _ptr(sw.w2_slab),
-                                            _ptr(sw.b2), _ptr(p), float(scale), _ptr(out), N, n, _stream(de_feat))
-    _lib.check(rc, "tpspp_score_fwd")
+    name, w1, w2 = ("tpspp_score_x3_fwd", sw.w1_x3, sw.w2_x3) if x3 else ("tpspp_score_fwd", sw.w1_slab, sw.w2_slab)
+    _call(name, de_feat, de_feat, w1, sw.b1, w2, sw.b2, p, float(scale), out, N, n)
     return out.transpose(1, 2)
 
 
@@ -979,12 +965,8 @@ def front(o0, o1, x, fw, store01=True):
     feat0 = torch.empty_like(feat_grid) if store01 else None
     feat1 = torch.empty_like(feat_grid) if store01 else None
     feat2 = torch.empty((N, 64, H // 2, W // 2), device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_front_fwd(_ptr(o0), _ptr(o1), _ptr(x), _ptr(fw.w0), _ptr(fw.b0), _ptr(fw.w1),
-                                        _ptr(fw.b1), _ptr(fw.w2), _ptr(fw.b2), _ptr(fw.wg), _ptr(fw.bg),
-                                        _ptr(feat0), _ptr(feat1), _ptr(feat2), _ptr(feat_grid), N, H, W,
-                                        _stream(o0))
-    _lib.check(rc, "tpspp_front_fwd")
+    _call("tpspp_front_fwd", o0, o0, o1, x, fw.w0, fw.b0, fw.w1, fw.b1, fw.w2, fw.b2, fw.wg, fw.bg, feat0, feat1, feat2,
+          feat_grid, N, H, W)
     return feat0, feat1, feat2, feat_grid
 
 
@@ -1006,10 +988,7 @@ def down_fused_f32(o, w0_slab, b0, cw, relu=True):
     out = torch.empty((N, 64, H // 2, W // 2), device=o.device, dtype=torch.float32)
     if N == 0:
         return out
-    with torch.cuda.device(o.device):
-        rc = _lib.lib().tpspp_down_fused_f32_fwd(_ptr(o), _ptr(w0_slab), _ptr(b0), _ptr(cw.tiled), _ptr(cw.bias), _ptr(out),
-                                                 N, H, W, int(relu), _stream(o))
-    _lib.check(rc, "tpspp_down_fused_f32_fwd")
+    _call("tpspp_down_fused_f32_fwd", o, o, w0_slab, b0, cw.tiled, cw.bias, out, N, H, W, int(relu))
     return out
 
 
@@ -1058,14 +1037,8 @@ def front_bf16(o0, o1, x, fw, feat_grid_dtype=torch.bfloat16, blocked=False, sto
             raise ValueError("front_bf16: store01=False goes with the blocked form")
         feat0 = feat1 = None
     feat_grid = torch.empty((N, 64, H, W), device=dev, dtype=feat_grid_dtype)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_front_bf16_fwd(_ptr(o0), _ptr(o1), _ptr(x), _ptr(fw.w0), _ptr(fw.b0), _ptr(fw.w1),
-                                             _ptr(fw.b1), _ptr(fw.w2), _ptr(fw.b2), _ptr(fw.wg), _ptr(fw.bg),
-                                             _ptr(feat0) if store01 else None, _ptr(feat1) if store01 else None,
-                                             _ptr(feat2), _ptr(feat_grid),
-                                             int(feat_grid_dtype == torch.float32) | (2 if blocked else 0), N, H, W,
-                                             int(fw.x3), _stream(o0))
-    _lib.check(rc, "tpspp_front_bf16_fwd")
+    _call("tpspp_front_bf16_fwd", o0, o0, o1, x, fw.w0, fw.b0, fw.w1, fw.b1, fw.w2, fw.b2, fw.wg, fw.bg, feat0, feat1, feat2,
+          feat_grid, int(feat_grid_dtype == torch.float32) | (2 if blocked else 0), N, H, W, int(fw.x3))
     if blocked:
         B = Blocked32 if fw.x3 else Blocked
         return (B(feat0), B(feat1), B(feat2), feat_grid) if store01 else (None, None, B(feat2), feat_grid)
@@ -1086,11 +1059,8 @@ def token_gemm_bf16(x_cm, cw, act=None, residual=None, out_dtype=torch.float32):
     if out_dtype not in (torch.float32, torch.bfloat16) or act not in (None, "gelu"):
         raise ValueError("token_gemm_bf16: out_dtype float32 | bfloat16, act None | 'gelu'")
     out = torch.empty((cw.cout, M), device=x_cm.device, dtype=out_dtype)
-    with torch.cuda.device(x_cm.device):
-        rc = _lib.lib().tpspp_token_gemm_bf16_fwd(_ptr(x_cm), _ptr(cw.arranged), _ptr(cw.bias), _ptr(residual), out.data_ptr(),
-                                                  int(out_dtype == torch.float32), K, cw.cout, M, 2 if act == "gelu" else 0,
-                                                  int(cw.x3), _stream(x_cm))
-    _lib.check(rc, "tpspp_token_gemm_bf16_fwd")
+    _call("tpspp_token_gemm_bf16_fwd", x_cm, x_cm, cw.arranged, cw.bias, residual, out,
+          int(out_dtype == torch.float32), K, cw.cout, M, 2 if act == "gelu" else 0, int(cw.x3))
     return out
 
 
@@ -1113,16 +1083,13 @@ def down_fused_bf16(o, w0_slab, b0, cw, relu=True):
     N, _, H, W = o.shape
     if cw.x3:                                           # three-term split: fp32 maps, `w0_slab` with its hi and lo halves
         out = Blocked32(torch.empty((N, 8, H // 2, W // 2, 8), device=o.device, dtype=torch.float32))
-        fn, name = _lib.lib().tpspp_down_fused_x3_fwd, "tpspp_down_fused_x3_fwd"
+        name = "tpspp_down_fused_x3_fwd"
     else:
         out = Blocked(torch.empty((N, 8, H // 2, W // 2, 8), device=o.device, dtype=torch.bfloat16))
-        fn, name = _lib.lib().tpspp_down_fused_bf16_fwd, "tpspp_down_fused_bf16_fwd"
+        name = "tpspp_down_fused_bf16_fwd"
     if N == 0:
         return out
-    with torch.cuda.device(o.device):
-        rc = fn(_ptr(o), _ptr(w0_slab), _ptr(b0), _ptr(cw.arranged), _ptr(cw.bias), out.t.data_ptr(), N, H, W, int(relu),
-                _stream(o))
-    _lib.check(rc, name)
+    _call(name, o, o, w0_slab, b0, cw.arranged, cw.bias, out.t, N, H, W, int(relu))
     return out
 
 
@@ -1134,11 +1101,8 @@ def cbam(x, atten):
     f = lambda t: t.detach().float().contiguous()
     ca, sa = atten.channel_attention, atten.spatial_attention
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_cbam_fwd(_ptr(x), _ptr(f(ca.shared_MLP[0].weight.view(4, 64))),
-                                       _ptr(f(ca.shared_MLP[2].weight.view(64, 4))), _ptr(f(sa.conv2d.weight)),
-                                       _ptr(f(sa.conv2d.bias)), _ptr(out), x.shape[0], _stream(x))
-    _lib.check(rc, "tpspp_cbam_fwd")
+    _call("tpspp_cbam_fwd", x, x, f(ca.shared_MLP[0].weight.view(4, 64)), f(ca.shared_MLP[2].weight.view(64, 4)),
+          f(sa.conv2d.weight), f(sa.conv2d.bias), out, x.shape[0])
     return out
 
 
@@ -1156,10 +1120,7 @@ def tpe_points(en_feat, tpe):
     p = torch.empty((N, 32, 128), device=en_feat.device, dtype=torch.float32)
     ws = [f(t) for t in (l1a.weight, l1a.bias, l1b.weight, l1b.bias, l2.weight, l2.bias, p0.weight, p0.bias,
                          p1.weight, p1.bias)]
-    with torch.cuda.device(en_feat.device):
-        rc = _lib.lib().tpspp_tpe_points_fwd(_ptr(en_feat), *[_ptr(w) for w in ws], _ptr(ctrl), _ptr(p), N,
-                                             _stream(en_feat))
-    _lib.check(rc, "tpspp_tpe_points_fwd")
+    _call("tpspp_tpe_points_fwd", en_feat, en_feat, *ws, ctrl, p, N)
     return ctrl, p
 
 
@@ -1168,9 +1129,7 @@ def maxpool2x2(x):
     x = _chk("input", x, 4)
     N, C, H, W = x.shape
     out = torch.empty((N, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_maxpool2x2_fwd(_ptr(x), N, C, H, W, _ptr(out), _stream(x))
-    _lib.check(rc, "tpspp_maxpool2x2_fwd")
+    _call("tpspp_maxpool2x2_fwd", x, x, N, C, H, W, out)
     return out
 
 
@@ -1179,9 +1138,7 @@ def global_avgpool(x):
     x = _chk("input", x, 4)
     N, C, H, W = x.shape
     out = torch.empty((N, C), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_global_avgpool_fwd(_ptr(x), N, C, H, W, _ptr(out), _stream(x))
-    _lib.check(rc, "tpspp_global_avgpool_fwd")
+    _call("tpspp_global_avgpool_fwd", x, x, N, C, H, W, out)
     return out
 
 
@@ -1226,9 +1183,7 @@ def transpose2d(x):
     x = _chk("input", x, 2)
     r, c = x.shape
     out = torch.empty((c, r), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_transpose2d(_ptr(x), r, c, _ptr(out), _stream(x))
-    _lib.check(rc, "tpspp_transpose2d")
+    _call("tpspp_transpose2d", x, x, r, c, out)
     return out
 
 
@@ -1237,10 +1192,7 @@ def layernorm_cm(x, gamma, beta, eps=1e-5):
     x = _chk("input", x, 2)
     C, M = x.shape
     y = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_layernorm_cm_fwd(_ptr(x), _ptr(_chk("gamma", gamma, 1)), _ptr(_chk("beta", beta, 1)),
-                                               C, M, float(eps), _ptr(y), _stream(x))
-    _lib.check(rc, "tpspp_layernorm_cm_fwd")
+    _call("tpspp_layernorm_cm_fwd", x, x, _chk("gamma", gamma, 1), _chk("beta", beta, 1), C, M, float(eps), y)
     return y
 
 
@@ -1263,11 +1215,8 @@ def linear_ln(x, folded, eps=1e-5, act=0, residual=None, token_major=False):
     K, M = x.shape
     Cout = wg.shape[1]
     out = torch.empty((M, Cout) if token_major else (Cout, M), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_linear_ln_fwd(_ptr(x), K, M, float(eps), _ptr(wg), _ptr(_chk("w_colsum", colsum, 1)), Cout,
-                                            _ptr(bias_eff), int(act), _ptr(residual), int(bool(token_major)),
-                                            _ptr(out), _stream(x))
-    _lib.check(rc, "tpspp_linear_ln_fwd")
+    _call("tpspp_linear_ln_fwd", x, x, K, M, float(eps), wg, _chk("w_colsum", colsum, 1), Cout, bias_eff, int(act),
+          residual, int(bool(token_major)), out)
     return out
 
 
@@ -1276,9 +1225,7 @@ def attn_enc(qkv, N, T, valid_len=None):
     qkv = _chk("qkv", qkv, 2)
     C = qkv.shape[0] // 3
     out = torch.empty((C, N * T), device=qkv.device, dtype=torch.float32)
-    with torch.cuda.device(qkv.device):
-        rc = _lib.lib().tpspp_attn_enc_fwd(_ptr(qkv), N, C, T, _ptr(valid_len), _ptr(out), _stream(qkv))
-    _lib.check(rc, "tpspp_attn_enc_fwd")
+    _call("tpspp_attn_enc_fwd", qkv, qkv, N, C, T, valid_len, out)
     return out
 
 
@@ -1351,16 +1298,12 @@ def nrtr_encoder(feat, table, n_layers, d_inner, ln_g, ln_b, valid_len=None, hol
     feat = _chk("feat", feat, 4)
     N, C, H, W = feat.shape
     T = H * W
-    L = _lib.lib()
-    nbytes = L.tpspp_nrtr_encoder_workspace(N, C, T, d_inner)
+    nbytes = _query("tpspp_nrtr_encoder_workspace", N, C, T, d_inner)
     ws = _workspace(holder if holder is not None else table, nbytes, feat.device)
     out_cm = torch.empty((C, N * T), device=feat.device, dtype=torch.float32)
     out = torch.empty((N, T, C), device=feat.device, dtype=torch.float32) if want_ntc else None
-    with torch.cuda.device(feat.device):
-        rc = L.tpspp_nrtr_encoder_fwd(_ptr(feat), N, C, T, d_inner, n_layers, table.ptr, _ptr(ln_g), _ptr(ln_b),
-                                      _ptr(valid_len), ws.data_ptr(), ws.numel(), _ptr(out_cm), _ptr(out),
-                                      int(flags), _stream(feat))
-    _lib.check(rc, "tpspp_nrtr_encoder_fwd")
+    _call("tpspp_nrtr_encoder_fwd", feat, feat, N, C, T, d_inner, n_layers, table.ptr, ln_g, ln_b, valid_len, ws,
+          ws.numel(), out_cm, out, int(flags))
     return out, out_cm
 
 
@@ -1377,8 +1320,7 @@ def nrtr_decoder(enc_cm, N, T, table, n_layers, d_inner, emb, pos_table, cls_fol
         raise ValueError("nrtr_decoder: enc_cm must be (C, N*T)")
     w_cls, cls_colsum, b_cls = cls_folded              # fold_layernorm(final layer_norm, classifier)
     num_out = w_cls.shape[1]
-    L = _lib.lib()
-    nbytes = L.tpspp_nrtr_decoder_workspace(N, C, T, d_inner, n_layers, max_seq_len, num_out)
+    nbytes = _query("tpspp_nrtr_decoder_workspace", N, C, T, d_inner, n_layers, max_seq_len, num_out)
     ws = _workspace(holder if holder is not None else table, nbytes, enc_cm.device)
     out = torch.empty((N, max_seq_len, num_out), device=enc_cm.device, dtype=torch.float32)
     # tokens and the status word in one buffer: one device->host copy fetches both
@@ -1389,13 +1331,9 @@ def nrtr_decoder(enc_cm, N, T, table, n_layers, d_inner, emb, pos_table, cls_fol
         if forced_tokens.dtype != torch.int32 or tuple(forced_tokens.shape) != (N, max_seq_len) or \
                 not forced_tokens.is_contiguous() or forced_tokens.device != enc_cm.device:
             raise ValueError("nrtr_decoder: forced_tokens must be a contiguous (N, max_seq_len) int32 device tensor")
-    with torch.cuda.device(enc_cm.device):
-        rc = L.tpspp_nrtr_decoder_fwd(_ptr(enc_cm), N, C, T, d_inner, n_layers, table.ptr, len(table),
-                                      _ptr(emb), _ptr(pos_table), pos_table.shape[0], _ptr(w_cls), _ptr(cls_colsum),
-                                      _ptr(b_cls), num_out, max_seq_len, int(start_idx), int(padding_idx), _ptr(valid_len),
-                                      _ptr(forced_tokens), ws.data_ptr(), ws.numel(), _ptr(out), tokens.data_ptr(),
-                                      status.data_ptr(), int(flags), _stream(enc_cm))
-    _lib.check(rc, "tpspp_nrtr_decoder_fwd")
+    _call("tpspp_nrtr_decoder_fwd", enc_cm, enc_cm, N, C, T, d_inner, n_layers, table.ptr, len(table), emb, pos_table,
+          pos_table.shape[0], w_cls, cls_colsum, b_cls, num_out, max_seq_len, int(start_idx), int(padding_idx), valid_len,
+          forced_tokens, ws, ws.numel(), out, tokens, status, int(flags))
     return out, tokens, status
 
 
@@ -1435,10 +1373,8 @@ def attn_tensor2idx(scores, end_idx, padding_idx, status=None):
     N, L, C = scores.shape
     # [idx (N*L) | val (N*L) as raw bits | status]: one int32 buffer, one copy
     buf = torch.empty((2 * N * L + 1,), device=scores.device, dtype=torch.int32)
-    with torch.cuda.device(scores.device):
-        rc = _lib.lib().tpspp_attn_tensor2idx_fwd(_ptr(scores), N, L, C, int(end_idx), int(padding_idx), buf.data_ptr(),
-                                                  buf.data_ptr() + 4 * N * L, _stream(scores))
-    _lib.check(rc, "tpspp_attn_tensor2idx_fwd")
+    _call("tpspp_attn_tensor2idx_fwd", scores, scores, N, L, C, int(end_idx), int(padding_idx), buf.data_ptr(),
+          buf.data_ptr() + 4 * N * L)
     if status is not None and status.device == scores.device:
         buf[-1:].copy_(status)
     else:
@@ -1467,11 +1403,8 @@ def resize_normalize(packed, offsets, src_h, src_w, resize_w, lut, pad_value, N,
             tuple(lut.shape) != (C, 256):
         raise ValueError("resize_normalize: per-image arrays need N entries, lut must be (C, 256)")
     out = torch.empty((N, C, H, W), device=packed.device, dtype=torch.float32)
-    with torch.cuda.device(packed.device):
-        rc = _lib.lib().tpspp_resize_normalize_fwd(_ptr(packed), _ptr(offsets), _ptr(src_h), _ptr(src_w), _ptr(resize_w),
-                                                   _ptr(lut), int(pad_value), int(N), int(C), int(H), int(W), _ptr(out),
-                                                   int(interpolation), _stream(packed))
-    _lib.check(rc, "tpspp_resize_normalize_fwd")
+    _call("tpspp_resize_normalize_fwd", packed, packed, offsets, src_h, src_w, resize_w, lut, int(pad_value), int(N),
+          int(C), int(H), int(W), out, int(interpolation))
     return out
 
 
@@ -1504,12 +1437,8 @@ def augment_normalize(packed, offsets, src_h, src_w, resize_w, lut, pad_value, N
             tuple(op_params.shape) != (N, op_codes.shape[1], AUG_OP_PARAMS):
         raise ValueError(f"augment_normalize: op_codes must be (N, 1..{AUG_MAX_OPS}), op_params (N, max_ops, {AUG_OP_PARAMS})")
     out = torch.empty((N, C, H, W), device=packed.device, dtype=torch.float32)
-    with torch.cuda.device(packed.device):
-        rc = _lib.lib().tpspp_augment_normalize_fwd(_ptr(packed), _ptr(offsets), _ptr(src_h), _ptr(src_w), _ptr(resize_w),
-                                                    _ptr(lut), int(pad_value), int(N), int(C), int(H), int(W), _ptr(out),
-                                                    int(interpolation), _ptr(op_codes), _ptr(op_params),
-                                                    int(op_codes.shape[1]), int(bool(bgr)), _stream(packed))
-    _lib.check(rc, "tpspp_augment_normalize_fwd")
+    _call("tpspp_augment_normalize_fwd", packed, packed, offsets, src_h, src_w, resize_w, lut, int(pad_value), int(N),
+          int(C), int(H), int(W), out, int(interpolation), op_codes, op_params, int(op_codes.shape[1]), int(bool(bgr)))
     return out
 
 
@@ -1565,14 +1494,9 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
     g_in0 = torch.empty_like(in0) if need_in0 else None
     g_in1 = torch.empty_like(in1) if (in1 is not None and need_in1) else None
     g_ctrl = torch.empty((N, F, 2), device=in0.device, dtype=torch.float32)
-    g_grid = torch.empty((int(_lib.lib().tpspp_warp_bwd_workspace_floats(N, Ho, Wo)),), device=in0.device, dtype=torch.float32)
-    with torch.cuda.device(in0.device):
-        rc = _lib.lib().tpspp_warp_bwd(_ptr(g_out0), _ptr(in0), C0, H0, W0, _ptr(g_out1), _ptr(in1), C1, H1, W1,
-                                       _ptr(grid), _ptr(T), _ptr(inv_delta_C), _ptr(P_hat), P_hat.shape[1],
-                                       _ptr(P_xy), _ptr(score), _ptr(P_hat_t), flags, N, F, Ho, Wo,
-                                       _ptr(g_in0), _ptr(g_in1), _ptr(g_ctrl), _ptr(g_score), _ptr(g_grid),
-                                       g_grid.numel(), _stream(in0))
-    _lib.check(rc, "tpspp_warp_bwd")
+    g_grid = torch.empty((_query("tpspp_warp_bwd_workspace_floats", N, Ho, Wo),), device=in0.device, dtype=torch.float32)
+    _call("tpspp_warp_bwd", in0, g_out0, in0, C0, H0, W0, g_out1, in1, C1, H1, W1, grid, T, inv_delta_C, P_hat,
+          P_hat.shape[1], P_xy, score, P_hat_t, flags, N, F, Ho, Wo, g_in0, g_in1, g_ctrl, g_score, g_grid, g_grid.numel())
     if g_score is not None and (flags & SCORE_TRANSPOSED):
         g_score = g_score.transpose(1, 2)                  # back to the logical (N, n, F) view
     return g_in0, g_in1, g_ctrl, g_score
@@ -1590,11 +1514,9 @@ class _WarpFunction(torch.autograd.Function):
             # a geometry the bf16 backward refuses raises here, with the library's message, not in the middle of .backward():
             # tpspp_warp_bwd checks it before its N == 0 return (no launch; the pointers only stand in for their alignment)
             H1, W1 = (int(in1.shape[2]), int(in1.shape[3])) if in1 is not None else (0, 0)
-            a, b = in0.data_ptr(), _ptr(in1)
-            rc = _lib.lib().tpspp_warp_bwd(a, a, 1, int(in0.shape[2]), int(in0.shape[3]), b, b, 1 if in1 is not None else 0,
-                                           H1, W1, a, a, a, a, 64, 0, 0, 0, IO_BF16, 0, 1, int(out_hw[0]), int(out_hw[1]),
-                                           a, b, a, 0, a, 0, 0)
-            _lib.check(rc, "tpspp_warp_bwd")
+            a, b = in0, in1
+            _call("tpspp_warp_bwd", a, a, a, 1, int(in0.shape[2]), int(in0.shape[3]), b, b, 1 if in1 is not None else 0,
+                  H1, W1, a, a, a, a, 64, None, None, None, IO_BF16, 0, 1, int(out_hw[0]), int(out_hw[1]), a, b, a, None, a, 0)
         out0, out1, grid, _ = warp(in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy=P_xy, score=score, in1=in1,
                                    want_grid=True, P_hat_t=P_hat_t, table_flags=table_flags)
         ctx.out_hw = out_hw
@@ -1655,8 +1577,7 @@ def mm(A, a_strides, B, b_strides, C, c_strides, batch, M, N, K, bias=None, R=No
     """`tpspp_mm_f32`: C[b][i][j] = epi(alpha * sum_k A[b][i][k] B[b][j][k] + bias[j]) (+ R[b][i][j]); strides in
     elements, (batch, row, k) for A / B and (batch, row, column) for C and R.  epi: 0 none, 1 ReLU, 2 GELU, 3 tanh."""
     sa, sb, sc = _i64(*a_strides), _i64(*b_strides), _i64(*c_strides)
-    _lib.check(_lib.lib().tpspp_mm_f32(batch, M, N, K, _ptr(A), _vp(sa), _ptr(B), _vp(sb), _ptr(C), _vp(sc), _ptr(bias),
-                                       _ptr(R), epi, float(alpha), k_total, _stream(C)), "tpspp_mm_f32")
+    _call("tpspp_mm_f32", C, batch, M, N, K, A, _vp(sa), B, _vp(sb), C, _vp(sc), bias, R, epi, float(alpha), k_total)
     return C
 
 
@@ -1684,7 +1605,7 @@ def linear_bwd_data(dy, weight, out=None, desc=None):
 
 
 def linear_bwd_weight_workspace_floats(M, O, K):
-    return int(_lib.lib().tpspp_linear_bwd_weight_workspace_floats(int(M), int(O), int(K)))
+    return _query("tpspp_linear_bwd_weight_workspace_floats", M, O, K)
 
 
 def linear_bwd_weight(dy, x, desc, O, K, want_weight=True, want_bias=True, x_gelu=False):
@@ -1697,11 +1618,9 @@ def linear_bwd_weight(dy, x, desc, O, K, want_weight=True, want_bias=True, x_gel
     dev = dy.device
     dw = torch.empty((O, K), device=dev, dtype=torch.float32) if want_weight else None
     db = torch.empty((O,), device=dev, dtype=torch.float32) if want_bias else None
-    n = linear_bwd_weight_workspace_floats(M, O, K)
-    ws = _ws(n, dev)
+    ws, n = _ws_n(linear_bwd_weight_workspace_floats(M, O, K), dev)
     lay = _i64(Mi, sb, si, sk)
-    _lib.check(_lib.lib().tpspp_linear_bwd_weight(_ptr(dy), _ptr(x), _vp(lay), 2 if x_gelu else 0, M, O, K, _ptr(dw), _ptr(db), _ptr(ws), n,
-                                                  _stream(dy)), "tpspp_linear_bwd_weight")
+    _call("tpspp_linear_bwd_weight", dy, dy, x, _vp(lay), 2 if x_gelu else 0, M, O, K, dw, db, ws, n)
     return dw, db
 
 
@@ -1711,8 +1630,7 @@ ACT_RELU, ACT_GELU, ACT_TANH = 0, 1, 2
 def act_bwd(op, g, t, scale=1.0, out=None):
     """`tpspp_act_bwd`: g * f'(.) for ReLU (t = output), GELU (t = input) or tanh(scale * u) (t = output, d/du)."""
     out = torch.empty_like(g) if out is None else out
-    _lib.check(_lib.lib().tpspp_act_bwd(op, g.numel(), _ptr(g), _ptr(t), float(scale), _ptr(out), _stream(g)),
-               "tpspp_act_bwd")
+    _call("tpspp_act_bwd", g, op, g.numel(), g, t, float(scale), out)
     return out
 
 
@@ -1723,13 +1641,12 @@ def plane_ln_fwd(x, weight, bias, eps):
     y = torch.empty_like(x)
     mean = torch.empty((rows,), device=x.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
-    _lib.check(_lib.lib().tpspp_plane_ln_fwd(_ptr(x), _ptr(weight), _ptr(bias), rows, P, float(eps), _ptr(y), _ptr(mean),
-                                             _ptr(rstd), _stream(x)), "tpspp_plane_ln_fwd")
+    _call("tpspp_plane_ln_fwd", x, x, weight, bias, rows, P, float(eps), y, mean, rstd)
     return y, mean, rstd
 
 
 def plane_ln_bwd_workspace_floats(rows, P):
-    return int(_lib.lib().tpspp_plane_ln_bwd_workspace_floats(int(rows), int(P)))
+    return _query("tpspp_plane_ln_bwd_workspace_floats", rows, P)
 
 
 def plane_ln_bwd(dy, x, weight, mean, rstd, dx=None, accumulate=False, want_params=True):
@@ -1742,13 +1659,10 @@ def plane_ln_bwd(dy, x, weight, mean, rstd, dx=None, accumulate=False, want_para
     if want_params:
         dw = torch.empty((P,), device=dev, dtype=torch.float32)
         db = torch.empty((P,), device=dev, dtype=torch.float32)
-        n = plane_ln_bwd_workspace_floats(rows, P)
-        ws = _ws(n, dev)
+        ws, n = _ws_n(plane_ln_bwd_workspace_floats(rows, P), dev)
     if dx is None and not want_params:
         return None, None
-    _lib.check(_lib.lib().tpspp_plane_ln_bwd(_ptr(dy), _ptr(x), _ptr(weight), _ptr(mean), _ptr(rstd), rows, P, _ptr(dx),
-                                             int(bool(accumulate)), _ptr(dw), _ptr(db), _ptr(ws), n, _stream(x)),
-               "tpspp_plane_ln_bwd")
+    _call("tpspp_plane_ln_bwd", x, dy, x, weight, mean, rstd, rows, P, dx, int(bool(accumulate)), dw, db, ws, n)
     return (dw.view(weight.shape), db.view(weight.shape)) if want_params else (None, None)
 
 
@@ -1815,18 +1729,16 @@ class _DgabFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, ln1w, ln1b, mww, mhw, pw, pb, ln2w, ln2b, f1w, f1b, f2w, f2b, eps1, eps2):
-        L = _lib.lib()
         N, C, H, W = x.shape
         T = y.shape[2]
-        st = _stream(x)
         xn, m1, r1 = plane_ln_fwd(x, ln1w, ln1b, eps1)
         catw = torch.empty((N * C, W + T), device=x.device, dtype=torch.float32)
         cath = torch.empty((N * C, H + T), device=x.device, dtype=torch.float32)
-        _lib.check(L.tpspp_dgab_pool_fwd(_ptr(xn), _ptr(y), N, C, H, W, T, _ptr(catw), _ptr(cath), st), "tpspp_dgab_pool_fwd")
+        _call("tpspp_dgab_pool_fwd", x, xn, y, N, C, H, W, T, catw, cath)
         wv = linear_fwd(catw, _dense(N * C, W + T), mww)
         hv = linear_fwd(cath, _dense(N * C, H + T), mhw)
         A = torch.empty_like(x)
-        _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
+        _call("tpspp_dgab_gate_fwd", x, xn, wv, hv, N, C, H, W, A)
         x1 = linear_fwd(A, _dense(N * C * H, W), pw, pb, R=x).view(N, C, H, W)
         del A, xn, catw, cath
         out, m2, r2 = _mlp_fwd(x1, ln2w, ln2b, eps2, f1w, f1b, f2w, f2b, residual=True)
@@ -1841,11 +1753,9 @@ class _DgabFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         if not any(need[:14]):
             return (None,) * 16
-        L = _lib.lib()
         N, C, H, W = x.shape
         T = y.shape[2]
         rows = N * C * H
-        st = _stream(x)
         eps1, eps2 = ctx.eps
         # ---- mlp (fc1 - GELU - fc2 along W) and norm2; x2n and u recomputed.  dx1 starts as a copy of gout (the residual)
         # and the kernels below accumulate into it in place
@@ -1856,29 +1766,26 @@ class _DgabFunction(torch.autograd.Function):
         dw_p = db_p = None
         if need[6] or need[7]:
             A = torch.empty_like(x)
-            _lib.check(L.tpspp_dgab_gate_fwd(_ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(A), st), "tpspp_dgab_gate_fwd")
+            _call("tpspp_dgab_gate_fwd", x, xn, wv, hv, N, C, H, W, A)
             dw_p, db_p = linear_bwd_weight(dx1, A, _dense(rows, W), W, W, need[6], need[7])
             del A
         dA = linear_bwd_data(dx1, pw)
         dxn = torch.empty_like(x)
         dwv, dhv = torch.empty_like(wv), torch.empty_like(hv)
-        _lib.check(L.tpspp_dgab_gate_bwd(_ptr(dA), _ptr(xn), _ptr(wv), _ptr(hv), N, C, H, W, _ptr(dxn), _ptr(dwv), _ptr(dhv),
-                                         st), "tpspp_dgab_gate_bwd")
+        _call("tpspp_dgab_gate_bwd", x, dA, xn, wv, hv, N, C, H, W, dxn, dwv, dhv)
         del dA
         dw_mw = dw_mh = None
         if need[4] or need[5]:
             catw = torch.empty((N * C, W + T), device=x.device, dtype=torch.float32)
             cath = torch.empty((N * C, H + T), device=x.device, dtype=torch.float32)
-            _lib.check(L.tpspp_dgab_pool_fwd(_ptr(xn), _ptr(y), N, C, H, W, T, _ptr(catw), _ptr(cath), st),
-                       "tpspp_dgab_pool_fwd")
+            _call("tpspp_dgab_pool_fwd", x, xn, y, N, C, H, W, T, catw, cath)
             dw_mw, _ = linear_bwd_weight(dwv, catw, _dense(N * C, W + T), W + 1, W + T, need[4], False)
             dw_mh, _ = linear_bwd_weight(dhv, cath, _dense(N * C, H + T), H + 1, H + T, need[5], False)
             del catw, cath
         dcatw = linear_bwd_data(dwv, mww)
         dcath = linear_bwd_data(dhv, mhw)
         dy = torch.empty_like(y) if need[1] else None
-        _lib.check(L.tpspp_dgab_pool_bwd(_ptr(dcatw), _ptr(dcath), N, C, H, W, T, _ptr(dxn), _ptr(dy), st),
-                   "tpspp_dgab_pool_bwd")
+        _call("tpspp_dgab_pool_bwd", x, dcatw, dcath, N, C, H, W, T, dxn, dy)
         del dcatw, dcath
         dx, dw_ln1, db_ln1 = _ln_bwd(dxn, x, ln1w, m1, r1, (need[0], need[2], need[3]), into=dx1)
         return (dx, dy, dw_ln1, db_ln1, dw_mw, dw_mh, dw_p, db_p, *d_mlp, None, None)
@@ -1968,8 +1875,7 @@ class _CbamFunction(torch.autograd.Function):
         out = torch.empty_like(x)
         ca = torch.empty((N, C), device=x.device, dtype=torch.float32)
         sa = torch.empty((N, H * W), device=x.device, dtype=torch.float32)
-        _lib.check(_lib.lib().tpspp_cbam_train_fwd(_ptr(x), _ptr(w1), _ptr(w2), _ptr(cw), _ptr(cb), N, C, Cr, H, W, _ptr(out),
-                                                   _ptr(ca), _ptr(sa), _stream(x)), "tpspp_cbam_train_fwd")
+        _call("tpspp_cbam_train_fwd", x, x, w1, w2, cw, cb, N, C, Cr, H, W, out, ca, sa)
         ctx.save_for_backward(x, w1, w2, cw, cb)
         return out
 
@@ -1987,15 +1893,13 @@ class _CbamFunction(torch.autograd.Function):
         dx = torch.empty_like(x)          # the kernel forms dx on the way to the parameter gradients in any case
         g = [torch.empty(t.shape, device=dev, dtype=torch.float32) if need[i + 1] else None
              for i, t in enumerate((w1, w2, cw, cb))]
-        n = cbam_bwd_workspace_floats(N, C, Cr)
-        ws = _ws(n, dev)
-        _lib.check(_lib.lib().tpspp_cbam_bwd(_ptr(gout), _ptr(x), _ptr(w1), _ptr(w2), _ptr(cw), _ptr(cb), N, C, Cr, H, W,
-                                             _ptr(dx), *(_ptr(t) for t in g), _ptr(ws), n, _stream(x)), "tpspp_cbam_bwd")
+        ws, n = _ws_n(cbam_bwd_workspace_floats(N, C, Cr), dev)
+        _call("tpspp_cbam_bwd", x, gout, x, w1, w2, cw, cb, N, C, Cr, H, W, dx, *g, ws, n)
         return (dx if need[0] else None, *g)
 
 
 def cbam_bwd_workspace_floats(N, C, Cr):
-    return int(_lib.lib().tpspp_cbam_bwd_workspace_floats(int(N), int(C), int(Cr)))
+    return _query("tpspp_cbam_bwd_workspace_floats", N, C, Cr)
 
 
 def cbam_autograd(x, mod):
@@ -2075,12 +1979,12 @@ def _chk_like(who, name, t, ref):
 
 def bn_stats_workspace_floats(N, C, HW):
     """Floats of workspace `bn_train_stats` needs (`tpspp_bn_stats_workspace_floats`): 3 per channel and slice of 4096."""
-    return int(_lib.lib().tpspp_bn_stats_workspace_floats(int(N), int(C), int(HW)))
+    return _query("tpspp_bn_stats_workspace_floats", N, C, HW)
 
 
 def bn_bwd_reduce_workspace_floats(N, C, HW):
     """Floats of workspace `bn_bwd_reduce` needs (`tpspp_bn_bwd_reduce_workspace_floats`)."""
-    return int(_lib.lib().tpspp_bn_bwd_reduce_workspace_floats(int(N), int(C), int(HW)))
+    return _query("tpspp_bn_bwd_reduce_workspace_floats", N, C, HW)
 
 
 def bn_train_stats(z, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, num_batches_tracked=None):
@@ -2103,13 +2007,9 @@ def bn_train_stats(z, eps=1e-5, momentum=0.1, running_mean=None, running_var=Non
         raise ValueError("bn_train_stats: momentum=None needs num_batches_tracked")
     mean = torch.empty((C,), device=dev, dtype=torch.float32)
     rstd = torch.empty((C,), device=dev, dtype=torch.float32)
-    nws = bn_stats_workspace_floats(N, C, HW)
-    ws = _ws(nws, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_train_stats(_ptr(z), N, C, HW, float(eps), -1.0 if momentum is None else float(momentum),
-                                             _ptr(num_batches_tracked), _ptr(running_mean), _ptr(running_var), _ptr(mean),
-                                             _ptr(rstd), _ptr(ws), nws, _stream(z))
-    _lib.check(rc, "tpspp_bn_train_stats")
+    ws, nws = _ws_n(bn_stats_workspace_floats(N, C, HW), dev)
+    _call("tpspp_bn_train_stats", z, z, N, C, HW, float(eps), -1.0 if momentum is None else float(momentum),
+          num_batches_tracked, running_mean, running_var, mean, rstd, ws, nws)
     return mean, rstd
 
 
@@ -2119,10 +2019,7 @@ def bn_eval_stats(running_mean, running_var, eps=1e-5):
     rm = _chk("bn_eval_stats running_mean", running_mean, 1)
     rv = _chk_vec("bn_eval_stats", "running_var", running_var, rm.shape[0], rm.device)
     mean, rstd = torch.empty_like(rm), torch.empty_like(rm)
-    with torch.cuda.device(rm.device):
-        rc = _lib.lib().tpspp_bn_eval_stats(_ptr(rm), _ptr(rv), rm.shape[0], float(eps), _ptr(mean), _ptr(rstd),
-                                            _stream(rm))
-    _lib.check(rc, "tpspp_bn_eval_stats")
+    _call("tpspp_bn_eval_stats", rm, rm, rv, rm.shape[0], float(eps), mean, rstd)
     return mean, rstd
 
 
@@ -2145,10 +2042,7 @@ def bn_apply(za, stats_a, gamma_a, beta_a, residual=None, zb=None, stats_b=None,
                                                        zip(("mean_b", "rstd_b", "gamma_b", "beta_b"),
                                                            (*stats_b, gamma_b, beta_b)))
     y = torch.empty_like(za)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_apply_fwd(_ptr(za), _ptr(ma), _ptr(ra), _ptr(ga), _ptr(ba), res_mode, _ptr(residual),
-                                           *[_ptr(t) for t in mb], int(bool(relu)), N, C, HW, _ptr(y), _stream(za))
-    _lib.check(rc, "tpspp_bn_apply_fwd")
+    _call("tpspp_bn_apply_fwd", za, za, ma, ra, ga, ba, res_mode, residual, *mb, int(bool(relu)), N, C, HW, y)
     return y
 
 
@@ -2168,13 +2062,8 @@ def bn_bwd_reduce(dy, y, za, stats_a, zb=None, stats_b=None, relu=True):
         sxb = torch.empty((C,), device=dev, dtype=torch.float32)
     sdr = torch.empty((C,), device=dev, dtype=torch.float32)
     sxa = torch.empty((C,), device=dev, dtype=torch.float32)
-    nws = bn_bwd_reduce_workspace_floats(N, C, HW)
-    ws = _ws(nws, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_bwd_reduce(_ptr(dy), _ptr(y), int(bool(relu)), _ptr(za), _ptr(ma), _ptr(ra), _ptr(zb),
-                                            _ptr(mb), _ptr(rb), N, C, HW, _ptr(sdr), _ptr(sxa), _ptr(sxb), _ptr(ws), nws,
-                                            _stream(dy))
-    _lib.check(rc, "tpspp_bn_bwd_reduce")
+    ws, nws = _ws_n(bn_bwd_reduce_workspace_floats(N, C, HW), dev)
+    _call("tpspp_bn_bwd_reduce", dy, dy, y, int(bool(relu)), za, ma, ra, zb, mb, rb, N, C, HW, sdr, sxa, sxb, ws, nws)
     return sdr, sxa, sxb
 
 
@@ -2212,12 +2101,8 @@ def bn_bwd_data(dy, y, za=None, stats_a=None, gamma_a=None, sums=None, train_a=T
         if not isinstance(dres, torch.Tensor) or not dres.is_contiguous():
             raise ValueError("bn_bwd_data: dres must be a contiguous tensor (it is written in place)")
         dres = _chk_like(who, "dres", dres, dy)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_bwd_data(_ptr(dy), _ptr(y), int(bool(relu)), *[_ptr(t) for t in args_a[:5]],
-                                          int(bool(train_a)), _ptr(args_a[5]), *[_ptr(t) for t in args_b[:5]],
-                                          int(bool(train_b)), _ptr(args_b[5]), _ptr(sdr), _ptr(dres), int(dres_mode),
-                                          N, C, HW, _stream(dy))
-    _lib.check(rc, "tpspp_bn_bwd_data")
+    _call("tpspp_bn_bwd_data", dy, dy, y, int(bool(relu)), *args_a[:5], int(bool(train_a)), args_a[5],
+          *args_b[:5], int(bool(train_b)), args_b[5], sdr, dres, int(dres_mode), N, C, HW)
     return dza, dzb
 
 
@@ -2427,15 +2312,13 @@ def bn_pool2x2_fwd(z, stats, gamma, beta):
     who = "bn_pool2x2_fwd"
     z, (N, C, H, W), vecs = _bn_pool_args(who, z, stats, gamma, beta)
     p = torch.empty((N, C, H // 2, W // 2), device=z.device, dtype=torch.float32)
-    with torch.cuda.device(z.device):
-        rc = _lib.lib().tpspp_bn_pool2x2_fwd(_ptr(z), *[_ptr(t) for t in vecs], N, C, H, W, _ptr(p), _stream(z))
-    _lib.check(rc, "tpspp_bn_pool2x2_fwd")
+    _call("tpspp_bn_pool2x2_fwd", z, z, *vecs, N, C, H, W, p)
     return p
 
 
 def bn_pool2x2_bwd_reduce_workspace_floats(N, C, H, W):
     """Floats of workspace `bn_pool2x2_bwd_reduce` needs: 2 per channel and slice of 4096 elements of N*H*W."""
-    return int(_lib.lib().tpspp_bn_pool2x2_bwd_reduce_workspace_floats(int(N), int(C), int(H), int(W)))
+    return _query("tpspp_bn_pool2x2_bwd_reduce_workspace_floats", N, C, H, W)
 
 
 def bn_pool2x2_bwd_reduce(dp, z, stats, gamma, beta):
@@ -2447,12 +2330,8 @@ def bn_pool2x2_bwd_reduce(dp, z, stats, gamma, beta):
     dp = _chk_pooled_grad(who, dp, (N, C, H, W), dev)
     sdr = torch.empty((C,), device=dev, dtype=torch.float32)
     sx = torch.empty((C,), device=dev, dtype=torch.float32)
-    nws = bn_pool2x2_bwd_reduce_workspace_floats(N, C, H, W)
-    ws = _ws(nws, dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_pool2x2_bwd_reduce(_ptr(dp), _ptr(z), *[_ptr(t) for t in vecs], N, C, H, W, _ptr(sdr),
-                                                    _ptr(sx), _ptr(ws), nws, _stream(dp))
-    _lib.check(rc, "tpspp_bn_pool2x2_bwd_reduce")
+    ws, nws = _ws_n(bn_pool2x2_bwd_reduce_workspace_floats(N, C, H, W), dev)
+    _call("tpspp_bn_pool2x2_bwd_reduce", dp, dp, z, *vecs, N, C, H, W, sdr, sx, ws, nws)
     return sdr, sx
 
 
@@ -2469,10 +2348,7 @@ def bn_pool2x2_bwd_data(dp, z, stats, gamma, beta, sums=None, train=True):
             raise ValueError("bn_pool2x2_bwd_data: a training-mode BatchNorm needs the sums of bn_pool2x2_bwd_reduce")
         sdr, sx = (_chk_vec(who, n, t, C, dev) for n, t in zip(("sum_dr", "sum_dr_x"), sums))
     dz = torch.empty_like(z)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_bn_pool2x2_bwd_data(_ptr(dp), _ptr(z), *[_ptr(t) for t in vecs], _ptr(sdr), _ptr(sx),
-                                                  int(bool(train)), N, C, H, W, _ptr(dz), _stream(dp))
-    _lib.check(rc, "tpspp_bn_pool2x2_bwd_data")
+    _call("tpspp_bn_pool2x2_bwd_data", dp, dp, z, *vecs, sdr, sx, int(bool(train)), N, C, H, W, dz)
     return dz
 
 
@@ -2482,9 +2358,7 @@ def global_avgpool_bwd(g, hw):
     N, C = g.shape
     H, W = int(hw[0]), int(hw[1])
     dx = torch.empty((N, C, H, W), device=g.device, dtype=torch.float32)
-    with torch.cuda.device(g.device):
-        rc = _lib.lib().tpspp_global_avgpool_bwd(_ptr(g), N, C, H, W, _ptr(dx), _stream(g))
-    _lib.check(rc, "tpspp_global_avgpool_bwd")
+    _call("tpspp_global_avgpool_bwd", g, g, N, C, H, W, dx)
     return dx
 
 
@@ -2668,38 +2542,31 @@ def attn_train_fwd(q, k, v, ld, N, C, heads, Tq, Tk, valid_len, drop_p, seed, of
     """`tpspp_attn_train_fwd` on raw operands (rows `ld` elements apart): (out (N*Tq, C), lse (N, heads, Tq))."""
     out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
     lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
-    _lib.check(_lib.lib().tpspp_attn_train_fwd(_ptr(q), _ptr(k), _ptr(v), ld, N, C, heads, Tq, Tk, _ptr(valid_len),
-                                               float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(out), _ptr(lse),
-                                               _stream(q)), "tpspp_attn_train_fwd")
+    _call("tpspp_attn_train_fwd", q, q, k, v, ld, N, C, heads, Tq, Tk, valid_len, float(drop_p), int(seed) & _U64,
+          int(offset) & _U64, out, lse)
     return out, lse
 
 
 def attn_train_bwd(d_out, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len, drop_p, seed, offset, dq, dk, dv, ld_grad):
     """`tpspp_attn_train_bwd`: writes dq (N*Tq rows), dk, dv (N*Tk rows), rows `ld_grad` elements apart."""
-    _lib.check(_lib.lib().tpspp_attn_train_bwd(_ptr(d_out), _ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), N, C, heads,
-                                               Tq, Tk, _ptr(valid_len), float(drop_p), int(seed) & _U64, int(offset) & _U64,
-                                               _ptr(dq), _ptr(dk), _ptr(dv), ld_grad, _stream(d_out)),
-               "tpspp_attn_train_bwd")
+    _call("tpspp_attn_train_bwd", d_out, d_out, q, k, v, ld, out, lse, N, C, heads, Tq, Tk, valid_len, float(drop_p),
+          int(seed) & _U64, int(offset) & _U64, dq, dk, dv, ld_grad)
 
 
 def attn_train_fwd_ex(q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed, offset):
     """`tpspp_attn_train_fwd_ex` on raw operands: (out (N*Tq, C), lse (N, heads, Tq))."""
     out = torch.empty((N * Tq, C), device=q.device, dtype=torch.float32)
     lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
-    _lib.check(_lib.lib().tpspp_attn_train_fwd_ex(_ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, N, C, heads, Tq, Tk, _ptr(valid_len),
-                                                  _ptr(key_mask), int(bool(causal)), float(drop_p), int(seed) & _U64,
-                                                  int(offset) & _U64, _ptr(out), _ptr(lse), _stream(q)),
-               "tpspp_attn_train_fwd_ex")
+    _call("tpspp_attn_train_fwd_ex", q, q, ld_q, k, v, ld_kv, N, C, heads, Tq, Tk, valid_len, key_mask, int(bool(causal)),
+          float(drop_p), int(seed) & _U64, int(offset) & _U64, out, lse)
     return out, lse
 
 
 def attn_train_bwd_ex(d_out, q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask, causal, drop_p, seed,
                       offset, dq, ld_dq, dk, dv, ld_dkv):
     """`tpspp_attn_train_bwd_ex`: writes dq (N*Tq rows, `ld_dq` apart), dk, dv (N*Tk rows, `ld_dkv` apart)."""
-    _lib.check(_lib.lib().tpspp_attn_train_bwd_ex(_ptr(d_out), _ptr(q), ld_q, _ptr(k), _ptr(v), ld_kv, _ptr(out), _ptr(lse), N,
-                                                  C, heads, Tq, Tk, _ptr(valid_len), _ptr(key_mask), int(bool(causal)),
-                                                  float(drop_p), int(seed) & _U64, int(offset) & _U64, _ptr(dq), ld_dq,
-                                                  _ptr(dk), _ptr(dv), ld_dkv, _stream(d_out)), "tpspp_attn_train_bwd_ex")
+    _call("tpspp_attn_train_bwd_ex", d_out, d_out, q, ld_q, k, v, ld_kv, out, lse, N, C, heads, Tq, Tk, valid_len, key_mask,
+          int(bool(causal)), float(drop_p), int(seed) & _U64, int(offset) & _U64, dq, ld_dq, dk, dv, ld_dkv)
 
 
 def attn_dropout_mask(N, heads, Tq, Tk, drop_p, seed, offset, device):
@@ -2709,9 +2576,7 @@ def attn_dropout_mask(N, heads, Tq, Tk, drop_p, seed, offset, device):
     if device.type != "cuda":
         raise _lib.TpsppError(f"attn_dropout_mask: device is {device}; the HIP path needs a GPU (no CPU fallback)")
     mask = torch.empty((N, heads, Tq, Tk), device=device, dtype=torch.uint8)
-    _lib.check(_lib.lib().tpspp_attn_dropout_mask(N, heads, Tq, Tk, float(drop_p), int(seed) & _U64, int(offset) & _U64,
-                                                  _ptr(mask), torch.cuda.current_stream(device).cuda_stream),
-               "tpspp_attn_dropout_mask")
+    _call("tpspp_attn_dropout_mask", device, N, heads, Tq, Tk, float(drop_p), int(seed) & _U64, int(offset) & _U64, mask)
     return mask
 
 
@@ -3021,13 +2886,12 @@ def embed_pos_fwd(tok, weight, pos):
     """`tpspp_embed_pos_fwd`: weight[tok] + pos[:L] -> (N, L, C); tok (N, L) int32 on the device."""
     N, L = tok.shape
     out = torch.empty((N, L, weight.shape[1]), device=weight.device, dtype=torch.float32)
-    _lib.check(_lib.lib().tpspp_embed_pos_fwd(_ptr(tok), _ptr(weight), _ptr(pos), N, L, weight.shape[1], weight.shape[0],
-                                              _ptr(out), _stream(weight)), "tpspp_embed_pos_fwd")
+    _call("tpspp_embed_pos_fwd", weight, tok, weight, pos, N, L, weight.shape[1], weight.shape[0], out)
     return out
 
 
 def embed_bwd_workspace_floats(M, num_classes, C):
-    return int(_lib.lib().tpspp_embed_bwd_workspace_floats(int(M), int(num_classes), int(C)))
+    return _query("tpspp_embed_bwd_workspace_floats", M, num_classes, C)
 
 
 def embed_bwd(dx, tok, num_classes, padding_idx):
@@ -3036,10 +2900,8 @@ def embed_bwd(dx, tok, num_classes, padding_idx):
     if M == 0:
         return torch.zeros((num_classes, C), device=dx.device, dtype=torch.float32)
     dw = torch.empty((num_classes, C), device=dx.device, dtype=torch.float32)
-    n = embed_bwd_workspace_floats(M, num_classes, C)
-    ws = _ws(n, dx.device)
-    _lib.check(_lib.lib().tpspp_embed_bwd(_ptr(dx), _ptr(tok), M, C, num_classes, -1 if padding_idx is None else padding_idx,
-                                          _ptr(dw), _ptr(ws), n, _stream(dx)), "tpspp_embed_bwd")
+    ws, n = _ws_n(embed_bwd_workspace_floats(M, num_classes, C), dx.device)
+    _call("tpspp_embed_bwd", dx, dx, tok, M, C, num_classes, -1 if padding_idx is None else padding_idx, dw, ws, n)
     return dw
 
 
@@ -3074,7 +2936,7 @@ def embed_pos_autograd(tokens, emb_weight, pos_table, padding_idx=None):
     return _EmbedPosFunction.apply(emb_weight, tok, pos, padding_idx)
 
 
-_CE_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
+_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 
 
 def _ce_operands(who, logits, targets, shift):
@@ -3106,9 +2968,8 @@ def seq_ce_fwd(logits, tgt, shift, ignore_index, reduction):
     if N == 0 and reduction:                   # the library returns before any launch
         red.fill_(float("nan") if reduction == 1 else 0.0)
         cnt.zero_()
-    _lib.check(_lib.lib().tpspp_seq_ce_fwd(_ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2), _ptr(tgt), N, L,
-                                           K, int(shift), int(ignore_index), reduction, _ptr(loss), _ptr(lse), _ptr(red),
-                                           _ptr(cnt), _stream(logits)), "tpspp_seq_ce_fwd")
+    _call("tpspp_seq_ce_fwd", logits, logits, logits.stride(0), logits.stride(1), logits.stride(2), tgt, N, L, K,
+          int(shift), int(ignore_index), reduction, loss, lse, red, cnt)
     return loss, lse, red, cnt
 
 
@@ -3116,9 +2977,8 @@ def seq_ce_bwd(g, logits, tgt, lse, cnt, shift, ignore_index, reduction):
     """`tpspp_seq_ce_bwd`: d_logits (N, L, K) dense."""
     N, L, K = logits.shape
     d = torch.empty((N, L, K), device=logits.device, dtype=torch.float32)
-    _lib.check(_lib.lib().tpspp_seq_ce_bwd(_ptr(g), _ptr(logits), logits.stride(0), logits.stride(1), logits.stride(2),
-                                           _ptr(tgt), _ptr(lse), _ptr(cnt), N, L, K, int(shift), int(ignore_index), reduction,
-                                           _ptr(d), _stream(logits)), "tpspp_seq_ce_bwd")
+    _call("tpspp_seq_ce_bwd", logits, g, logits, logits.stride(0), logits.stride(1), logits.stride(2), tgt, lse, cnt, N, L,
+          K, int(shift), int(ignore_index), reduction, d)
     return d
 
 
@@ -3152,10 +3012,10 @@ def seq_cross_entropy_autograd(logits, targets, ignore_index=-100, reduction="no
     "mean" / "sum", (N * L',) for "none" with flatten, else (N, L'), L' = L - shift.  The logits are read through their
     strides (no copy for a view such as logits[:, :-1]); targets on the host or on the device, any integer type."""
     who = "seq_cross_entropy_autograd"
-    if reduction not in _CE_REDUCTIONS:
+    if reduction not in _REDUCTIONS:
         raise ValueError(f'{who}: reduction must be "none", "mean" or "sum", got {reduction!r}')
     tgt = _ce_operands(who, logits, targets, shift)
-    return _SeqCeFunction.apply(logits, tgt, (bool(shift), int(ignore_index), _CE_REDUCTIONS[reduction], bool(flatten)))
+    return _SeqCeFunction.apply(logits, tgt, (bool(shift), int(ignore_index), _REDUCTIONS[reduction], bool(flatten)))
 
 
 class _LinearFunction(torch.autograd.Function):
@@ -3215,9 +3075,7 @@ def crnn_maxpool(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
         raise ValueError(f"crnn_maxpool: kernel {(kh, kw)} / stride {(sh, sw)} / padding {(ph, pw)} on a {H} x {W} map")
     Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
     out = torch.empty((N, C, Ho, Wo), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_crnn_maxpool_fwd(_ptr(x), N, C, H, W, kh, kw, sh, sw, ph, pw, _ptr(out), Ho, Wo, _stream(x))
-    _lib.check(rc, "tpspp_crnn_maxpool_fwd")
+    _call("tpspp_crnn_maxpool_fwd", x, x, N, C, H, W, kh, kw, sh, sw, ph, pw, out, Ho, Wo)
     return out
 
 
@@ -3235,10 +3093,7 @@ def crnn_maxpool_blocked(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
     out = type(x)(torch.empty((N, C // 8, Ho, Wo, 8), device=x.device, dtype=x.dtype))
     if N == 0:          # an empty batch has no device pointer to hand over
         return out
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().tpspp_crnn_maxpool_blk_fwd(x.data_ptr(), _layout_code(x), N, C, H, W, kh, kw, sh, sw, ph, pw,
-                                                   out.data_ptr(), Ho, Wo, _stream(x.t))
-    _lib.check(rc, "tpspp_crnn_maxpool_blk_fwd")
+    _call("tpspp_crnn_maxpool_blk_fwd", x.t, x.t, _layout_code(x), N, C, H, W, kh, kw, sh, sw, ph, pw, out.t, Ho, Wo)
     return out
 
 
@@ -3248,7 +3103,7 @@ CRNN_LSTM_GROUPS = (4, 8, 16)          # the accepted non-zero images_per_group 
 
 def crnn_lstm_plan(N, images_per_group=0, compute_units=0):
     """`tpspp_crnn_lstm_plan`: the images per workgroup `crnn_lstm` uses (host only; compute_units 0: the current device's)."""
-    g = _lib.lib().tpspp_crnn_lstm_plan(int(N), int(images_per_group), int(compute_units))
+    g = _query("tpspp_crnn_lstm_plan", N, images_per_group, compute_units)
     _lib.check(min(g, 0), "tpspp_crnn_lstm_plan")
     return g
 
@@ -3265,10 +3120,7 @@ def crnn_lstm(xg, w_hh, images_per_group=0):
     out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
     if N == 0:
         return out
-    with torch.cuda.device(xg.device):
-        rc = _lib.lib().tpspp_crnn_lstm_fwd(_ptr(xg), _ptr(w_hh), _ptr(out), T, N, CRNN_HIDDEN, int(images_per_group),
-                                            _stream(xg))
-    _lib.check(rc, "tpspp_crnn_lstm_fwd")
+    _call("tpspp_crnn_lstm_fwd", xg, xg, w_hh, out, T, N, CRNN_HIDDEN, int(images_per_group))
     return out
 
 
@@ -3284,10 +3136,7 @@ def crnn_ctc_decode_device(logits, decode_len, blank=0):
     score = torch.empty((N, T), device=logits.device, dtype=torch.float32)
     if N == 0:
         return idx, score
-    with torch.cuda.device(logits.device):
-        rc = _lib.lib().tpspp_crnn_ctc_decode(_ptr(logits), _ptr(decode_len), N, T, C, int(blank), _ptr(idx), _ptr(score),
-                                              _stream(logits))
-    _lib.check(rc, "tpspp_crnn_ctc_decode")
+    _call("tpspp_crnn_ctc_decode", logits, logits, decode_len, N, T, C, int(blank), idx, score)
     return idx, score
 
 
@@ -3304,10 +3153,8 @@ def crnn_ctc_decode(logits, decode_len, blank=0):
         z = buf.cpu().numpy()
         return z.reshape(0, T), z.view("float32").reshape(0, T)
     buf[2 * N * T:].copy_(torch.tensor([int(v) for v in decode_len], dtype=torch.int32))
-    with torch.cuda.device(logits.device):
-        rc = _lib.lib().tpspp_crnn_ctc_decode(_ptr(logits), buf.data_ptr() + 8 * N * T, N, T, C, int(blank), buf.data_ptr(),
-                                              buf.data_ptr() + 4 * N * T, _stream(logits))
-    _lib.check(rc, "tpspp_crnn_ctc_decode")
+    _call("tpspp_crnn_ctc_decode", logits, logits, buf.data_ptr() + 8 * N * T, N, T, C, int(blank), buf.data_ptr(),
+          buf.data_ptr() + 4 * N * T)
     host = buf[:2 * N * T].cpu().numpy()
     return host[:N * T].reshape(N, T), host[N * T:].view("float32").reshape(N, T)
 
@@ -3334,10 +3181,7 @@ def crnn_lstm_train_fwd(xg, w_hh, images_per_group=0):
     cell = torch.empty((T, N, 2, CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
     if N == 0:
         return out, gates, cell
-    with torch.cuda.device(xg.device):
-        rc = _lib.lib().tpspp_crnn_lstm_train_fwd(_ptr(xg), _ptr(w_hh), _ptr(out), _ptr(gates), _ptr(cell), T, N, CRNN_HIDDEN,
-                                                  int(images_per_group), _stream(xg))
-    _lib.check(rc, "tpspp_crnn_lstm_train_fwd")
+    _call("tpspp_crnn_lstm_train_fwd", xg, xg, w_hh, out, gates, cell, T, N, CRNN_HIDDEN, int(images_per_group))
     return out, gates, cell
 
 
@@ -3356,10 +3200,8 @@ def crnn_lstm_bwd(d_out, gates, cell, w_hh_t, images_per_group=0, direction_majo
     d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
     d_dir = torch.empty((2, T, N, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32) if direction_major else None
     if N > 0:
-        with torch.cuda.device(gates.device):
-            rc = _lib.lib().tpspp_crnn_lstm_bwd(_ptr(d_out), _ptr(gates), _ptr(cell), _ptr(w_hh_t), _ptr(d_xg), _ptr(d_dir), T, N,
-                                                CRNN_HIDDEN, int(images_per_group), _stream(gates))
-        _lib.check(rc, "tpspp_crnn_lstm_bwd")
+        _call("tpspp_crnn_lstm_bwd", gates, d_out, gates, cell, w_hh_t, d_xg, d_dir, T, N, CRNN_HIDDEN,
+              int(images_per_group))
     return (d_xg, d_dir) if direction_major else d_xg
 
 
@@ -3477,12 +3319,11 @@ def linear_nwc_autograd(x, lin):
     return _LinearNwcFunction.apply(x, lin.weight, lin.bias)
 
 
-_CTC_REDUCTIONS = {"none": 0, "mean": 1, "sum": 2}
 CTC_MAX_CLASSES, CTC_MAX_TARGET = 1024, 1024
 
 
 def crnn_ctc_loss_workspace_floats(N, T, Lmax):
-    return int(_lib.lib().tpspp_crnn_ctc_loss_workspace_floats(int(N), int(T), int(Lmax)))
+    return _query("tpspp_crnn_ctc_loss_workspace_floats", N, T, Lmax)
 
 
 def _ctc_operands(who, logits, targets, target_len, input_len):
@@ -3508,15 +3349,11 @@ def crnn_ctc_loss_fwd(logits, targets, target_len, input_len, blank=0, zero_infi
     loss = torch.empty((N,), device=dev, dtype=torch.float32)
     lse = torch.empty((N, T), device=dev, dtype=torch.float32)
     red = torch.empty((1,), device=dev, dtype=torch.float32) if reduction else None
-    n = crnn_ctc_loss_workspace_floats(N, T, Lmax)
-    ws = _ws(n, dev)
+    ws, n = _ws_n(crnn_ctc_loss_workspace_floats(N, T, Lmax), dev)
     if N == 0 and reduction:                   # the library returns before any launch
         red.fill_(float("nan") if reduction == 1 else 0.0)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().tpspp_crnn_ctc_loss_fwd(_ptr(logits), _ptr(targets), _ptr(target_len), _ptr(input_len), N, T, C, Lmax,
-                                                int(blank), int(bool(zero_infinity)), reduction, _ptr(loss), _ptr(lse),
-                                                _ptr(red), _ptr(ws), n, _stream(logits))
-    _lib.check(rc, "tpspp_crnn_ctc_loss_fwd")
+    _call("tpspp_crnn_ctc_loss_fwd", logits, logits, targets, target_len, input_len, N, T, C, Lmax, int(blank),
+          int(bool(zero_infinity)), reduction, loss, lse, red, ws, n)
     return loss, lse, red, ws
 
 
@@ -3524,11 +3361,8 @@ def crnn_ctc_loss_bwd(g, logits, targets, target_len, input_len, lse, ws, blank=
     """`tpspp_crnn_ctc_loss_bwd`: d_logits (N, T, C) dense, exact zeros from each image's input length on."""
     N, T, C = logits.shape
     d = torch.empty((N, T, C), device=logits.device, dtype=torch.float32)
-    with torch.cuda.device(logits.device):
-        rc = _lib.lib().tpspp_crnn_ctc_loss_bwd(_ptr(g), _ptr(logits), _ptr(targets), _ptr(target_len), _ptr(input_len),
-                                                _ptr(lse), _ptr(ws), N, T, C, targets.shape[1], int(blank),
-                                                int(bool(zero_infinity)), reduction, _ptr(d), _stream(logits))
-    _lib.check(rc, "tpspp_crnn_ctc_loss_bwd")
+    _call("tpspp_crnn_ctc_loss_bwd", logits, g, logits, targets, target_len, input_len, lse, ws, N, T, C, targets.shape[1],
+          int(blank), int(bool(zero_infinity)), reduction, d)
     return d
 
 
@@ -3561,7 +3395,7 @@ def crnn_ctc_loss_autograd(logits, targets, target_len, input_len, blank=0, redu
     device; lengths are clamped to 0 .. Lmax and 0 .. T.  Targets on the host are checked here, where they originate: one
     outside 0 .. C - 1 or equal to blank (within its image's length) raises."""
     who = "crnn_ctc_loss_autograd"
-    if reduction not in _CTC_REDUCTIONS:
+    if reduction not in _REDUCTIONS:
         raise ValueError(f'{who}: reduction must be "none", "mean" or "sum", got {reduction!r}')
     if isinstance(logits, torch.Tensor) and logits.dim() == 3:
         N, T, C = logits.shape
@@ -3580,4 +3414,4 @@ def crnn_ctc_loss_autograd(logits, targets, target_len, input_len, blank=0, redu
                                  f"{logits.shape[2] - 1} or the blank {int(blank)}")
     logits, targets, target_len, input_len = _ctc_operands(who, logits, targets, target_len, input_len)
     return _CtcLossFunction.apply(logits, targets, target_len, input_len,
-                                  (int(blank), bool(zero_infinity), _CTC_REDUCTIONS[reduction]))
+                                  (int(blank), bool(zero_infinity), _REDUCTIONS[reduction]))

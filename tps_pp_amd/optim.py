@@ -27,6 +27,7 @@ import math
 import torch
 
 from . import _lib
+from .ops import _call
 
 CHUNK = 4096      # elements per workgroup and THREADS per workgroup: scripts/bench_optimizer.py's sweep
 THREADS = 1024
@@ -231,21 +232,15 @@ class _MultiTensorAdam(torch.optim.Optimizer):
             self._scalars = self._upload(rows, torch.float32, (len(rows), 4), device, into=self._scalars)
             self._rows = rows
             self.scalar_uploads += 1
-        L = _lib.lib()
-        with torch.cuda.device(device):
-            stream = torch.cuda.current_stream(device).cuda_stream
-            coef = 0
-            if self.max_norm is not None:
-                _lib.check(L.tpspp_mt_sumsq(self._table.data_ptr(), self._n_tensors, self._map.data_ptr(), self._n_chunks,
-                                            self.chunk, self.threads, self._partials.data_ptr(), self._partials.numel(),
-                                            stream), "tpspp_mt_sumsq")
-                _lib.check(L.tpspp_mt_norm_finish(self._partials.data_ptr(), self._n_chunks, self.max_norm,
-                                                  self._norm.data_ptr(), stream), "tpspp_mt_norm_finish")
-                self.last_grad_norm = self._norm[0]
-                coef = self._norm.data_ptr() + 4
-            _lib.check(L.tpspp_mt_adam(self._table.data_ptr(), self._scalars.data_ptr(), self._n_tensors, self._map.data_ptr(),
-                                       self._n_chunks, self.chunk, self.threads, beta1, beta2, eps, _MODES[self._MODE], coef,
-                                       stream), "tpspp_mt_adam")
+        coef = 0
+        if self.max_norm is not None:
+            _call("tpspp_mt_sumsq", device, self._table, self._n_tensors, self._map, self._n_chunks, self.chunk, self.threads,
+                  self._partials, self._partials.numel())
+            _call("tpspp_mt_norm_finish", device, self._partials, self._n_chunks, self.max_norm, self._norm)
+            self.last_grad_norm = self._norm[0]
+            coef = self._norm.data_ptr() + 4
+        _call("tpspp_mt_adam", device, self._table, self._scalars, self._n_tensors, self._map, self._n_chunks, self.chunk,
+              self.threads, beta1, beta2, eps, _MODES[self._MODE], coef)
         # the kernel wrote through raw pointers: tell autograd and the prepared-weight cache that the parameters changed
         torch.autograd.graph.increment_version([p for p, k in zip(params, key) if k[2]])
         return loss
@@ -267,10 +262,7 @@ class _MultiTensorAdam(torch.optim.Optimizer):
         self._prepare(key, params, where)
         if self._n_chunks == 0:
             return
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().tpspp_mt_zero(self._table.data_ptr(), self._n_tensors, self._map.data_ptr(), self._n_chunks,
-                                                self.chunk, self.threads, torch.cuda.current_stream(device).cuda_stream),
-                       "tpspp_mt_zero")
+        _call("tpspp_mt_zero", device, self._table, self._n_tensors, self._map, self._n_chunks, self.chunk, self.threads)
         torch.autograd.graph.increment_version([p.grad for p, k in zip(params, key) if k[2]])
 
 
