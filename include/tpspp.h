@@ -270,6 +270,37 @@ int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, int H0, int W0
                    float* g_grid_ws, size_t g_grid_ws_floats, tpspp_stream_t stream);
 
 /*
+ * The kernels tpspp_warp_bwd launches for these arguments (a host-side query: touches no device, works without one, launches
+ * nothing).  Takes tpspp_warp_bwd's arguments without the stream; a pointer is only compared with NULL and read for its
+ * alignment, never dereferenced, so any address with the alignment of the real buffer will do.  Both functions decide through
+ * one planner (warp_bwd_plan, tpspp_warp_bwd.hip): whatever tpspp_warp_bwd refuses -- null pointers, bad sizes, a workspace
+ * that is too small, N > 65535, the TPSPP_IO_BF16 shapes -- is refused here with the same TPSPP_EINVAL and the same
+ * tpspp_last_error text; honours tpspp_warp_bwd_set_accumulator.  On TPSPP_OK `route` (at least TPSPP_WARP_BWD_ROUTE_INTS
+ * ints, checked) holds:
+ *   [0]  sampling family: 0 the one-launch classic kernel, 1 its bf16 form, 2 kernel A'' ("lds2": 8-byte LDS accumulators,
+ *        per-workgroup slices of dL/d grid), 3 kernel A' ("lds": fp32 LDS atomics), 4 kernel A ("atomics": fp32 global
+ *        atomics, dL/d input zeroed by memsets); -1 with N = 0 (accepted, nothing to launch; every other entry is 0)
+ *   [1] [2]  kernel A'': output pixels per thread (1, 2, 4) and threads per workgroup (256, 1024)
+ *   [3]  1 = dL/d input accumulated in fp64, 0 = 64-bit fixed point (families 0, 1, 2)      [4]  1 = bf16 images and gradients
+ *   [5]  G, sampling workgroups per (image, input) (families 2, 3; at most 8)
+ *   [6] [7]  channels per chunk of input 0 / 1        [8] [9]  channel chunks of input 0 / 1 (families 2, 3, 4)
+ *   [10] slices of dL/d grid the parameter kernel adds, in ascending order (G x inputs for families 2 and 3; the channel
+ *        chunks of both inputs, at most 16, for family 4; 0 for the one-launch forms): dL/d grid never goes through atomics
+ *   [11] 1 = warp_bwd_params_kernel follows (families 2, 3, 4); then its instantiation and grid:
+ *   [12] KMAX (24, 36, 64: the smallest that holds F + 3)   [13] TABLE (0 classic [1, x, y, rbf], 1 TPS_PP: p_xy given)
+ *   [14] TRANSPOSED (p_hat_t given)   [15] SCORE (0 none, 1 (N, n, F), 2 (N, F, n))   [16] GSCORE (g_score wanted)
+ *   [17] S, workgroups per image (1..8), each over ceil(Ho*Wo / S) pixels
+ */
+#define TPSPP_WARP_BWD_ROUTE_INTS 18
+int tpspp_warp_bwd_route(const float* g_out0, const float* in0, int C0, int H0, int W0,
+                         const float* g_out1, const float* in1, int C1, int H1, int W1,
+                         const float* grid, const float* T, const float* inv_delta_c,
+                         const float* p_hat, int p_hat_ld, const float* p_xy, const float* score,
+                         const float* p_hat_t_or_null, int table_flags, int N, int F, int Ho, int Wo,
+                         const float* g_in0, const float* g_in1, const float* g_ctrl, const float* g_score,
+                         const float* g_grid_ws, size_t g_grid_ws_floats, int* route, int route_ints);
+
+/*
  * out = act(conv2d(cat_c(up(src_0), up(src_1), up(src_2)), W) + bias [+ residual]) [+ residual]
  *       [* post_scale + post_shift]
  * fp32, NCHW, 1x1 or 3x3 kernel with "same" padding ((K-1)/2), stride (sh, sw), on the fp32 matrix

@@ -20,6 +20,7 @@ ALLOWED = {
         "WarpPlan.run": "the headline's hot path: one foreign call on a stored handle, the status read only when non-zero",
         "conv2d_route": "host-side query of a host array whose negative result is an error code for _lib.check",
         "nrtr_decoder_route": "host-side query of a host pointer table whose negative result is an error code",
+        "warp_backward_route": "host-side query of pointers (alignment only) whose non-zero status is an error for _lib.check",
         "crnn_lstm_plan": "host-side query (through _query) whose negative result is an error code for _lib.check",
         "set_warp_bwd_accumulator": "process-wide setter: no tensor, no stream, no device",
         "set_warp_tuning": "process-wide setter: no tensor, no stream, no device",

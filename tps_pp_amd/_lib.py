@@ -94,6 +94,8 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_warp_bwd_set_accumulator": ([_i], _i),
     "tpspp_warp_bwd": ([_f, _f, _i, _i, _i, _f, _f, _i, _i, _i, _f, _f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _i,
                         _f, _f, _f, _f, _f, ctypes.c_size_t, _f], _i),
+    "tpspp_warp_bwd_route": ([_f, _f, _i, _i, _i, _f, _f, _i, _i, _i, _f, _f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _i,
+                              _f, _f, _f, _f, _f, ctypes.c_size_t, _f, _i], _i),
     "tpspp_transpose2d": ([_f, _i, _i, _f, _f], _i),
     "tpspp_layernorm_cm_fwd": ([_f, _f, _f, _i, _i, ctypes.c_float, _f, _f], _i),
     "tpspp_attn_enc_fwd": ([_f, _i, _i, _i, _f, _f, _f], _i),

@@ -9,7 +9,7 @@
 //   A (thread = pixel x 8 channels of one input): dL/d(ix, iy) from the four taps (ATen's CPU formulation:
 //     gx += ((ne - nw) s + (se - sw) n) g,  gy += ((sw - nw) e + (se - ne) w) g), times (size-1)/2 and
 //     the border-clip derivative (0 where the coordinate was clamped); dL/d in_i scattered with float
-//     atomics (taps of neighbouring pixels overlap), the chunk's coordinate gradient added to g_grid;
+//     atomics (taps of neighbouring pixels overlap), the coordinate gradients stored as slices that kernel B adds in order;
 //   B (workgroup = image):
 //   dL/ds[p][k] = 0.5 rbf[p][k] (g_grid(p) . T[3+k]);
 //   dL/dT[k] = sum_p row(p)[k] g_grid(p)  (register partials, wavefront shuffles, LDS across wavefronts);
@@ -48,9 +48,8 @@ struct BwdParams {
 };
 
 // ---- kernel A: sampler backward.  Thread = one output pixel x kCPT channels of one input ---------------
-// grid = (pixel blocks, channel chunks of input 0 then input 1, images).  dL/d input goes out as float
-// atomics (fire-and-forget), the coordinate gradient of the chunk is added to g_grid[b][p] (zeroed by
-// the host side), so the parallelism is N * n * C / kCPT threads instead of N * n.  unsafeAtomicAdd = the
+// grid = (pixel blocks, channel chunks of input 0 then input 1 -- at most 16 rows --, images).  dL/d input goes out as float
+// atomics (fire-and-forget), so the parallelism is N * n * C / kCPT threads instead of N * n.  unsafeAtomicAdd = the
 // hardware's return-less global_atomic_add_f32 (valid on ordinary device allocations; plain atomicAdd on a
 // float compiles to a compare-and-swap loop here, 10x slower).
 constexpr int kCPT = 8;
@@ -61,14 +60,21 @@ constexpr int kBwdMaxG = 8;      // sampling workgroups per (image, input) of ke
 __device__ __forceinline__ float ld_io(const float* p) { return *p; }
 __device__ __forceinline__ float ld_io(const unsigned short* p) { return bf16_bits_to_f32(*p); }
 
+// The coordinate gradient does NOT go through atomics: a float sum in arrival order would make dL/d grid, and with it dL/d
+// control points and dL/d score, differ from run to run as soon as three chunks meet in a pixel.  grid.y = min(chunks, 16)
+// and a thread walks the chunks y, y + grid.y, ... in ascending order, sums their coordinate gradients in registers and
+// stores ONE slice element (workspace (N, grid.y, n, 2), as kernel A''); the parameter kernel adds the slices in ascending order.
 __global__ void __launch_bounds__(256)
-warp_bwd_sample_kernel(const BwdParams P, int chunks0, float* __restrict__ g_grid)
+warp_bwd_sample_kernel(const BwdParams P, int chunks0, int chunks1, float* __restrict__ g_grid_part)
 {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P.n) return;
     const int b = blockIdx.z;
-    const int i = (int)blockIdx.y >= chunks0 ? 1 : 0;
-    const int c_lo = ((int)blockIdx.y - (i ? chunks0 : 0)) * kCPT;
+    float sx = 0.0f, sy = 0.0f;
+#pragma unroll 1
+    for (int cy = blockIdx.y; cy < chunks0 + chunks1; cy += gridDim.y) {
+    const int i = cy >= chunks0 ? 1 : 0;
+    const int c_lo = (cy - (i ? chunks0 : 0)) * kCPT;
     const int H = P.H[i], W = P.W[i], C = P.C[i];
     const int c_hi = min(C, c_lo + kCPT);
     const float2 g = reinterpret_cast<const float2*>(P.grid)[(size_t)b * P.n + p];
@@ -112,9 +118,10 @@ warp_bwd_sample_kernel(const BwdParams P, int chunks0, float* __restrict__ g_gri
             }
         }
     }
-    float* gg = g_grid + ((size_t)b * P.n + p) * 2;
-    unsafeAtomicAdd(gg, gx * mx);
-    unsafeAtomicAdd(gg + 1, gy * my);
+    sx += gx * mx;
+    sy += gy * my;
+    }
+    reinterpret_cast<float2*>(g_grid_part)[((size_t)b * gridDim.y + blockIdx.y) * P.n + p] = make_float2(sx, sy);
 }
 
 // ---- kernel A': the same with the input-gradient planes accumulated in LDS ------------------------------
@@ -123,10 +130,10 @@ warp_bwd_sample_kernel(const BwdParams P, int chunks0, float* __restrict__ g_gri
 // every G-th channel chunk), walks ALL output pixels for each of its chunks, accumulates dL/d input with
 // LDS atomics (ds_add_f32) and writes each plane once, coalesced, without a preceding memset; the
 // coordinate gradients of its chunks are summed per pixel in LDS too (a thread always owns the same
-// pixels) and reach g_grid as ONE pair of global atomics per pixel and workgroup.
+// pixels) and leave as the workgroup's slice of the workspace.
 // grid = (G groups of input 0 then G groups of input 1, images).
 __global__ void __launch_bounds__(1024)
-warp_bwd_sample_lds_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* __restrict__ g_grid)
+warp_bwd_sample_lds_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* __restrict__ g_grid_part)
 {
     extern __shared__ float smem[];
     float* sgg = smem;                                     // [n][2] coordinate gradients of this workgroup
@@ -197,8 +204,10 @@ warp_bwd_sample_lds_kernel(const BwdParams P, int G, int cpt0, int cpt1, float* 
         }
     }
     __syncthreads();
-    float* gg = g_grid + (size_t)b * P.n * 2;
-    for (int e = threadIdx.x; e < 2 * P.n; e += blockDim.x) unsafeAtomicAdd(gg + e, sgg[e]);
+    // this workgroup's slice (workspace (N, G x inputs, n, 2), as kernel A''; a group without a chunk stores zeros): plain
+    // stores, added by the parameter kernel in ascending order, so that dL/d grid has a fixed summation order
+    float* gg = g_grid_part + ((size_t)b * gridDim.x + blockIdx.x) * P.n * 2;
+    for (int e = threadIdx.x; e < 2 * P.n; e += blockDim.x) gg[e] = sgg[e];
 }
 
 // ---- kernel A'' (round 3): input-gradient planes accumulated in LDS as 64-bit FIXED POINT ------------------
@@ -492,6 +501,9 @@ warp_bwd_params_kernel(const BwdParams P, float* __restrict__ g_grid, const floa
                     for (int sl = 1; sl < 2 * kBwdMaxG; ++sl) if (sl < slots) { gg.x += part[sl].x; gg.y += part[sl].y; }
                     reinterpret_cast<float2*>(g_grid)[(size_t)b * n + p] = gg;      // dL/d grid, as documented
                 } else {
+                    // slots == 0 = dL/d grid already summed in place.  warp_bwd_plan never asks for it (every sampling kernel
+                    // leaves 1 .. 2 kBwdMaxG slices); the branch stays because without it the compiler keeps part[] of the
+                    // KMAX = 64 instantiations in a 36-byte private segment (tests/test_no_new_scratch.py)
                     gg = reinterpret_cast<const float2*>(g_grid)[(size_t)b * n + p];
                 }
             }
@@ -891,14 +903,32 @@ TPSPP_EXPORT size_t tpspp_warp_bwd_workspace_floats(int N, int Ho, int Wo)
          + (size_t)N + 2;                                      // + its arrival counters (one int per image)
 }
 
-TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, int H0, int W0,
-                                const float* g_out1, const float* in1, int C1, int H1, int W1,
-                                const float* grid, const float* T, const float* inv_delta_c,
-                                const float* p_hat, int p_hat_ld, const float* p_xy, const float* score,
-                                const float* p_hat_t_or_null, int table_flags, int N, int F, int Ho, int Wo,
-                                float* g_in0, float* g_in1, float* g_ctrl, float* g_score,
-                                float* g_grid_ws, size_t g_grid_ws_floats, tpspp_stream_t stream)
+// ---- the planner: every decision of tpspp_warp_bwd, taken on the host from the arguments alone ---------------------------
+// tpspp_warp_bwd launches from this record and tpspp_warp_bwd_route reports it: there is no second copy of a condition.
+// Pointers are compared with NULL and read for their alignment, never dereferenced.
+namespace {
+
+enum BwdFamily { kBwdClassic = 0, kBwdClassicBf16 = 1, kBwdLds2 = 2, kBwdLds = 3, kBwdAtomics = 4 };
+
+struct BwdPlan {
+    bool empty;                    // N == 0: the arguments are accepted and nothing is launched
+    int family;                    // BwdFamily
+    int ppt, nt, f64, bf16;        // kernel A'': pixels per thread, threads, fp64 (1) or fixed-point (0) accumulators, bf16 I/O
+    int G, cpt0, cpt1, chunks0, chunks1, slots;
+    size_t lds;                    // dynamic LDS bytes of the sampling launch
+    int params;                    // 1: warp_bwd_params_kernel follows (every family but the one-launch forms)
+    int kmax, table, transposed, score, gscore, S;
+};
+
+int warp_bwd_plan(const float* g_out0, const float* in0, int C0, int H0, int W0,
+                  const float* g_out1, const float* in1, int C1, int H1, int W1,
+                  const float* grid, const float* T, const float* inv_delta_c,
+                  const float* p_hat, int p_hat_ld, const float* p_xy, const float* score,
+                  const float* p_hat_t_or_null, int table_flags, int N, int F, int Ho, int Wo,
+                  const float* g_in0, const float* g_in1, const float* g_ctrl, const float* g_score,
+                  const float* g_grid_ws, size_t g_grid_ws_floats, BwdPlan& pl)
 {
+    pl = BwdPlan{};
     TPSPP_REQUIRE(g_grid_ws_floats >= tpspp_warp_bwd_workspace_floats(N, Ho, Wo),
                   "tpspp_warp_bwd: g_grid_ws too small (needs tpspp_warp_bwd_workspace_floats(N, Ho, Wo) floats)");
     TPSPP_REQUIRE(g_out0 && in0 && grid && inv_delta_c && p_hat && g_ctrl && g_grid_ws, "tpspp_warp_bwd: null pointer");
@@ -930,26 +960,11 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
                                "<= 4096, input planes of at most 4096 pixels and a multiple of 8, 16-byte aligned images); "
                                "here: %s", why);
     }
-    if (N == 0) return TPSPP_OK;
-    hipStream_t st = tpspp::as_stream(stream);
-    BwdParams P;
-    P.g_out[0] = g_out0; P.in[0] = in0; P.g_in[0] = g_in0; P.C[0] = C0; P.H[0] = H0; P.W[0] = W0;
-    P.g_out[1] = g_out1; P.in[1] = in1; P.g_in[1] = g_in1; P.C[1] = C1; P.H[1] = H1; P.W[1] = W1;
-    P.nin = in1 ? 2 : 1;
-    P.grid = grid; P.T = T; P.inv_delta_c = inv_delta_c; P.p_hat = p_hat; P.p_hat_ld = p_hat_ld;
-    P.p_hat_t = p_hat_t_or_null; P.p_xy = p_xy; P.score = score;
-    P.score_t = (score && (table_flags & TPSPP_SCORE_TRANSPOSED)) ? 1 : 0;
-    P.g_ctrl = g_ctrl; P.g_score = g_score; P.N = N; P.F = F; P.n = Ho * Wo;
+    if (N == 0) { pl.empty = true; return TPSPP_OK; }
     TPSPP_REQUIRE(N <= 65535, "tpspp_warp_bwd: N > 65535");
-    const dim3 block(256);
+    const int n = Ho * Wo, nin = in1 ? 2 : 1;
+    const int score_t = (score && (table_flags & TPSPP_SCORE_TRANSPOSED)) ? 1 : 0;
     const size_t plane0 = (size_t)H0 * W0 * sizeof(float), plane1 = in1 ? (size_t)H1 * W1 * sizeof(float) : 0;
-    int slots = 0;
-    float* part = g_grid_ws + (size_t)N * P.n * 2;          // behind dL/d grid: the sampling workgroups' slices
-    // the parameter kernel's partial dL/dT (fp64, behind the slices, at an 8-byte boundary) and arrival counters
-    double* gT_part = reinterpret_cast<double*>(
-        (reinterpret_cast<uintptr_t>(g_grid_ws + (size_t)N * P.n * 2 * (1 + 2 * kBwdMaxG)) + 7) & ~(uintptr_t)7);
-    int* arrivals = reinterpret_cast<int*>(gT_part + (size_t)N * kBwdMaxS * 2 * kMaxK);
-    bool arrivals_zeroed = false;                           // (the LDS-accumulating sampling kernel zeroes them itself)
     // kernel A'': two fixed-point planes (8 bytes per element) of a pass in <= 64 KB of LDS, <= 4096 output pixels
     // (1024-thread workgroups above 1024: the classic 32x100 geometry), planes of whole 16-byte pieces
     const size_t kLds2 = 16 * 1024;
@@ -962,38 +977,24 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
     const bool io_bf16 = (table_flags & TPSPP_IO_BF16) != 0;
     // kernel A'' for either element type: the grid, the workspace slices and the LDS are the same (the accumulators are 8
     // bytes per element whatever the planes hold)
-    auto launch_lds2 = [&](auto io) {
-        constexpr bool BF16 = decltype(io)::value;
+    auto plan_lds2 = [&](bool bf16) {
+        pl.family = kBwdLds2; pl.bf16 = bf16 ? 1 : 0; pl.f64 = fixed_point ? 0 : 1;
         // channels per chunk: a chunk is worked off two planes at a time, so the LDS only ever holds two
         const int cpt0 = 8, cpt1 = 8;
         const int chunks0 = (C0 + cpt0 - 1) / cpt0, chunks1 = in1 ? (C1 + cpt1 - 1) / cpt1 : 0;
         const int most = chunks0 > chunks1 ? chunks0 : chunks1;
-        const bool big = P.n > 1024;                        // 1024-thread workgroups, 4 pixels per thread
-        int G = ((big ? 1024 : 4096) + N * P.nin - 1) / (N * P.nin);      // ~16 (4) workgroups of 256 (1024) threads per CU
+        const bool big = n > 1024;                          // 1024-thread workgroups, 4 pixels per thread
+        int G = ((big ? 1024 : 4096) + N * nin - 1) / (N * nin);          // ~16 (4) workgroups of 256 (1024) threads per CU
         G = G < 1 ? 1 : (G > most ? most : G);
         G = G > kBwdMaxG ? kBwdMaxG : G;
-        slots = G * P.nin;                                  // every slice is written by its workgroup (round 5: was 2 G with a
+        pl.G = G; pl.cpt0 = cpt0; pl.cpt1 = cpt1; pl.chunks0 = chunks0; pl.chunks1 = chunks1;
+        pl.slots = G * nin;                                 // every slice is written by its workgroup (round 5: was 2 G with a
                                                             // 26-MB memset of the unused half for single-input calls)
-        const size_t accb = 2 * 8 * (elems0 > elems1 ? elems0 : elems1);      // two planes x 8 bytes per element
-        const dim3 g2((unsigned)(G * P.nin), (unsigned)N);
-        auto go = [&](auto f64) {
-            constexpr bool F64 = decltype(f64)::value;
-#define TPSPP_LDS2(PPT, NT)                                                                                                  \
-            do {                                                                                                             \
-                if constexpr (BF16) hipLaunchKernelGGL((warp_bwd_sample_lds2_bf16_kernel<PPT, NT, F64>), g2, dim3(NT), accb, st, P, G, \
-                                             cpt0, cpt1, part, arrivals);                                                    \
-                else hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<PPT, NT, F64>), g2, dim3(NT), accb, st, P, G, cpt0,     \
-                                        cpt1, part, arrivals);                                                               \
-            } while (0)
-            if (P.n <= 256)       TPSPP_LDS2(1, 256);
-            else if (P.n <= 512)  TPSPP_LDS2(2, 256);
-            else if (P.n <= 1024) TPSPP_LDS2(4, 256);
-            else                  TPSPP_LDS2(4, 1024);
-#undef TPSPP_LDS2
-        };
-        if (fixed_point) go(std::false_type{});
-        else go(std::true_type{});
-        arrivals_zeroed = true;
+        pl.lds = 2 * 8 * (elems0 > elems1 ? elems0 : elems1);                 // two planes x 8 bytes per element
+        if (n <= 256)       { pl.ppt = 1; pl.nt = 256; }
+        else if (n <= 512)  { pl.ppt = 2; pl.nt = 256; }
+        else if (n <= 1024) { pl.ppt = 4; pl.nt = 256; }
+        else                { pl.ppt = 4; pl.nt = 1024; }
     };
     if (io_bf16) {
         // the one-launch form: the fp32 form's conditions with the image staged at TWO bytes per pixel.  LDS = the fp64
@@ -1002,85 +1003,186 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
         // staged in 16-byte pieces (elems0 % 8 == 0 and in0 aligned: checked before the N == 0 return), g_in0 leaves in 4-byte pieces.
         const size_t lds = (size_t)C0 * elems0 * 8;
         if (!in1 && !score && !p_xy && !fixed_point && !two_kernels && C0 <= 3 && F + 3 <= 24 &&
-            p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && P.n % 4 == 0 &&
-            P.n > 1024 && lds <= 78 * 1024 && lds >= (size_t)P.n * 8 && lds >= ((size_t)C0 * elems0 + W0 + 1) * 2) {
-            auto go = [&](auto cc) {
-                constexpr int CC = decltype(cc)::value;
-                static bool attr_done[tpspp::kMaxDevices] = {};
-                if (tpspp::first_use_on_device(attr_done)) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&warp_bwd_classic_bf16_kernel<CC>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024);
-                    (void)hipGetLastError();
-                }
-                hipLaunchKernelGGL(warp_bwd_classic_bf16_kernel<CC>, dim3((unsigned)N), dim3(kClassicNT), lds, st, P, g_grid_ws);
-            };
-            if (C0 == 1) go(std::integral_constant<int, 1>{});
-            else if (C0 == 2) go(std::integral_constant<int, 2>{});
-            else go(std::integral_constant<int, 3>{});
-            return tpspp::check_launch("tpspp_warp_bwd(classic, bf16 planes)");
+            p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && n % 4 == 0 &&
+            n > 1024 && lds <= 78 * 1024 && lds >= (size_t)n * 8 && lds >= ((size_t)C0 * elems0 + W0 + 1) * 2) {
+            pl.family = kBwdClassicBf16; pl.bf16 = 1; pl.f64 = 1; pl.lds = lds;
+            return TPSPP_OK;
         }
-        launch_lds2(std::true_type{});
+        plan_lds2(true);
     } else if (!in1 && !score && !p_xy && !fixed_point && !two_kernels && C0 <= 3 && F + 3 <= 24 &&
-        p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && P.n % 4 == 0 &&
-        P.n > 1024 && P.n <= 4096 && (size_t)C0 * plane0 * 2 <= 78 * 1024 && (size_t)C0 * plane0 * 2 >= (size_t)P.n * 8 &&
+        p_hat_t_or_null && reinterpret_cast<uintptr_t>(p_hat_t_or_null) % 16 == 0 && n % 4 == 0 &&
+        n > 1024 && n <= 4096 && (size_t)C0 * plane0 * 2 <= 78 * 1024 && (size_t)C0 * plane0 * 2 >= (size_t)n * 8 &&
         (size_t)C0 * plane0 * 2 >= (size_t)C0 * plane0 + ((size_t)W0 + 1) * 4 &&
         plane0 % 16 == 0 && reinterpret_cast<uintptr_t>(in0) % 16 == 0 && (!g_in0 || reinterpret_cast<uintptr_t>(g_in0) % 16 == 0)) {
-        const size_t lds = (size_t)C0 * plane0 * 2;
-        auto go = [&](auto cc) {
-            constexpr int CC = decltype(cc)::value;
-            static bool attr_done[tpspp::kMaxDevices] = {};
-            if (tpspp::first_use_on_device(attr_done)) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&warp_bwd_classic_kernel<CC>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024);
-                (void)hipGetLastError();
-            }
-            hipLaunchKernelGGL(warp_bwd_classic_kernel<CC>, dim3((unsigned)N), dim3(kClassicNT), lds, st, P, g_grid_ws);
-        };
-        if (C0 == 1) go(std::integral_constant<int, 1>{});
-        else if (C0 == 2) go(std::integral_constant<int, 2>{});
-        else go(std::integral_constant<int, 3>{});
-        return tpspp::check_launch("tpspp_warp_bwd(classic)");
-    } else if (P.n <= 4096 && plane0 <= kLds2 && plane1 <= kLds2 && plane0 % 16 == 0 && plane1 % 16 == 0 &&
+        pl.family = kBwdClassic; pl.f64 = 1; pl.lds = (size_t)C0 * plane0 * 2;
+        return TPSPP_OK;
+    } else if (n <= 4096 && plane0 <= kLds2 && plane1 <= kLds2 && plane0 % 16 == 0 && plane1 % 16 == 0 &&
         (!g_in0 || reinterpret_cast<uintptr_t>(g_in0) % 16 == 0) && (!g_in1 || reinterpret_cast<uintptr_t>(g_in1) % 16 == 0)) {
-        launch_lds2(std::false_type{});
+        plan_lds2(false);
     } else {
-    if (hipMemsetAsync(g_grid_ws, 0, (size_t)N * P.n * 2 * sizeof(float), st) != hipSuccess)
-        return tpspp::check_launch("tpspp_warp_bwd(memset)");
     // LDS-accumulating sampler backward when whole planes fit (64 KB per workgroup), else global atomics
     const size_t kLdsBudget = 64 * 1024;
-    const size_t gg_bytes = (size_t)P.n * 2 * sizeof(float);
+    const size_t gg_bytes = (size_t)n * 2 * sizeof(float);
     if (plane0 <= kLdsBudget && plane1 <= kLdsBudget && gg_bytes <= 32 * 1024) {
         const int cpt0 = (int)(kLdsBudget / plane0 < (size_t)kCPT ? kLdsBudget / plane0 : (size_t)kCPT);
         const int cpt1 = in1 ? (int)(kLdsBudget / plane1 < (size_t)kCPT ? kLdsBudget / plane1 : (size_t)kCPT) : 1;
         const int chunks0 = (C0 + cpt0 - 1) / cpt0, chunks1 = in1 ? (C1 + cpt1 - 1) / cpt1 : 0;
         const int most = chunks0 > chunks1 ? chunks0 : chunks1;
-        int G = (2048 + N * P.nin - 1) / (N * P.nin);      // enough workgroups for ~4 per CU
+        int G = (2048 + N * nin - 1) / (N * nin);          // enough workgroups for ~4 per CU
         G = G < 1 ? 1 : (G > most ? most : G);
+        G = G > kBwdMaxG ? kBwdMaxG : G;                    // one slice of dL/d grid per workgroup: the workspace holds 2 kBwdMaxG
+        pl.slots = G * nin;
         const size_t accb = (size_t)cpt0 * plane0 > (size_t)cpt1 * plane1 ? (size_t)cpt0 * plane0 : (size_t)cpt1 * plane1;
-        const size_t lds = gg_bytes + accb;
-        static bool attr_done[tpspp::kMaxDevices] = {};
-        if (tpspp::first_use_on_device(attr_done)) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&warp_bwd_sample_lds_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(warp_bwd_sample_lds_kernel, dim3((unsigned)(G * P.nin), (unsigned)N), dim3(1024), lds, st, P,
-                           G, cpt0, cpt1, g_grid_ws);
+        pl.family = kBwdLds; pl.G = G; pl.cpt0 = cpt0; pl.cpt1 = cpt1; pl.chunks0 = chunks0; pl.chunks1 = chunks1;
+        pl.lds = gg_bytes + accb;
     } else {
-        if (g_in0 && hipMemsetAsync(g_in0, 0, (size_t)N * C0 * H0 * W0 * sizeof(float), st) != hipSuccess)
-            return tpspp::check_launch("tpspp_warp_bwd(memset)");
-        if (g_in1 && hipMemsetAsync(g_in1, 0, (size_t)N * C1 * H1 * W1 * sizeof(float), st) != hipSuccess)
-            return tpspp::check_launch("tpspp_warp_bwd(memset)");
-        const int chunks0 = (C0 + kCPT - 1) / kCPT, chunks1 = in1 ? (C1 + kCPT - 1) / kCPT : 0;
-        hipLaunchKernelGGL(warp_bwd_sample_kernel, dim3((unsigned)((P.n + 255) / 256), (unsigned)(chunks0 + chunks1), (unsigned)N),
-                           block, 0, st, P, chunks0, g_grid_ws);
+        pl.family = kBwdAtomics; pl.cpt0 = kCPT; pl.cpt1 = kCPT;
+        pl.chunks0 = (C0 + kCPT - 1) / kCPT; pl.chunks1 = in1 ? (C1 + kCPT - 1) / kCPT : 0;
+        // grid.y = slices of dL/d grid: a row of workgroups walks the chunks y, y + slots, ...
+        pl.slots = pl.chunks0 + pl.chunks1 > 2 * kBwdMaxG ? 2 * kBwdMaxG : pl.chunks0 + pl.chunks1;
     }
     }
     // parameter gradients: S workgroups per image (about eight workgroups per CU in all, at least 256 pixels each), then
     // the reduction over S
     int S = (2048 + N - 1) / N;
     S = S < 1 ? 1 : (S > kBwdMaxS ? kBwdMaxS : S);
-    while (S > 1 && (P.n + S - 1) / S < 256) --S;
+    while (S > 1 && (n + S - 1) / S < 256) --S;
+    pl.params = 1; pl.S = S;
+    pl.kmax = F + 3 <= 24 ? 24 : (F + 3 <= 36 ? 36 : 64);
+    pl.table = p_xy ? 1 : 0;
+    pl.transposed = p_hat_t_or_null ? 1 : 0;
+    pl.score = !score ? 0 : (score_t ? 2 : 1);
+    pl.gscore = (score && g_score) ? 1 : 0;
+    return TPSPP_OK;
+}
+
+}  // namespace
+
+// What warp_bwd_plan decided, as TPSPP_WARP_BWD_ROUTE_INTS ints (include/tpspp.h lists them); nothing is launched.
+TPSPP_EXPORT int tpspp_warp_bwd_route(const float* g_out0, const float* in0, int C0, int H0, int W0,
+                                      const float* g_out1, const float* in1, int C1, int H1, int W1,
+                                      const float* grid, const float* T, const float* inv_delta_c,
+                                      const float* p_hat, int p_hat_ld, const float* p_xy, const float* score,
+                                      const float* p_hat_t_or_null, int table_flags, int N, int F, int Ho, int Wo,
+                                      const float* g_in0, const float* g_in1, const float* g_ctrl, const float* g_score,
+                                      const float* g_grid_ws, size_t g_grid_ws_floats, int* route, int route_ints)
+{
+    TPSPP_REQUIRE(route && route_ints >= TPSPP_WARP_BWD_ROUTE_INTS,
+                  "tpspp_warp_bwd_route: route must hold TPSPP_WARP_BWD_ROUTE_INTS (%d) ints", TPSPP_WARP_BWD_ROUTE_INTS);
+    BwdPlan pl;
+    const int rc = warp_bwd_plan(g_out0, in0, C0, H0, W0, g_out1, in1, C1, H1, W1, grid, T, inv_delta_c, p_hat, p_hat_ld, p_xy,
+                                 score, p_hat_t_or_null, table_flags, N, F, Ho, Wo, g_in0, g_in1, g_ctrl, g_score, g_grid_ws,
+                                 g_grid_ws_floats, pl);
+    if (rc != TPSPP_OK) return rc;
+    const int v[TPSPP_WARP_BWD_ROUTE_INTS] = {pl.empty ? -1 : pl.family, pl.ppt, pl.nt, pl.f64, pl.bf16, pl.G, pl.cpt0, pl.cpt1,
+                                              pl.chunks0, pl.chunks1, pl.slots, pl.params, pl.kmax, pl.table, pl.transposed,
+                                              pl.score, pl.gscore, pl.S};
+    for (int i = 0; i < TPSPP_WARP_BWD_ROUTE_INTS; ++i) route[i] = v[i];
+    return TPSPP_OK;
+}
+
+TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, int H0, int W0,
+                                const float* g_out1, const float* in1, int C1, int H1, int W1,
+                                const float* grid, const float* T, const float* inv_delta_c,
+                                const float* p_hat, int p_hat_ld, const float* p_xy, const float* score,
+                                const float* p_hat_t_or_null, int table_flags, int N, int F, int Ho, int Wo,
+                                float* g_in0, float* g_in1, float* g_ctrl, float* g_score,
+                                float* g_grid_ws, size_t g_grid_ws_floats, tpspp_stream_t stream)
+{
+    BwdPlan pl;
+    const int rc = warp_bwd_plan(g_out0, in0, C0, H0, W0, g_out1, in1, C1, H1, W1, grid, T, inv_delta_c, p_hat, p_hat_ld, p_xy,
+                                 score, p_hat_t_or_null, table_flags, N, F, Ho, Wo, g_in0, g_in1, g_ctrl, g_score, g_grid_ws,
+                                 g_grid_ws_floats, pl);
+    if (rc != TPSPP_OK || pl.empty) return rc;
+    hipStream_t st = tpspp::as_stream(stream);
+    BwdParams P;
+    P.g_out[0] = g_out0; P.in[0] = in0; P.g_in[0] = g_in0; P.C[0] = C0; P.H[0] = H0; P.W[0] = W0;
+    P.g_out[1] = g_out1; P.in[1] = in1; P.g_in[1] = g_in1; P.C[1] = C1; P.H[1] = H1; P.W[1] = W1;
+    P.nin = in1 ? 2 : 1;
+    P.grid = grid; P.T = T; P.inv_delta_c = inv_delta_c; P.p_hat = p_hat; P.p_hat_ld = p_hat_ld;
+    P.p_hat_t = p_hat_t_or_null; P.p_xy = p_xy; P.score = score;
+    P.score_t = pl.score == 2 ? 1 : 0;
+    P.g_ctrl = g_ctrl; P.g_score = g_score; P.N = N; P.F = F; P.n = Ho * Wo;
+    const dim3 block(256);
+    float* part = g_grid_ws + (size_t)N * P.n * 2;          // behind dL/d grid: the sampling workgroups' slices
+    // the parameter kernel's partial dL/dT (fp64, behind the slices, at an 8-byte boundary) and arrival counters
+    double* gT_part = reinterpret_cast<double*>(
+        (reinterpret_cast<uintptr_t>(g_grid_ws + (size_t)N * P.n * 2 * (1 + 2 * kBwdMaxG)) + 7) & ~(uintptr_t)7);
+    int* arrivals = reinterpret_cast<int*>(gT_part + (size_t)N * kBwdMaxS * 2 * kMaxK);
+    bool arrivals_zeroed = false;                           // (the LDS-accumulating sampling kernel zeroes them itself)
+    using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    // the classic geometry: sampling + parameter gradients in one launch (warp_bwd_classic_kernel), either element type
+    if (pl.family == kBwdClassic || pl.family == kBwdClassicBf16) {
+        auto go = [&](auto cc, auto io) {
+            constexpr int CC = decltype(cc)::value;
+            constexpr bool BF16 = decltype(io)::value;
+            static bool attr_done[tpspp::kMaxDevices] = {};
+            const void* kern = BF16 ? reinterpret_cast<const void*>(&warp_bwd_classic_bf16_kernel<CC>)
+                                    : reinterpret_cast<const void*>(&warp_bwd_classic_kernel<CC>);
+            if (tpspp::first_use_on_device(attr_done)) {
+                (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 78 * 1024);
+                (void)hipGetLastError();
+            }
+            if constexpr (BF16)
+                hipLaunchKernelGGL(warp_bwd_classic_bf16_kernel<CC>, dim3((unsigned)N), dim3(kClassicNT), pl.lds, st, P, g_grid_ws);
+            else
+                hipLaunchKernelGGL(warp_bwd_classic_kernel<CC>, dim3((unsigned)N), dim3(kClassicNT), pl.lds, st, P, g_grid_ws);
+        };
+        auto pick_c = [&](auto io) {
+            if (C0 == 1) go(I1{}, io);
+            else if (C0 == 2) go(I2{}, io);
+            else go(std::integral_constant<int, 3>{}, io);
+        };
+        if (pl.family == kBwdClassicBf16) { pick_c(std::true_type{}); return tpspp::check_launch("tpspp_warp_bwd(classic, bf16 planes)"); }
+        pick_c(std::false_type{});
+        return tpspp::check_launch("tpspp_warp_bwd(classic)");
+    }
+    if (pl.family == kBwdLds2) {
+        // kernel A'' for either element type: the grid, the workspace slices and the LDS are the same (the accumulators are 8
+        // bytes per element whatever the planes hold)
+        const dim3 g2((unsigned)(pl.G * P.nin), (unsigned)N);
+        auto go = [&](auto io, auto f64) {
+            constexpr bool BF16 = decltype(io)::value;
+            constexpr bool F64 = decltype(f64)::value;
+#define TPSPP_LDS2(PPT, NT)                                                                                                  \
+            do {                                                                                                             \
+                if constexpr (BF16) hipLaunchKernelGGL((warp_bwd_sample_lds2_bf16_kernel<PPT, NT, F64>), g2, dim3(NT), pl.lds, st, P, \
+                                             pl.G, pl.cpt0, pl.cpt1, part, arrivals);                                        \
+                else hipLaunchKernelGGL((warp_bwd_sample_lds2_kernel<PPT, NT, F64>), g2, dim3(NT), pl.lds, st, P, pl.G,      \
+                                        pl.cpt0, pl.cpt1, part, arrivals);                                                   \
+            } while (0)
+            if (pl.nt == 1024)    TPSPP_LDS2(4, 1024);
+            else if (pl.ppt == 1) TPSPP_LDS2(1, 256);
+            else if (pl.ppt == 2) TPSPP_LDS2(2, 256);
+            else                  TPSPP_LDS2(4, 256);
+#undef TPSPP_LDS2
+        };
+        if (pl.bf16) { if (pl.f64) go(std::true_type{}, std::true_type{}); else go(std::true_type{}, std::false_type{}); }
+        else { if (pl.f64) go(std::false_type{}, std::true_type{}); else go(std::false_type{}, std::false_type{}); }
+        arrivals_zeroed = true;
+    } else {
+        // (dL/d grid leaves as slices that the parameter kernel adds: nothing to zero)
+        if (pl.family == kBwdLds) {
+            static bool attr_done[tpspp::kMaxDevices] = {};
+            if (tpspp::first_use_on_device(attr_done)) {
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&warp_bwd_sample_lds_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                (void)hipGetLastError();
+            }
+            hipLaunchKernelGGL(warp_bwd_sample_lds_kernel, dim3((unsigned)(pl.G * P.nin), (unsigned)N), dim3(1024), pl.lds, st, P,
+                               pl.G, pl.cpt0, pl.cpt1, part);
+        } else {
+            if (g_in0 && hipMemsetAsync(g_in0, 0, (size_t)N * C0 * H0 * W0 * sizeof(float), st) != hipSuccess)
+                return tpspp::check_launch("tpspp_warp_bwd(memset)");
+            if (g_in1 && hipMemsetAsync(g_in1, 0, (size_t)N * C1 * H1 * W1 * sizeof(float), st) != hipSuccess)
+                return tpspp::check_launch("tpspp_warp_bwd(memset)");
+            hipLaunchKernelGGL(warp_bwd_sample_kernel,
+                               dim3((unsigned)((P.n + 255) / 256), (unsigned)pl.slots, (unsigned)N),
+                               block, 0, st, P, pl.chunks0, pl.chunks1, part);
+        }
+    }
+    // parameter gradients: S workgroups per image, then the reduction over S
+    const int S = pl.S, slots = pl.slots;
     if (S > 1 && !arrivals_zeroed && hipMemsetAsync(arrivals, 0, (size_t)N * sizeof(int), st) != hipSuccess)
         return tpspp::check_launch("tpspp_warp_bwd(memset)");
     const dim3 grid_dim((unsigned)(N * S));
@@ -1090,18 +1192,16 @@ TPSPP_EXPORT int tpspp_warp_bwd(const float* g_out0, const float* in0, int C0, i
         hipLaunchKernelGGL(kern, grid_dim, block, 0, st, P, g_grid_ws, part, slots, S, gT_part, arrivals);
     };
     auto pick_score = [&](auto kmax, auto table, auto transposed) {
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        if (!score) launch_b(kmax, table, transposed, I0{}, std::false_type{});
-        else if (P.score_t) { if (g_score) launch_b(kmax, table, transposed, I2{}, std::true_type{}); else launch_b(kmax, table, transposed, I2{}, std::false_type{}); }
-        else { if (g_score) launch_b(kmax, table, transposed, I1{}, std::true_type{}); else launch_b(kmax, table, transposed, I1{}, std::false_type{}); }
+        if (pl.score == 0) launch_b(kmax, table, transposed, I0{}, std::false_type{});
+        else if (pl.score == 2) { if (pl.gscore) launch_b(kmax, table, transposed, I2{}, std::true_type{}); else launch_b(kmax, table, transposed, I2{}, std::false_type{}); }
+        else { if (pl.gscore) launch_b(kmax, table, transposed, I1{}, std::true_type{}); else launch_b(kmax, table, transposed, I1{}, std::false_type{}); }
     };
     auto pick_table = [&](auto kmax) {
-        using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-        if (p_xy) { if (p_hat_t_or_null) pick_score(kmax, I1{}, std::true_type{}); else pick_score(kmax, I1{}, std::false_type{}); }
-        else { if (p_hat_t_or_null) pick_score(kmax, I0{}, std::true_type{}); else pick_score(kmax, I0{}, std::false_type{}); }
+        if (pl.table) { if (pl.transposed) pick_score(kmax, I1{}, std::true_type{}); else pick_score(kmax, I1{}, std::false_type{}); }
+        else { if (pl.transposed) pick_score(kmax, I0{}, std::true_type{}); else pick_score(kmax, I0{}, std::false_type{}); }
     };
-    if (F + 3 <= 24)      pick_table(std::integral_constant<int, 24>{});
-    else if (F + 3 <= 36) pick_table(std::integral_constant<int, 36>{});
-    else                  pick_table(std::integral_constant<int, 64>{});
+    if (pl.kmax == 24)      pick_table(std::integral_constant<int, 24>{});
+    else if (pl.kmax == 36) pick_table(std::integral_constant<int, 36>{});
+    else                    pick_table(std::integral_constant<int, 64>{});
     return tpspp::check_launch("tpspp_warp_bwd");
 }

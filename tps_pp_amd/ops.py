@@ -79,8 +79,12 @@ _F32 = (torch.float32,)
 _F32_BF16 = (torch.float32, torch.bfloat16)         # what the bf16 paths take
 
 
-def _chk(name, t, ndim=None, dtypes=_F32):
-    _chk_gpu(name, t)
+def _chk(name, t, ndim=None, dtypes=_F32, gpu=True):
+    """(`gpu=False`: a host-side query reads shapes and addresses only, so a CPU tensor will do.)"""
+    if gpu:
+        _chk_gpu(name, t)
+    elif not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor")
     if t.dtype not in dtypes:
         raise TypeError(f"{name}: expected {' or '.join(str(d)[6:] for d in dtypes)}, got {t.dtype}")
     if ndim is not None and t.dim() != ndim:
@@ -226,14 +230,14 @@ def table_mirror_symmetry(P_hat_host, out_hw, F):
     return _query("tpspp_table_mirror_symmetry", a.ctypes.data, a.shape[1], out_hw[0], out_hw[1], F)
 
 
-def _chk_score(who, score, N, n, F):
+def _chk_score(who, score, N, n, F, gpu=True):
     """(N, n, F) as the reference produces it, or a transposed VIEW of an (N, F, n) buffer: the latter is what lets lanes
     that own consecutive pixels read the score coalesced.  -> (the contiguous buffer, SCORE_TRANSPOSED | 0)."""
     if not isinstance(score, torch.Tensor) or tuple(score.shape) != (N, n, F):
         raise ValueError(f"{who}: score must be (N, n, F)")
     if score.stride() == (F * n, 1, n) and n > 1 and F > 1:
-        return _chk("score", score.transpose(1, 2), 3), SCORE_TRANSPOSED      # the underlying (N, F, n) buffer
-    return _chk("score", score, 3), 0
+        return _chk("score", score.transpose(1, 2), 3, gpu=gpu), SCORE_TRANSPOSED      # the underlying (N, F, n) buffer
+    return _chk("score", score, 3, gpu=gpu), 0
 
 
 def _warp_call(who, in0, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, out0, out1, P_hat_t, table_flags,
@@ -1443,6 +1447,52 @@ def augment_normalize(packed, offsets, src_h, src_w, resize_w, lut, pad_value, N
 
 
 # ---- backward of the fused warp ------------------------------------------------
+_WarpBwdCall = collections.namedtuple("_WarpBwdCall", "args in0 in1 ctrl inv_delta_C score N F Ho Wo flags")
+
+
+def _warp_bwd_marshal(who, gpu, g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, g_out1, P_hat_t,
+                      fixed_point, two_kernels):
+    """The checks and the argument order of one `tpspp_warp_bwd` call, shared by `warp_backward` (gpu=True) and
+    `warp_backward_route` (gpu=False: CPU tensors pass), so that the query sees exactly the launch's flags, sizes and
+    (contiguous) tensors.  `.args(T, g_in0, g_in1, g_ctrl, g_score, ws, ws_floats)` completes the argument tuple."""
+    io_dtype = in0.dtype if isinstance(in0, torch.Tensor) else None
+    for nm, t in (("g_out0", g_out0), ("in1", in1), ("g_out1", g_out1)):
+        if isinstance(t, torch.Tensor) and t.dtype != io_dtype:
+            raise TypeError(f"{who}: in0 / in1 / g_out0 / g_out1 must share their dtype (all float32 or all "
+                            f"bfloat16); in0 is {io_dtype}, {nm} is {t.dtype}")
+    io = (torch.bfloat16,) if io_dtype == torch.bfloat16 else _F32
+    chk = lambda name, t, ndim, dtypes=_F32: _chk(name, t, ndim, dtypes, gpu=gpu)      # noqa: E731
+    g_out0, in0 = chk("g_out0", g_out0, 4, io), chk("in0", in0, 4, io)
+    grid, ctrl = chk("grid", grid, 3), chk("ctrl", ctrl, 3)
+    inv_delta_C, P_hat = chk("inv_delta_C", inv_delta_C, 2), chk("P_hat", P_hat, 2)
+    N, C0, H0, W0 = in0.shape
+    F = int(ctrl.shape[1])
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    n = Ho * Wo
+    if tuple(g_out0.shape) != (N, C0, Ho, Wo) or tuple(grid.shape) != (N, n, 2):
+        raise ValueError(f"{who}: g_out0 / grid shape")
+    flags = (BWD_FIXED_POINT if fixed_point else 0) | (BWD_TWO_KERNELS if two_kernels else 0) | \
+        (IO_BF16 if io_dtype == torch.bfloat16 else 0)
+    if score is not None:
+        score, transposed = _chk_score(who, score, N, n, F, gpu=gpu)
+        flags |= transposed
+    if P_xy is not None:
+        P_xy = chk("P_xy", P_xy, 2)
+    if P_hat_t is not None:
+        P_hat_t = chk("P_hat_t", P_hat_t, 2)
+    C1 = H1 = W1 = 0
+    if in1 is not None:
+        in1, g_out1 = chk("in1", in1, 4, io), chk("g_out1", g_out1, 4, io)
+        _, C1, H1, W1 = in1.shape
+        if tuple(g_out1.shape) != (N, C1, Ho, Wo):
+            raise ValueError(f"{who}: g_out1 shape")
+
+    def args(T, g_in0, g_in1, g_ctrl, g_score, ws, ws_floats):
+        return (g_out0, in0, C0, H0, W0, g_out1, in1, C1, H1, W1, grid, T, inv_delta_C, P_hat, P_hat.shape[1], P_xy, score,
+                P_hat_t, flags, N, F, Ho, Wo, g_in0, g_in1, g_ctrl, g_score, ws, ws_floats)
+    return _WarpBwdCall(args, in0, in1, ctrl, inv_delta_C, score, N, F, Ho, Wo, flags)
+
+
 def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None,
                   g_out1=None, P_hat_t=None, need_in0=True, need_in1=True, need_score=True, fixed_point=False,
                   two_kernels=False):
@@ -1457,49 +1507,72 @@ def warp_backward(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None
     anything else is looked at): g_in0 / g_in1 come back in the images' dtype, g_ctrl / g_score, the grid, the tables and
     all accumulation stay fp32.  bfloat16 is served where dL/d input is finished in LDS (include/tpspp.h); any other
     shape raises with the library's message."""
-    io_dtype = in0.dtype if isinstance(in0, torch.Tensor) else None
-    for nm, t in (("g_out0", g_out0), ("in1", in1), ("g_out1", g_out1)):
-        if isinstance(t, torch.Tensor) and t.dtype != io_dtype:
-            raise TypeError(f"warp_backward: in0 / in1 / g_out0 / g_out1 must share their dtype (all float32 or all "
-                            f"bfloat16); in0 is {io_dtype}, {nm} is {t.dtype}")
-    io = (torch.bfloat16,) if io_dtype == torch.bfloat16 else _F32
-    g_out0, in0 = _chk("g_out0", g_out0, 4, io), _chk("in0", in0, 4, io)
-    grid, ctrl = _chk("grid", grid, 3), _chk("ctrl", ctrl, 3)
-    inv_delta_C, P_hat = _chk("inv_delta_C", inv_delta_C, 2), _chk("P_hat", P_hat, 2)
-    N, C0, H0, W0 = in0.shape
-    F = int(ctrl.shape[1])
-    Ho, Wo = int(out_hw[0]), int(out_hw[1])
-    n = Ho * Wo
-    if tuple(g_out0.shape) != (N, C0, Ho, Wo) or tuple(grid.shape) != (N, n, 2):
-        raise ValueError("warp_backward: g_out0 / grid shape")
-    flags = (BWD_FIXED_POINT if fixed_point else 0) | (BWD_TWO_KERNELS if two_kernels else 0) | \
-        (IO_BF16 if io_dtype == torch.bfloat16 else 0)
-    g_score = None
-    if score is not None:
-        score, transposed = _chk_score("warp_backward", score, N, n, F)
-        flags |= transposed
-        if need_score:
-            g_score = torch.empty_like(score)
-    if P_xy is not None:
-        P_xy = _chk("P_xy", P_xy, 2)
-    if P_hat_t is not None:
-        P_hat_t = _chk("P_hat_t", P_hat_t, 2)
-    C1 = H1 = W1 = 0
-    if in1 is not None:
-        in1, g_out1 = _chk("in1", in1, 4, io), _chk("g_out1", g_out1, 4, io)
-        _, C1, H1, W1 = in1.shape
-        if tuple(g_out1.shape) != (N, C1, Ho, Wo):
-            raise ValueError("warp_backward: g_out1 shape")
-    T = solve_T(inv_delta_C, ctrl) if score is not None else None      # (only dL/d score reads T)
-    g_in0 = torch.empty_like(in0) if need_in0 else None
-    g_in1 = torch.empty_like(in1) if (in1 is not None and need_in1) else None
-    g_ctrl = torch.empty((N, F, 2), device=in0.device, dtype=torch.float32)
-    g_grid = torch.empty((_query("tpspp_warp_bwd_workspace_floats", N, Ho, Wo),), device=in0.device, dtype=torch.float32)
-    _call("tpspp_warp_bwd", in0, g_out0, in0, C0, H0, W0, g_out1, in1, C1, H1, W1, grid, T, inv_delta_C, P_hat,
-          P_hat.shape[1], P_xy, score, P_hat_t, flags, N, F, Ho, Wo, g_in0, g_in1, g_ctrl, g_score, g_grid, g_grid.numel())
-    if g_score is not None and (flags & SCORE_TRANSPOSED):
+    m = _warp_bwd_marshal("warp_backward", True, g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1, g_out1,
+                          P_hat_t, fixed_point, two_kernels)
+    g_score = torch.empty_like(m.score) if (m.score is not None and need_score) else None
+    T = solve_T(m.inv_delta_C, m.ctrl) if m.score is not None else None      # (only dL/d score reads T)
+    g_in0 = torch.empty_like(m.in0) if need_in0 else None
+    g_in1 = torch.empty_like(m.in1) if (m.in1 is not None and need_in1) else None
+    g_ctrl = torch.empty((m.N, m.F, 2), device=m.in0.device, dtype=torch.float32)
+    g_grid = torch.empty((_query("tpspp_warp_bwd_workspace_floats", m.N, m.Ho, m.Wo),), device=m.in0.device, dtype=torch.float32)
+    _call("tpspp_warp_bwd", m.in0, *m.args(T, g_in0, g_in1, g_ctrl, g_score, g_grid, g_grid.numel()))
+    if g_score is not None and (m.flags & SCORE_TRANSPOSED):
         g_score = g_score.transpose(1, 2)                  # back to the logical (N, n, F) view
     return g_in0, g_in1, g_ctrl, g_score
+
+
+class WarpBwdRoute(collections.namedtuple("WarpBwdRoute", (
+        "family", "ppt", "nt", "f64", "bf16", "G", "cpt0", "cpt1", "chunks0", "chunks1", "slots", "params", "kmax", "table",
+        "transposed", "score", "gscore", "S"))):
+    """What `tpspp_warp_bwd_route` reports (include/tpspp.h), with the family as a word: "classic", "classic_bf16", "lds2",
+    "lds", "atomics", or "none" for an empty batch.  `str()` reads `lds2 ppt4 nt256 f64 G3 | params k36 tpspp T score_t
+    gscore S4`; `params_key` is the parameter kernel's instantiation (KMAX, TABLE, TRANSPOSED, SCORE, GSCORE) or None."""
+    __slots__ = ()
+    FAMILIES = ("classic", "classic_bf16", "lds2", "lds", "atomics")
+
+    @property
+    def params_key(self):
+        return (self.kmax, self.table, self.transposed, self.score, self.gscore) if self.params else None
+
+    def __str__(self):
+        io = " bf16" if self.bf16 else ""
+        acc = "f64" if self.f64 else "fix"
+        if self.family == "lds2":
+            s = f"lds2 ppt{self.ppt} nt{self.nt} {acc}{io} G{self.G}"
+        elif self.family == "lds":
+            s = f"lds cpt{self.cpt0},{self.cpt1} G{self.G}"
+        elif self.family == "atomics":
+            s = f"atomics chunks{self.chunks0}+{self.chunks1}"
+        else:
+            s = self.family
+        if self.params:
+            s += (f" | params k{self.kmax} {'tpspp' if self.table else 'classic'} {'T' if self.transposed else 'N'} "
+                  f"{('noscore', 'score', 'score_t')[self.score]}{' gscore' if self.gscore else ''} S{self.S}")
+        return s
+
+
+def warp_backward_route(g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy=None, score=None, in1=None,
+                        g_out1=None, P_hat_t=None, need_in0=True, need_in1=True, need_score=True, fixed_point=False,
+                        two_kernels=False, g_in0=None, g_in1=None):
+    """The kernels `warp_backward` would launch for these arguments (`tpspp_warp_bwd_route`), as a `WarpBwdRoute`.  A
+    host-side query that launches nothing: the tensors are read for their shapes, dtypes and addresses only (the library
+    looks at a pointer's alignment, never behind it), so CPU tensors will do.  `g_in0` / `g_in1`: tensors that stand for the
+    buffers dL/d input would be written to, for callers of the entry point that bring their own -- `warp_backward`
+    allocates them, 16-byte aligned, which is what is assumed without them.  Whatever `tpspp_warp_bwd` refuses raises the
+    same `TpsppError` here."""
+    m = _warp_bwd_marshal("warp_backward_route", False, g_out0, in0, grid, ctrl, inv_delta_C, P_hat, out_hw, P_xy, score, in1,
+                          g_out1, P_hat_t, fixed_point, two_kernels)
+    aligned = 64                                            # stands for a buffer warp_backward allocates itself
+    ws = _query("tpspp_warp_bwd_workspace_floats", m.N, m.Ho, m.Wo)
+    route = _int_array([0] * 18)
+    args = m.args(aligned if m.score is not None else None,
+                  (g_in0 if g_in0 is not None else aligned) if need_in0 else None,
+                  (g_in1 if g_in1 is not None else aligned) if (m.in1 is not None and need_in1) else None,
+                  aligned, aligned if (m.score is not None and need_score) else None, aligned, ws)
+    rc = _lib.lib().tpspp_warp_bwd_route(*_marshal(args), _vp(route), len(route))
+    _lib.check(rc, "tpspp_warp_bwd_route")
+    v = list(route)
+    return WarpBwdRoute("none" if v[0] < 0 else WarpBwdRoute.FAMILIES[v[0]], *v[1:])
 
 
 class _WarpFunction(torch.autograd.Function):
