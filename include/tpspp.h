@@ -54,7 +54,9 @@ extern "C" {
                                (still 12): the CRNN recogniser's entry points, declared in tpspp_crnn.h, tpspp_crnn_train.h and
                                   tpspp_crnn_bf16.h, are bound by name; they change nothing declared here;
                                (still 12): the classic rectifier's training kernels tpspp_bn_pool2x2_fwd / _bwd_reduce
-                                  (+ _workspace_floats) / _bwd_data and tpspp_global_avgpool_bwd, bound by name */
+                                  (+ _workspace_floats) / _bwd_data and tpspp_global_avgpool_bwd, bound by name;
+                               (still 12): the CRNN decoder's reduced-precision kernels tpspp_crnn_lstm_bf16_fwd and tpspp_mm_bf16,
+                                  bound by name */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -804,6 +806,51 @@ int tpspp_front_bf16_fwd(const void* outs0, const void* outs1, const void* x,
 int tpspp_token_gemm_bf16_fwd(const float* X, const void* w_arranged, const float* bias, const float* res,
                               void* out, int out_f32, int K, int Co, int M, int act, int split3,
                               tpspp_stream_t stream);
+
+/*
+ * CRNNDecoder's reduced-precision eval path (opt-in; tpspp_crnn_dec_bf16.hip): the LSTM input projection and the
+ * recurrence on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16).  Both take their weight W (rows, K) fp32 ARRANGED on the
+ * host side (ops.arrange_mfma16) into the lane order of the instruction's B operand:
+ *   [hi | lo][rows / 16][K / 32][64 lanes][8] bf16,  lane l of tile (ct, ks) holds W[16 ct + (l & 15)][32 ks + 8 (l >> 4) + j],
+ * j = 0..7: a lane's fragment is one 16-byte load, a wavefront's 1 KB contiguous.  Without split3 there is one slab,
+ * bf16(W), round to nearest even; with split3 two, hi = bf16(W) and lo = bf16(W - hi), the lo slab rows * K elements behind
+ * the hi slab.  16-byte aligned.
+ *
+ * Arithmetic of a product sum_k a[k] w[k] (a: the fp32 activation, w: the weight), both kernels:
+ *   split3 == 0: sum_k bf16(a[k]) * bf16(w[k]);
+ *   split3 == 1: with a_hi = bf16(a), a_lo = bf16(a - a_hi), per k step of 32 the three terms in tpspp_conv2d_bf16_fwd's
+ *                order  w_hi a_hi,  w_hi a_lo,  w_lo a_hi  (the lo lo term is dropped);
+ * every term one v_mfma_f32_16x16x32_bf16 with fp32 accumulation, k steps ascending: the order is fixed by the layout alone.
+ *
+ * tpspp_mm_bf16:   C[b][i][j] = sum_{k < K} A[b][i][k] * W[j][k] + bias[j]     b < batch, i < M, j < N
+ * A and C fp32, addressed through element strides as tpspp_mm_f32 takes them ((batch, row, k) and (batch, row, column), all
+ * >= 0); A is rounded -- split3: split -- while it is staged; B_arranged: W (N, K) arranged as above; bias (N) fp32, added
+ * to the finished fp32 sum, or NULL.  K % 32 == 0 and N % 128 == 0 (-22 otherwise); batch * M <= 2^30.  A is staged
+ * coalesced along whichever of its strides is 1: k (dense rows), the row, or the batch -- tokens (t, n, c) = feat[n, c, 0, t]
+ * of an NCHW map are (batch t: stride 1, row n, k c), and are then taken in the order t fastest.  A row's result does not
+ * depend on batch, M or its position.  Only the addressed elements of C are written.  batch, M or N of 0: success, nothing
+ * written.
+ *
+ * tpspp_crnn_lstm_bf16_fwd: tpspp_crnn_lstm_fwd (tpspp_crnn.h) with the recurrent product on the bf16 matrix cores.  xg, out,
+ * the directions, the gate order, the cell update and the activations are tpspp_crnn_lstm_fwd's, unchanged:
+ *   a_q = xg[t][n][d][q hidden + u] + sum_k h[n][k] w_hh[d][q hidden + u][k]     accumulated ON xg's value, k steps b = 0..7,
+ *   c = sigma(a_f) c + sigma(a_i) tanh(a_g),   h = sigma(a_o) tanh(c)            (two multiplies and one add, not fused)
+ * xg, c, the activations and the stored out are fp32.  The h that is stored is unrounded; the copy that feeds the next step
+ * is bf16(h), round to nearest even (split3: h_hi = bf16(h), h_lo = bf16(h - h_hi), split every step).
+ *   w_hh_arranged: [2 directions][hi | lo][64][8][64][8] bf16 -- each direction's (4 hidden, hidden) matrix arranged as above.
+ * An image's output depends on its own xg rows alone: not on N, on its position in the batch or on images_per_group, bit
+ * for bit.  Work division as tpspp_crnn_lstm_fwd: one workgroup of 512 threads per (direction, block of images_per_group
+ * images) for all T steps, planned by tpspp_crnn_lstm_plan; rows past the block stay zero; h in LDS as bf16 (two copies of
+ * 16 x 256, hi and lo with split3, swapped at the one barrier per step), c in registers, w_hh read again through L2 every
+ * step (512 KB per direction, 1 MB with split3).  No communication between workgroups, no spin-wait, no grid barrier:
+ * every loop is bounded by T.  hidden must be 256; T >= 1; T * N <= 2^30; images_per_group 0, 4, 8 or 16; split3 0 or 1
+ * (-22 otherwise, before any launch).  N == 0 returns 0 and launches nothing.
+ * replaces (opt-in): nn.LSTM(nIn, 256, bidirectional=True), layers/lstm_layer.py:10,14
+ */
+int tpspp_mm_bf16(int batch, int M, int N, int K, const float* A, const long long* a_strides, const void* B_arranged,
+                  float* C, const long long* c_strides, const float* bias, int split3, tpspp_stream_t stream);
+int tpspp_crnn_lstm_bf16_fwd(const float* xg, const void* w_hh_arranged, float* out, int T, int N, int hidden,
+                             int images_per_group, int split3, tpspp_stream_t stream);
 
 /*
  * down0 + down0_1 (or down1 + down1_1) of the ResNet45v2 wiring in one kernel (bf16 configuration):

@@ -5,6 +5,9 @@ Rows: the rectifier; the VGG; each BiLSTM layer split into its input projection 
 Then, for each precision mode (fp32 = compute_dtype None, the control; "bf16x3"; torch.bfloat16): the VGG alone, each of its
 seven convolutions (TFLOP/s) and four pools (GB/s) through the calls the VGG makes, and `simple_test` whole; and the
 agreement of each reduced mode's decisions with the exact fp32 kernels on 256 images (printed, not a bar).
+Then the decoder's own modes (`CRNNDecoder.set_compute_dtype`): the decoder whole in fp32 / bf16x3 / bf16, both input
+projections (tpspp_mm_bf16) and both recurrences (tpspp_crnn_lstm_bf16_fwd) in the two reduced modes -- their fp32
+counterparts are the rows above, in the same run --, and `simple_test` with VGG and decoder in the same mode.
 Two comparison columns, neither of them a pass bar:
   * `torch.nn.LSTM` on the same GPU against projection + recurrence of the same layer (the library fuses the two, so the
     recurrence alone has no counterpart);
@@ -184,6 +187,36 @@ def main():
     }
     rows.update(mode_rows)
 
+    # ---- the decoder's precision modes: both projections, both recurrences, the decoder whole, and
+    # simple_test with VGG and decoder in the same mode; the fp32 rows above are their control in the same run --------------
+    def with_decoder(mode, f, whole=False):
+        """f() with the decoder (whole: VGG and decoder, through the model's public switch) in `mode`; defaults afterwards."""
+        def call():
+            if whole:
+                m.set_compute_dtype(mode, decoder=mode)
+            else:
+                dec.set_compute_dtype(mode)
+            try:
+                return f()
+            finally:
+                m.set_compute_dtype(None, decoder=None)
+        return call
+
+    for label, mode in MODES:
+        rows[f"decoder (whole), {label}"] = (with_decoder(mode, lambda: dec(rot(feats), None, None, None, train_mode=False)), False)
+        if mode is None:
+            continue
+        b0, b1 = l0._hip_weights_bf16(mode == "bf16x3"), l1._hip_weights_bf16(mode == "bf16x3")
+        rows[f"lstm0 input projection 512 -> 2x1024, {label}"] = (
+            lambda b0=b0: ops.linear_bf16_fwd(rot(feats), (T, N, sw, sn, sc), b0[0]), False)
+        rows[f"lstm0 recurrence, {label}"] = (lambda b0=b0: ops.crnn_lstm_bf16(rot(xg0), b0[1]), False)
+        rows[f"lstm0 recurrence, {label}, 16 images per workgroup"] = (lambda b0=b0: ops.crnn_lstm_bf16(rot(xg0), b0[1], 16), False)
+        rows[f"lstm1 input projection 256 -> 2x1024, {label}"] = (
+            lambda b1=b1: ops.linear_bf16_fwd(rot(e0), (T, N, N * H, H, 1), b1[0]), False)
+        rows[f"lstm1 recurrence, {label}"] = (lambda b1=b1: ops.crnn_lstm_bf16(rot(xg1), b1[1]), False)
+        rows[f"simple_test (whole model), VGG and decoder {label}"] = (
+            with_decoder(mode, lambda: m.simple_test(rot(imgs), metas), True), True)
+
     def region(f, host):
         e0_, e1_ = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -230,6 +263,9 @@ def main():
                   tail_hip_over_torch=med["VGG + decoder + decode, HIP"] / med["VGG + decoder + decode, PyTorch composition"],
                   images_per_s=N / med["simple_test (whole model)"] * 1e3,
                   images_per_s_by_mode={label: N / med[f"simple_test (whole model), {label}"] * 1e3 for label, _ in MODES},
+                  decoder_ms_by_mode={label: med[f"decoder (whole), {label}"] for label, _ in MODES},
+                  images_per_s_by_mode_with_decoder={
+                      label: N / med[f"simple_test (whole model), VGG and decoder {label}"] * 1e3 for label, _ in MODES[1:]},
                   agreement_with_fp32_kernels=agreement)
     for label, ag in agreement.items():
         print(f"{label} against the exact fp32 kernels, {ag['images']} images (random-init weights): greedy strings equal "

@@ -20,8 +20,11 @@ the NRTR backbone, and keeps its meaning for the preprocessor (its localisation 
 exact fp32 path.  In a reduced mode the seven convolutions run on the bf16 matrix cores (`ops.conv2d_bf16`: plain bf16
 operands and maps, or the three-term split on fp32 maps), the feature maps stay in the blocked layout from conv0's output
 to conv6's input, and the four pools run on it (include/tpspp_crnn_bf16.h); the features leave as fp32.  The decoder
-stays exact fp32 in every mode -- the LSTM recurrence, its input projections, the embeddings and the CTC decode --, as
-NRTR's per-step projections do.
+stays exact fp32 unless it is asked: `set_compute_dtype(mode, decoder=mode)` of the recogniser, or
+`CRNNDecoder.set_compute_dtype(mode)`, moves the two LSTM input projections and the two recurrences of the eval path onto
+the bf16 matrix cores (`tpspp_mm_bf16`, `tpspp_crnn_lstm_bf16_fwd`, include/tpspp.h: operands rounded or split, fp32
+accumulation, fp32 cell state and outputs).  The embeddings and the CTC decode stay exact fp32 in every mode, as NRTR's
+per-step projections do.
 """
 import math
 
@@ -187,6 +190,7 @@ class BidirectionalLSTM(nn.Module):
 
     def __init__(self, nIn, nHidden, nOut):
         super().__init__()
+        self.lstm_dtype = None                      # the HIP path's arithmetic: `CRNNDecoder.set_compute_dtype` sets it
         self.rnn = nn.LSTM(nIn, nHidden, bidirectional=True)
         self.embedding = nn.Linear(nHidden * 2, nOut)
 
@@ -198,12 +202,28 @@ class BidirectionalLSTM(nn.Module):
             torch.cat([r.bias_ih_l0 + r.bias_hh_l0, r.bias_ih_l0_reverse + r.bias_hh_l0_reverse]).detach().float().contiguous(),
             torch.stack([r.weight_hh_l0, r.weight_hh_l0_reverse]).detach().float().contiguous()))
 
-    def recurrent_hip(self, x, desc, T, N, images_per_group=0):
+    def _hip_weights_bf16(self, x3):
+        """`_hip_weights` for the bf16 matrix cores: (w_ih of both directions with b_ih + b_hh, w_hh of both), each an
+        `ops.MfmaWeight` -- rounded to bf16 or, `x3`, split into the hi and lo slabs of the three-term product.  Keys of
+        its own: the fp32 set stays prepared next to it."""
+        r = self.rnn
+
+        def build():
+            w_ih, b, w_hh = self._hip_weights()
+            return ops.arrange_mfma16(w_ih, b, x3=x3), ops.arrange_mfma16(w_hh, x3=x3)
+        return prepared(self, "lstm_bf16x3" if x3 else "lstm_bf16", [r], build)
+
+    def recurrent_hip(self, x, desc, T, N, images_per_group=0, mode=None):
         """The LSTM of the token operand x (`desc` = (batch = T, rows = N, batch stride, row stride, k stride), as
         `ops.linear_fwd` takes it) -> (T, N, 2 H): one product for the input pre-activations of all tokens and both
-        directions, then the recurrence kernel."""
+        directions, then the recurrence kernel.  `mode`: None the exact fp32 kernels; "bf16x3" / torch.bfloat16 both
+        products on the bf16 matrix cores (`tpspp_mm_bf16`, `tpspp_crnn_lstm_bf16_fwd`)."""
         if self.rnn.hidden_size != ops.CRNN_HIDDEN or self.rnn.num_layers != 1:
             raise ValueError("BidirectionalLSTM: the HIP recurrence serves one layer of 256 hidden units")
+        if mode is not None:
+            w_ih, w_hh = self._hip_weights_bf16(mode == "bf16x3")
+            xg = ops.linear_bf16_fwd(x, desc, w_ih)
+            return ops.crnn_lstm_bf16(xg.view(T, N, 2, 4 * ops.CRNN_HIDDEN), w_hh, images_per_group)
         w_ih, b, w_hh = self._hip_weights()
         xg = ops.linear_fwd(x, desc, w_ih, b)                                  # (T N, 2 * 4 H)
         return ops.crnn_lstm(xg.view(T, N, 2, 4 * ops.CRNN_HIDDEN), w_hh, images_per_group)
@@ -214,7 +234,7 @@ class BidirectionalLSTM(nn.Module):
         ops.require_gpu(input, "BidirectionalLSTM")
         x = input.float().contiguous()
         T, N, K = x.shape
-        rec = self.recurrent_hip(x, (T, N, N * K, K, 1), T, N)
+        rec = self.recurrent_hip(x, (T, N, N * K, K, 1), T, N, mode=self.lstm_dtype)
         emb = self.embedding
         return ops.linear_fwd(rec, ops._dense(T * N, rec.shape[2]), emb.weight.detach(), emb.bias.detach()).view(T, N, -1)
 
@@ -236,8 +256,24 @@ class CRNNDecoder(TrainBackendMixin, nn.Module):
         path are not affected."""
         return super().set_train_backend(mode)
 
+    def set_compute_dtype(self, mode):
+        """Opt-in precision of the eval fast path (`_forward_hip`, rnn_flag=True; not in the reference).  None (the
+        default): the exact fp32 kernels.  "bf16x3" / torch.bfloat16: both LSTM layers' input projections and recurrences
+        on the bf16 matrix cores (`tpspp_mm_bf16`, `tpspp_crnn_lstm_bf16_fwd`: three-term split, or plain bf16 operands
+        with fp32 accumulation, fp32 cell state and fp32 outputs); the two embeddings and the CTC decode stay exact fp32.
+        Kept in `lstm_dtype` (the recogniser's own switch does not reach it unless asked to: `decoder=`).  `.train()`, an
+        input that requires grad, a host tensor, rnn_flag=False and `set_train_backend("hip")` are not affected."""
+        if not (mode is None or mode == "bf16x3" or mode == torch.bfloat16):
+            raise ValueError('set_compute_dtype: None, "bf16x3" or torch.bfloat16')
+        self.lstm_dtype = mode
+        if self.rnn_flag:
+            for layer in self.decoder:
+                layer.lstm_dtype = mode
+        return self
+
     def __init__(self, in_channels=None, num_classes=None, rnn_flag=False, init_cfg=None, **kwargs):
         super().__init__()
+        self.lstm_dtype = None                      # None: exact fp32; "bf16x3" / torch.bfloat16: `set_compute_dtype`
         self.init_cfg = init_cfg
         self.num_classes = num_classes
         self.rnn_flag = rnn_flag
@@ -263,7 +299,9 @@ class CRNNDecoder(TrainBackendMixin, nn.Module):
 
     def _forward_hip(self, feat):
         """No layout pass: the first input projection reads the (W, N, C) tokens out of the NCHW feature map through
-        tpspp_mm_f32's strides (a sliced map included), the last embedding writes (N, W, C) through them."""
+        tpspp_mm_f32's strides (a sliced map included), the last embedding writes (N, W, C) through them.  With a reduced
+        mode set (`set_compute_dtype`) the two input projections and the two recurrences run on the bf16 matrix cores
+        (`tpspp_mm_bf16` reads the same strides); the embeddings stay on tpspp_mm_f32."""
         N, C, H, W = feat.shape
         if H != 1:
             raise ValueError(f"CRNNDecoder: feature height must be 1, got {H}")
@@ -274,12 +312,14 @@ class CRNNDecoder(TrainBackendMixin, nn.Module):
             y = ops.conv2d([feat.contiguous()], cw, 1, False)          # (N, num_classes, 1, W)
             return y.view(N, -1, W).permute(0, 2, 1).contiguous()
         l0, l1 = self.decoder[0], self.decoder[1]
+        if N == 0 and l0.lstm_dtype is not None:    # an empty batch has no device pointer to hand over
+            return torch.empty((0, W, l1.embedding.weight.shape[0]), device=feat.device, dtype=torch.float32)
         sn, sc, _, sw = feat.stride()
-        rec = l0.recurrent_hip(feat, (W, N, sw, sn, sc), W, N)         # token (t, n, c) = feat[n, c, 0, t]
+        rec = l0.recurrent_hip(feat, (W, N, sw, sn, sc), W, N, mode=l0.lstm_dtype)     # token (t, n, c) = feat[n, c, 0, t]
         e0 = l0.embedding
         x = ops.linear_fwd(rec, ops._dense(W * N, rec.shape[2]), e0.weight.detach(), e0.bias.detach())     # (W N, 256)
         K = x.shape[1]
-        rec = l1.recurrent_hip(x, (W, N, N * K, K, 1), W, N)
+        rec = l1.recurrent_hip(x, (W, N, N * K, K, 1), W, N, mode=l1.lstm_dtype)
         e1 = l1.embedding
         O, K = e1.weight.shape
         out = torch.empty((N, W, O), device=feat.device, dtype=torch.float32)

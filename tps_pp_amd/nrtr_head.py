@@ -679,15 +679,26 @@ class EncodeDecodeRecognizer(nn.Module):
         self.loss = None if loss is None else build_loss(self.loss_cfg)
         self.train_cfg, self.test_cfg, self.max_seq_len = train_cfg, test_cfg, max_seq_len
 
-    def set_compute_dtype(self, mode):
+    _UNSET = object()
+
+    def set_compute_dtype(self, mode, decoder=_UNSET):
         """One switch for the precision of the wide matrix products of every stage (not in the reference: its modules
         are fp32).  None: the exact fp32 kernels; "bf16x3": fp32 tensors, three-term bf16 split (still within the
         1e-4 bar); torch.bfloat16: bf16 operands / feature maps / encoder keys and values (control points, TPS solve,
         grid, LayerNorms, softmaxes and the decoder's per-step projections stay fp32 in every mode).  For `CRNNNet` the
-        backbone is `VeryDeepVgg`, whose convolutions and pools follow the mode; its `CRNNDecoder` (LSTM recurrence, input
-        projections, embeddings) and the CTC decode stay exact fp32 in every mode."""
+        backbone is `VeryDeepVgg`, whose convolutions and pools follow the mode; its `CRNNDecoder` stays exact fp32
+        unless `decoder` is given: `decoder=` None | "bf16x3" | torch.bfloat16 is handed to the decoder's own
+        `set_compute_dtype` (`CRNNDecoder`: the LSTM input projections and recurrences of the eval path on the bf16
+        matrix cores); a decoder without that switch raises.  The embeddings and the CTC decode stay exact fp32 in every
+        mode.  A call that fails changes nothing."""
         if mode not in (None, "bf16x3", torch.bfloat16):
             raise ValueError('set_compute_dtype: None, "bf16x3" or torch.bfloat16')
+        if decoder is not self._UNSET:
+            if decoder not in (None, "bf16x3", torch.bfloat16):
+                raise ValueError('set_compute_dtype: decoder must be None, "bf16x3" or torch.bfloat16')
+            if not callable(getattr(self.decoder, "set_compute_dtype", None)):
+                raise ValueError(f"set_compute_dtype: {type(self.decoder).__name__} has no precision switch of its own")
+            self.decoder.set_compute_dtype(decoder)
         self.backbone.compute_dtype = mode
         if self.tpsnet is not None:          # on bf16 activations TPS_PP follows its input; "bf16x3" must be told
             self.tpsnet.compute_dtype = mode if mode == "bf16x3" else None

@@ -3197,6 +3197,85 @@ def crnn_lstm(xg, w_hh, images_per_group=0):
     return out
 
 
+class MfmaWeight:
+    """A (rows, K) weight -- or a stack (n, rows, K) of them -- arranged for the B operand of v_mfma_f32_16x16x32_bf16
+    (`arrange_mfma16`): `arranged` bf16 ([n], [hi | lo], rows / 16, K / 32, 64, 8), fp32 `bias` | None."""
+
+    def __init__(self, arranged, bias, rows, k, x3):
+        self.arranged, self.bias, self.rows, self.k, self.x3 = arranged, bias, rows, k, x3
+
+
+def arrange_mfma16(w, bias=None, x3=False):
+    """fp32 (rows, K) or (n, rows, K), rows % 16 == 0 and K % 32 == 0 -> MfmaWeight (include/tpspp.h, tpspp_mm_bf16): per
+    matrix [hi | lo][rows / 16][K / 32][lane][8] bf16 with lane l holding W[16 ct + (l & 15)][32 ks + 8 (l >> 4) + j];
+    one slab bf16(w), or, x3, the two of `_hi_lo`."""
+    w = w.detach().float()
+    if w.dim() not in (2, 3) or w.shape[-2] % 16 or w.shape[-1] % 32:
+        raise ValueError(f"arrange_mfma16: (rows, K) or (n, rows, K) with rows % 16 == 0 and K % 32 == 0, got {tuple(w.shape)}")
+    rows, K = w.shape[-2:]
+    st = torch.stack(_hi_lo(w) if x3 else (w.to(torch.bfloat16),), dim=-3)          # (..., s, rows, K)
+    st = st.reshape(st.shape[:-2] + (rows // 16, 16, K // 32, 4, 8))                # (..., s, ct, col, ks, quad, j)
+    nd = st.dim()
+    st = st.permute(*range(nd - 5), nd - 5, nd - 3, nd - 2, nd - 4, nd - 1)         # (..., s, ct, ks, quad, col, j)
+    arranged = st.reshape(st.shape[:-3] + (64, 8)).contiguous()
+    return MfmaWeight(arranged, None if bias is None else bias.detach().float().contiguous(), rows, K, bool(x3))
+
+
+def dearrange_mfma16(mw):
+    """The inverse of `arrange_mfma16`: the bf16 slabs as ([n], [hi | lo], rows, K) (what the tests compare with `_hi_lo`)."""
+    a = mw.arranged
+    lead = a.shape[:-4]
+    a = a.reshape(lead + (mw.rows // 16, mw.k // 32, 4, 16, 8))                     # (..., ct, ks, quad, col, j)
+    nd = a.dim()
+    a = a.permute(*range(nd - 5), nd - 5, nd - 2, nd - 4, nd - 3, nd - 1)           # (..., ct, col, ks, quad, j)
+    return a.reshape(lead + (mw.rows, mw.k))
+
+
+def mm_bf16(A, a_strides, mw, C, c_strides, batch, M):
+    """`tpspp_mm_bf16`: C[b][i][j] = sum_k A[b][i][k] W[j][k] + bias[j] on the bf16 matrix cores, A rounded to bf16 or
+    (mw.x3) split as it is staged; strides in elements, (batch, row, k) for A and (batch, row, column) for C."""
+    for name, t in (("mm_bf16 A", A), ("mm_bf16 C", C)):        # (strided views: taken as they are, never copied)
+        _chk_gpu(name, t)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 5:
+        raise TypeError("mm_bf16: the weight must be an MfmaWeight of one (rows, K) matrix (arrange_mfma16)")
+    _chk_gpu("mm_bf16 weight", mw.arranged)
+    if mw.arranged.device != C.device or A.device != C.device or (mw.bias is not None and mw.bias.device != C.device):
+        raise ValueError("mm_bf16: operands on different devices")
+    if batch * M == 0:
+        return C
+    sa, sc = _i64(*a_strides), _i64(*c_strides)
+    _call("tpspp_mm_bf16", C, batch, M, mw.rows, mw.k, A, _vp(sa), mw.arranged, C, _vp(sc), mw.bias, int(mw.x3))
+    return C
+
+
+def linear_bf16_fwd(x, desc, mw):
+    """`linear_fwd` on `tpspp_mm_bf16`: y (rows, O) dense fp32 = x W^T + b for the token operand x described by `desc`."""
+    nb, Mi, sb, si, sk = desc
+    y = torch.empty((nb * Mi, mw.rows), device=mw.arranged.device, dtype=torch.float32)
+    return mm_bf16(x, (sb, si, sk), mw, y, (Mi * mw.rows, mw.rows, 1), nb, Mi)
+
+
+def crnn_lstm_bf16(xg, mw, images_per_group=0):
+    """`crnn_lstm` with the recurrent product on the bf16 matrix cores (`tpspp_crnn_lstm_bf16_fwd`): xg (T, N, 2, 1024)
+    fp32, mw = `arrange_mfma16(w_hh (2, 1024, 256), x3=...)` -> (T, N, 512) fp32; h is rounded (x3: split) per step."""
+    xg = _chk("crnn_lstm_bf16 xg", xg, 4)
+    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 6:
+        raise TypeError("crnn_lstm_bf16: the weight must be an MfmaWeight of the (2, 1024, 256) stack (arrange_mfma16)")
+    _chk_gpu("crnn_lstm_bf16 w_hh", mw.arranged)
+    T, N = xg.shape[0], xg.shape[1]
+    if tuple(xg.shape[2:]) != (2, 4 * CRNN_HIDDEN) or (mw.arranged.shape[0], mw.rows, mw.k) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) \
+            or mw.arranged.device != xg.device:
+        raise ValueError(f"crnn_lstm_bf16: xg (T, N, 2, 1024) and w_hh (2, 1024, 256) arranged, on one device, got "
+                         f"{tuple(xg.shape)}, {tuple(mw.arranged.shape)}")
+    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    if N == 0:
+        return out
+    _call("tpspp_crnn_lstm_bf16_fwd", xg, xg, mw.arranged, out, T, N, CRNN_HIDDEN, int(images_per_group), int(mw.x3))
+    return out
+
+
 def crnn_ctc_decode_device(logits, decode_len, blank=0):
     """`tpspp_crnn_ctc_decode` into fresh device tensors: (idx (N, T) int32, -1 where the scan of ctc.py:119-129 drops the
     position; score (N, T) float32, 0 there).  decode_len: (N) int32 on the logits' device."""
