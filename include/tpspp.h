@@ -56,7 +56,9 @@ extern "C" {
                                (still 12): the classic rectifier's training kernels tpspp_bn_pool2x2_fwd / _bwd_reduce
                                   (+ _workspace_floats) / _bwd_data and tpspp_global_avgpool_bwd, bound by name;
                                (still 12): the CRNN decoder's reduced-precision kernels tpspp_crnn_lstm_bf16_fwd and tpspp_mm_bf16,
-                                  bound by name */
+                                  bound by name;
+                               (still 12): their training counterparts tpspp_crnn_lstm_bf16_train_fwd, tpspp_crnn_lstm_bf16_bwd and
+                                  tpspp_linear_bwd_weight_bf16 (+ _workspace_floats), bound by name */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -851,6 +853,52 @@ int tpspp_mm_bf16(int batch, int M, int N, int K, const float* A, const long lon
                   float* C, const long long* c_strides, const float* bias, int split3, tpspp_stream_t stream);
 int tpspp_crnn_lstm_bf16_fwd(const float* xg, const void* w_hh_arranged, float* out, int T, int N, int hidden,
                              int images_per_group, int split3, tpspp_stream_t stream);
+
+/*
+ * CRNNDecoder's training graph on the bf16 matrix cores (opt-in: CRNNDecoder.set_train_compute_dtype("bf16x3");
+ * tpspp_crnn_dec_bf16.hip).  The arranged weights, split3 and the arithmetic of a product are those stated above
+ * tpspp_mm_bf16; the input projection and dx of a layer run on tpspp_mm_bf16 itself.  No atomics; every loop is bounded by T;
+ * no communication between workgroups, no spin-wait, no grid barrier.  Every argument is checked before any launch.
+ *
+ * tpspp_crnn_lstm_bf16_train_fwd: tpspp_crnn_lstm_bf16_fwd -- one kernel body with a compile-time switch, `out` has the same
+ * bits -- that also stores, fp32, what the backward reads, laid out as tpspp_crnn_lstm_train_fwd (tpspp_crnn_train.h) stores
+ * it: gates (T, N, 2, 4 hidden) after their activations, cell (T, N, 2, hidden).  Limits as tpspp_crnn_lstm_bf16_fwd.
+ *
+ * tpspp_crnn_lstm_bf16_bwd: tpspp_crnn_lstm_bwd's recursion (tpspp_crnn_train.h), unchanged: the `+ 0.0f`, tanh from the
+ * stored cell, dc and dh_rec in registers, d_xg the unrounded fp32 da.  The one change is the product
+ *   dh_rec[n][k] = sum_j da[n][j] w_hh[d][j][k]
+ * on v_mfma_f32_16x16x32_bf16: da is rounded (split3: split into hi / lo) as it is written to LDS, the B operand is
+ *   w_hh_t_arranged: [2 directions][hi | lo][16][32][64][8] bf16 -- each direction's TRANSPOSE (hidden rows, K = 4 hidden)
+ *   arranged as above (ops.arrange_mfma16(w_hh.transpose(1, 2))),
+ * per k step of 32 the terms w_hi da_hi, w_hi da_lo, w_lo da_hi, fp32 accumulation from 0, k steps ascending, one chain.
+ * Work division and lane <-> (image, unit) map of tpspp_crnn_lstm_bwd: one workgroup of 512 threads per (direction, block of
+ * 4, 8 or 16 images); a wavefront's two 16 x 16 tiles are the dh_rec of its own pairs.  An image's d_xg does not depend on
+ * N, its position or images_per_group, bit for bit; d_out == 0 gives d_xg == +0.  da in LDS: [hi | lo] x 16 x (1024 + 8)
+ * bf16, 66048 bytes with split3 (one workgroup per CU), 33024 without.  There is no direction-major copy.
+ * hidden must be 256; T >= 1; T * N <= 2^30; images_per_group 0, 4, 8 or 16; split3 0 or 1.  N == 0 launches nothing.
+ *
+ * tpspp_linear_bwd_weight_bf16:   dW[i][j] = sum_{b < batch, r < M} DY[b][r][i] * X[b][r][j]     i < O, j < K
+ * DY and X fp32, read through (batch, row, column) element strides >= 0 (the NCHW token view and shifted views included);
+ * dW dense (O, K) fp32, every element written.  Both operands are rounded -- split3: split -- while they are staged into
+ * LDS; the rows (b, r) in the order b M + r are the instruction's k: per k step of 32 rows the terms dy_hi x_hi, dy_hi x_lo,
+ * dy_lo x_hi, fp32 accumulation from 0, k steps ascending; rows past batch * M count as zeros.  An operand whose column
+ * stride is 1 is staged coalesced along its columns, any other along its rows; both are transposed in LDS into the
+ * fragment order.  One workgroup of 256 threads per 128 x 128 tile of dW and slice of the rows.  The split over rows is
+ * fixed by (batch, M, O, K) alone:  R = batch M, steps = ceil(R / 32), tiles = (O / 128)(K / 128),
+ *   per = ceil(steps / max(1, 512 / tiles)),  slices = ceil(steps / per),  workspace = slices > 1 ? slices O K : 0 floats;
+ * with more than one slice each writes its partial to ws and a second launch adds them in ascending order: the result is
+ * bitwise reproducible from call to call and from stream to stream, and depends on batch and M through R alone.
+ * O % 128 == 0 and K % 128 == 0 (-22 otherwise); batch, M >= 0, R <= 2^30.  R == 0: dW is all +0, no workspace.
+ * replaces (opt-in): the autograd of nn.LSTM(nIn, 256, bidirectional=True), layers/lstm_layer.py:10,14
+ */
+int tpspp_crnn_lstm_bf16_train_fwd(const float* xg, const void* w_hh_arranged, float* out, float* gates, float* cell, int T,
+                                   int N, int hidden, int images_per_group, int split3, tpspp_stream_t stream);
+int tpspp_crnn_lstm_bf16_bwd(const float* d_out, const float* gates, const float* cell, const void* w_hh_t_arranged,
+                             float* d_xg, int T, int N, int hidden, int images_per_group, int split3, tpspp_stream_t stream);
+size_t tpspp_linear_bwd_weight_bf16_workspace_floats(int batch, int M, int O, int K);
+int tpspp_linear_bwd_weight_bf16(int batch, int M, int O, int K, const float* DY, const long long* dy_strides, const float* X,
+                                 const long long* x_strides, float* dW, float* ws, size_t ws_floats, int split3,
+                                 tpspp_stream_t stream);
 
 /*
  * down0 + down0_1 (or down1 + down1_1) of the ResNet45v2 wiring in one kernel (bf16 configuration):

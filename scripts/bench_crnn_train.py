@@ -7,6 +7,9 @@ recurrence of the first layer (it stores gates and cell states) next to the infe
 under the planner and under each group size, d w_hh both ways (tpspp_linear_bwd_weight on the direction-major copy of d_xg,
 which the product uses, and tpspp_mm_f32 over shifted views of d_xg itself), the first layer's input projection with its
 weight and data gradients and the per-call weight preparation, and the CTC loss forward and backward next to PyTorch's.
+The "hip" step a second time with `set_train_compute_dtype("bf16x3")`, and per layer (lstm0: K = 512, tokens read from the
+NCHW map; lstm1: K = 256, dense tokens) in fp32 and in bf16x3: the projection forward, the recurrence forward with stored
+gates, the recurrence backward, d w_ih, d w_hh, dx and the per-call arrangement of the weights.
 
 Every row: `reps` calls between two device events per region, the variants interleaved region by region, inputs rotated
 over `--buffers` copies so that no call finds its own input in cache, medians over the regions with min and max
@@ -49,8 +52,9 @@ def main():
     decs["torch"] = build_decoder(dict(type="CRNNDecoder", in_channels=512, num_classes=conv.num_classes(),
                                        rnn_flag=True)).to(dev).train()
     decs["hip"] = copy.deepcopy(decs["torch"]).set_train_backend("hip")
+    decs["hip bf16x3"] = copy.deepcopy(decs["hip"]).set_train_compute_dtype("bf16x3")
     for k in decs:
-        losses[k] = CTCLoss().set_train_backend(k)
+        losses[k] = CTCLoss().set_train_backend(k.split()[0])
     td = conv.str2tensor([WORDS[i % len(WORDS)] for i in range(N)])
     metas = [{} for _ in range(N)]
     feats = [torch.randn((N, 512, 1, T), device=dev).relu_() for _ in range(B)]
@@ -131,8 +135,73 @@ def main():
                 torch.stack([ops.transpose2d(r.weight_hh_l0.detach()), ops.transpose2d(r.weight_hh_l0_reverse.detach())]))
 
     nograd = lambda f: (lambda: _no_grad(torch, f))  # noqa: E731
+
+    # the five wide products of each layer, fp32 and bf16x3, on saved operands of that layer
+    G = 4 * H
+    layer_rows = {}
+    for li, K in ((0, 512), (1, 256)):
+        layer = decs["hip"].decoder[li]
+        with torch.no_grad():
+            lw_ih, lb, lw_hh = layer._hip_weights()
+            lw_hh_t = lw_hh.transpose(1, 2).contiguous()
+            xs = feats if li == 0 else [torch.randn((T, N, K), device=dev) for _ in range(B)]
+            desc = desc0 if li == 0 else (T, N, N * K, K, 1)
+            a_ih, a_hh = ops.arrange_mfma16(lw_ih, lb, x3=True), ops.arrange_mfma16(lw_hh, x3=True)
+            a_hh_t, a_ih_t = ops.arrange_mfma16(lw_hh.transpose(1, 2), x3=True), ops.arrange_mfma16(lw_ih.t(), x3=True)
+            lxg = [ops.linear_fwd(x, desc, lw_ih, lb).view(T, N, 2, G) for x in xs]
+            lsv = [ops.crnn_lstm_train_fwd(x, lw_hh) for x in lxg]
+            ldx = [ops.crnn_lstm_bwd(d_out[i], lsv[i][1], lsv[i][2], lw_hh_t, direction_major=True) for i in range(B)]
+            dxo = torch.empty_like(xs[0])
+        sdx = (dxo.stride(3), dxo.stride(0), dxo.stride(1)) if li == 0 else (N * K, K, 1)
+        sd, sx = (N * 2 * G, 2 * G, 1), (N * 2 * H, 2 * H, 1)
+
+        def parts(xs=xs, desc=desc, K=K, lw_ih=lw_ih, lb=lb, lw_hh=lw_hh, lw_hh_t=lw_hh_t, a_ih=a_ih, a_hh=a_hh, a_hh_t=a_hh_t,
+                  a_ih_t=a_ih_t, lxg=lxg, lsv=lsv, ldx=ldx, dxo=dxo, sdx=sdx, layer=layer):
+            def sv():
+                i = rot(range(B))
+                return d_out[i], lsv[i][1], lsv[i][2]
+
+            def dwhh_bf16():
+                i = rot(range(B))
+                d, out = ldx[i][0], lsv[i][0]
+                return (ops.linear_bwd_weight_bf16(d[1:, :, 0], sd, out[:-1, :, :H], sx, T - 1, N, G, H),
+                        ops.linear_bwd_weight_bf16(d[:-1, :, 1], sd, out[1:, :, H:], sx, T - 1, N, G, H))
+
+            def arrange():
+                r = layer.rnn
+                w_ih_ = torch.cat([r.weight_ih_l0, r.weight_ih_l0_reverse]).float().contiguous()
+                b_ = torch.cat([r.bias_ih_l0 + r.bias_hh_l0, r.bias_ih_l0_reverse + r.bias_hh_l0_reverse]).float().contiguous()
+                w_hh_ = torch.stack([r.weight_hh_l0, r.weight_hh_l0_reverse]).float().contiguous()
+                return (ops.arrange_mfma16(w_ih_, b_, x3=True), ops.arrange_mfma16(w_hh_, x3=True),
+                        ops.arrange_mfma16(w_hh_.transpose(1, 2), x3=True), ops.arrange_mfma16(w_ih_.t(), x3=True))
+
+            def pair(f):
+                """f(d_xg of a saved step, that step's layer input)."""
+                i = rot(range(B))
+                return f(ldx[i], xs[i], lsv[i][0])
+            return {
+                "projection forward, fp32": lambda: ops.linear_fwd(rot(xs), desc, lw_ih, lb),
+                "projection forward, bf16x3": lambda: ops.linear_bf16_fwd(rot(xs), desc, a_ih),
+                "recurrence forward with stored gates, fp32": lambda: ops.crnn_lstm_train_fwd(rot(lxg), lw_hh),
+                "recurrence forward with stored gates, bf16x3": lambda: ops.crnn_lstm_bf16_train_fwd(rot(lxg), a_hh),
+                "recurrence backward, fp32": lambda: ops.crnn_lstm_bwd(*sv(), lw_hh_t, 0, True),
+                "recurrence backward, bf16x3": lambda: ops.crnn_lstm_bf16_bwd(*sv(), a_hh_t),
+                "d w_ih, fp32 (with d bias)": lambda: pair(lambda d, x, o: ops.linear_bwd_weight(d[0].view(T * N, 2 * G), x, desc, 2 * G, K)),
+                "d w_ih, bf16x3": lambda: pair(lambda d, x, o: ops.linear_bwd_weight_bf16(d[0], sd, x, desc[2:], T, N, 2 * G, K)),
+                "d bias alone, fp32 (the bf16x3 step's)": lambda: pair(
+                    lambda d, x, o: ops.linear_bwd_weight(d[0].view(T * N, 2 * G), x, desc, 2 * G, K, False, True)),
+                "d w_hh, fp32": lambda: pair(lambda d, x, o: ops.crnn_lstm_bwd_w_hh(d[1], o)),
+                "d w_hh, bf16x3 (shifted views)": dwhh_bf16,
+                "dx, fp32": lambda: ops.linear_bwd_data(rot(ldx)[0].view(T * N, 2 * G), lw_ih, dxo, desc),
+                "dx, bf16x3": lambda: ops.mm_bf16(rot(ldx)[0], sd, a_ih_t, dxo, sdx, T, N),
+                "weights per call, bf16x3: four arrangements": arrange,
+            }
+        for name, f in parts().items():
+            layer_rows[f"lstm{li} {name}"] = nograd(f)
+
     rows = {
         "decoder + loss, forward + backward, hip": lambda: step("hip"),
+        "decoder + loss, forward + backward, hip bf16x3": lambda: step("hip bf16x3"),
         "decoder + loss, forward + backward, torch": lambda: step("torch"),
         "lstm0 recurrence forward (inference kernel)": nograd(lambda: ops.crnn_lstm(rot(xg), w_hh)),
         "lstm0 recurrence forward, saving gates and cell": nograd(lambda: ops.crnn_lstm_train_fwd(rot(xg), w_hh)),
@@ -152,6 +221,7 @@ def main():
         "CTC loss backward, hip": nograd(ctc_bwd),
         "CTC loss forward + backward, torch": ctc_torch,
     }
+    rows.update(layer_rows)
 
     def region(f):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -182,10 +252,13 @@ def main():
                   table=table,
                   step_hip_over_torch=med["decoder + loss, forward + backward, hip"] /
                   med["decoder + loss, forward + backward, torch"],
+                  step_hip_bf16x3_over_torch=med["decoder + loss, forward + backward, hip bf16x3"] /
+                  med["decoder + loss, forward + backward, torch"],
                   recurrence_bwd_over_fwd=med["lstm0 recurrence backward"] / med["lstm0 recurrence forward (inference kernel)"],
                   ctc_hip_over_torch=(med["CTC loss forward, hip"] + med["CTC loss backward, hip"]) /
                   med["CTC loss forward + backward, torch"])
-    print(f"planner: {plan} images per workgroup; decoder + loss step hip / torch {result['step_hip_over_torch']:.2f}; "
+    print(f"planner: {plan} images per workgroup; decoder + loss step hip / torch {result['step_hip_over_torch']:.2f}, "
+          f"hip bf16x3 / torch {result['step_hip_bf16x3_over_torch']:.2f}; "
           f"recurrence backward / forward {result['recurrence_bwd_over_fwd']:.2f}; CTC loss hip / torch "
           f"{result['ctc_hip_over_torch']:.2f}", flush=True)
     if a.json:

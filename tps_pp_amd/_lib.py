@@ -82,6 +82,10 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_token_gemm_bf16_fwd": ([_f] * 5 + [_i, _i, _i, _i, _i, _i, _f], _i),
     "tpspp_mm_bf16": ([_i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _f], _i),
     "tpspp_crnn_lstm_bf16_fwd": ([_f, _f, _f, _i, _i, _i, _i, _i, _f], _i),
+    "tpspp_crnn_lstm_bf16_train_fwd": ([_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f], _i),
+    "tpspp_crnn_lstm_bf16_bwd": ([_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f], _i),
+    "tpspp_linear_bwd_weight_bf16_workspace_floats": ([_i, _i, _i, _i], ctypes.c_size_t),
+    "tpspp_linear_bwd_weight_bf16": ([_i, _i, _i, _i, _f, _f, _f, _f, _f, _f, ctypes.c_size_t, _i, _f], _i),
     "tpspp_cbam_fwd": ([_f, _f, _f, _f, _f, _f, _i, _f], _i),
     "tpspp_tpe_points_fwd": ([_f] * 13 + [_i, _f], _i),
     "tpspp_maxpool2x2_fwd": ([_f, _i, _i, _i, _i, _f, _f], _i),

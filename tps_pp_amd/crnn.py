@@ -13,7 +13,8 @@ trains through PyTorch plus the HIP warp forward and backward of the preprocesso
 (and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
 kernels of include/tpspp_crnn_train.h, and `TPSPreprocessor.set_train_backend("hip")` the preprocessor's localisation network
 onto HIP kernels (`CRNNNet.set_train_backend("torch", preprocessor="hip", decoder="hip", loss="hip")` sets all three); the VGG,
-with its pools, keeps training on PyTorch.
+with its pools, keeps training on PyTorch.  `CRNNDecoder.set_train_compute_dtype("bf16x3")` (opt-in) runs that HIP training
+graph's LSTM layers on the bf16 matrix cores, forward and backward, as three-term splits (include/tpspp.h).
 
 Precision: `set_compute_dtype` of the recogniser (None | "bf16x3" | torch.bfloat16) means for the VGG what it means for
 the NRTR backbone, and keeps its meaning for the preprocessor (its localisation network).  None, the default, is the
@@ -271,9 +272,26 @@ class CRNNDecoder(TrainBackendMixin, nn.Module):
                 layer.lstm_dtype = mode
         return self
 
+    def set_train_compute_dtype(self, mode):
+        """Opt-in precision of the HIP training graph (`_forward_train_hip`; not in the reference).  None (the default):
+        the exact fp32 kernels.  "bf16x3": in both LSTM layers the input projection, the recurrence forward and backward,
+        d w_ih, d w_hh and dx run on the bf16 matrix cores as three-term splits with fp32 accumulation
+        (`ops.crnn_bilstm_autograd(mode="bf16x3")`); the bias gradients, the embeddings and the CTC loss stay exact fp32.
+        It acts only where `_forward_train_hip` runs: `set_train_backend("hip")`, rnn_flag, features on the GPU, not the
+        eval fast path.  Kept in `train_lstm_dtype`; `lstm_dtype` (the eval path's) is not touched.  Plain bf16 operands
+        are refused: over 26 steps their flipped roundings leave under a factor of two of margin to the bar the tests
+        hold a reduced mode to, so plain-bf16 training is a follow-up."""
+        if isinstance(mode, torch.dtype) and mode == torch.bfloat16:
+            raise ValueError('set_train_compute_dtype: plain-bf16 training is a follow-up; None or "bf16x3"')
+        if not (mode is None or (isinstance(mode, str) and mode == "bf16x3")):
+            raise ValueError('set_train_compute_dtype: None or "bf16x3"')
+        self.train_lstm_dtype = mode
+        return self
+
     def __init__(self, in_channels=None, num_classes=None, rnn_flag=False, init_cfg=None, **kwargs):
         super().__init__()
         self.lstm_dtype = None                      # None: exact fp32; "bf16x3" / torch.bfloat16: `set_compute_dtype`
+        self.train_lstm_dtype = None                # None: exact fp32; "bf16x3": `set_train_compute_dtype`
         self.init_cfg = init_cfg
         self.num_classes = num_classes
         self.rnn_flag = rnn_flag
@@ -329,17 +347,19 @@ class CRNNDecoder(TrainBackendMixin, nn.Module):
     def _forward_train_hip(self, feat):
         """The training graph on HIP kernels: per layer the input projection (`tpspp_mm_f32`; the first reads its tokens
         out of the NCHW feature map through its strides), the recurrence that keeps its gates
-        (`tpspp_crnn_lstm_train_fwd` / `tpspp_crnn_lstm_bwd`) and the embedding; the last embedding writes (N, W, C)."""
+        (`tpspp_crnn_lstm_train_fwd` / `tpspp_crnn_lstm_bwd`) and the embedding; the last embedding writes (N, W, C).
+        With `set_train_compute_dtype("bf16x3")` both LSTM layers run on the bf16 matrix cores, forward and backward."""
         N, C, H, W = feat.shape
         if H != 1:
             raise ValueError(f"CRNNDecoder: feature height must be 1, got {H}")
         feat = feat.float()
         l0, l1 = self.decoder[0], self.decoder[1]
         sn, sc, _, sw = feat.stride()
-        rec = ops.crnn_bilstm_autograd(feat, (W, N, sw, sn, sc), W, N, l0.rnn)
+        kw = {} if self.train_lstm_dtype is None else {"mode": self.train_lstm_dtype}
+        rec = ops.crnn_bilstm_autograd(feat, (W, N, sw, sn, sc), W, N, l0.rnn, **kw)
         x = ops.linear_autograd(rec, l0.embedding)                      # (W, N, 256)
         K = x.shape[2]
-        rec = ops.crnn_bilstm_autograd(x, (W, N, N * K, K, 1), W, N, l1.rnn)
+        rec = ops.crnn_bilstm_autograd(x, (W, N, N * K, K, 1), W, N, l1.rnn, **kw)
         return ops.linear_nwc_autograd(rec, l1.embedding)
 
     def forward_train(self, feat, out_enc, targets_dict, img_metas):

@@ -25,9 +25,12 @@ __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c)
 // lstm_recurrence<false> (tpspp_crnn_cell.h) with the product on the bf16 matrix cores: the same work division, the same
 // accumulator map (lane l: unit l & 15 of the tile, images 4 (l >> 4) + r, all four gates), the same cell update.  Lane l
 // holds, as the A operand, h[image l & 15][k = 32 b + 8 (l >> 4) + j] read from the bf16 copy of h in LDS.
-template <bool X3>
+// Save (tpspp_crnn_lstm_bf16_train_fwd): also stores the gates after their activations and the cell state, as
+// lstm_recurrence<true> does; the two instantiations perform the same operations on h, c and out, in the same order.
+template <bool X3, bool Save>
 __global__ void __launch_bounds__(kLstmThreads)
-crnn_lstm_bf16_kernel(const float* __restrict__ xg, const u32x4* __restrict__ whh, float* __restrict__ out, int T, int N, int g)
+crnn_lstm_bf16_kernel(const float* __restrict__ xg, const u32x4* __restrict__ whh, float* __restrict__ out,
+                      float* __restrict__ gates, float* __restrict__ cell, int T, int N, int g)
 {
     constexpr int S = X3 ? 2 : 1;
     __shared__ __attribute__((aligned(16))) unsigned short hbuf[2][S][kRows * kLdH];
@@ -88,7 +91,18 @@ crnn_lstm_bf16_kernel(const float* __restrict__ xg, const u32x4* __restrict__ wh
                 unsigned short* hn = &hbuf[cur ^ 1][0][(4 * quad + r) * kLdH + u];
                 hn[0] = (unsigned short)hi;
                 if (X3) hn[kRows * kLdH] = (unsigned short)lo;
-                if (valid[r]) out[((size_t)t * N + n0 + 4 * quad + r) * (2 * kHid) + d * kHid + u] = h;
+                if (valid[r]) {
+                    const size_t tok = (size_t)t * N + n0 + 4 * quad + r;
+                    out[tok * (2 * kHid) + d * kHid + u] = h;
+                    if (Save) {
+                        float* gt = gates + (tok * 2 + d) * kGates + u;
+                        gt[0] = gi;
+                        gt[kHid] = gf;
+                        gt[2 * kHid] = gg;
+                        gt[3 * kHid] = go;
+                        cell[(tok * 2 + d) * kHid + u] = c[ut][r];
+                    }
+                }
             }
         }
         __syncthreads();            // h of this step is complete before any wavefront reads it; the other copy is free
@@ -223,30 +237,60 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 }  // namespace
 
-TPSPP_EXPORT int tpspp_crnn_lstm_bf16_fwd(const float* xg, const void* w_hh_arranged, float* out, int T, int N, int hidden,
-                                          int images_per_group, int split3, tpspp_stream_t stream)
+namespace {
+
+int check_lstm_bf16(const char* who, const void* w, int T, int N, int hidden, int images_per_group, int split3)
 {
-    const char* who = "tpspp_crnn_lstm_bf16_fwd";
-    TPSPP_REQUIRE(xg && w_hh_arranged && out, "%s: null pointer", who);
-    TPSPP_REQUIRE(aligned16(w_hh_arranged), "%s: w_hh_arranged must be 16-byte aligned", who);
+    TPSPP_REQUIRE(aligned16(w), "%s: the arranged weight must be 16-byte aligned", who);
     TPSPP_REQUIRE(hidden == kHid, "%s: hidden must be %d, got %d", who, kHid, hidden);
     TPSPP_REQUIRE(T >= 1 && N >= 0, "%s: bad sizes (T >= 1, N >= 0)", who);
     TPSPP_REQUIRE(images_per_group == 0 || lstm_group_ok(images_per_group), "%s: images_per_group must be 0, 4, 8 or 16, got %d",
                   who, images_per_group);
     TPSPP_REQUIRE(split3 == 0 || split3 == 1, "%s: split3 must be 0 or 1, got %d", who, split3);
     TPSPP_REQUIRE((long long)T * N <= (1LL << 30), "%s: T * N too large", who);
+    return TPSPP_OK;
+}
+
+template <bool Save>
+int launch_lstm_bf16(const char* who, const float* xg, const void* w_hh_arranged, float* out, float* gates, float* cell, int T,
+                     int N, int images_per_group, int split3, tpspp_stream_t stream)
+{
     if (N == 0) return TPSPP_OK;
     const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
     if (g < 0) return g;
     const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     const u32x4* w = static_cast<const u32x4*>(w_hh_arranged);
     if (split3)
-        hipLaunchKernelGGL(crnn_lstm_bf16_kernel<true>, dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg, w, out,
-                           T, N, g);
+        hipLaunchKernelGGL((crnn_lstm_bf16_kernel<true, Save>), dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg,
+                           w, out, gates, cell, T, N, g);
     else
-        hipLaunchKernelGGL(crnn_lstm_bf16_kernel<false>, dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg, w, out,
-                           T, N, g);
+        hipLaunchKernelGGL((crnn_lstm_bf16_kernel<false, Save>), dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg,
+                           w, out, gates, cell, T, N, g);
     return tpspp::check_launch(who);
+}
+
+}  // namespace
+
+TPSPP_EXPORT int tpspp_crnn_lstm_bf16_fwd(const float* xg, const void* w_hh_arranged, float* out, int T, int N, int hidden,
+                                          int images_per_group, int split3, tpspp_stream_t stream)
+{
+    const char* who = "tpspp_crnn_lstm_bf16_fwd";
+    TPSPP_REQUIRE(xg && w_hh_arranged && out, "%s: null pointer", who);
+    TPSPP_REQUIRE(aligned16(w_hh_arranged), "%s: w_hh_arranged must be 16-byte aligned", who);
+    const int rc = check_lstm_bf16(who, w_hh_arranged, T, N, hidden, images_per_group, split3);
+    if (rc != TPSPP_OK) return rc;
+    return launch_lstm_bf16<false>(who, xg, w_hh_arranged, out, nullptr, nullptr, T, N, images_per_group, split3, stream);
+}
+
+TPSPP_EXPORT int tpspp_crnn_lstm_bf16_train_fwd(const float* xg, const void* w_hh_arranged, float* out, float* gates,
+                                                float* cell, int T, int N, int hidden, int images_per_group, int split3,
+                                                tpspp_stream_t stream)
+{
+    const char* who = "tpspp_crnn_lstm_bf16_train_fwd";
+    TPSPP_REQUIRE(xg && w_hh_arranged && out && gates && cell, "%s: null pointer", who);
+    const int rc = check_lstm_bf16(who, w_hh_arranged, T, N, hidden, images_per_group, split3);
+    if (rc != TPSPP_OK) return rc;
+    return launch_lstm_bf16<true>(who, xg, w_hh_arranged, out, gates, cell, T, N, images_per_group, split3, stream);
 }
 
 TPSPP_EXPORT int tpspp_mm_bf16(int batch, int M, int N, int K, const float* A, const long long* a_strides,

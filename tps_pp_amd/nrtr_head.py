@@ -709,6 +709,16 @@ class EncodeDecodeRecognizer(nn.Module):
             self.preprocessor.LocalizationNetwork.compute_dtype = mode
         return self
 
+    def set_train_compute_dtype(self, decoder=None):
+        """The precision of the decoder's HIP training graph (not in the reference): handed to the decoder's own
+        `set_train_compute_dtype` (`CRNNDecoder`: None, the exact fp32 kernels, or "bf16x3", both LSTM layers forward and
+        backward on the bf16 matrix cores; it acts where `set_train_backend(..., decoder="hip")` does).  A decoder
+        without that switch raises.  A call that fails changes nothing."""
+        if not callable(getattr(self.decoder, "set_train_compute_dtype", None)):
+            raise ValueError(f"set_train_compute_dtype: {type(self.decoder).__name__} has no training precision switch")
+        self.decoder.set_train_compute_dtype(decoder)
+        return self
+
     def set_train_backend(self, mode, backbone=None, encoder=None, decoder=None, loss=None, preprocessor=None):
         """Kernels of the TPS++ regressor in the training graph (TPS_PP.set_train_backend): "torch" (default, PyTorch's),
         "hip" (its convolutions on the HIP forward / backward kernels) or "hip_all" (every layer of it on HIP kernels).

@@ -3372,18 +3372,128 @@ def crnn_lstm_bwd_w_hh(d_xg_dir, out):
     return torch.stack([linear_bwd_weight(dy.reshape(M, G), x, (1, M, 0, 2 * H, 1), G, H, True, False)[0] for dy, x in pairs])
 
 
+def _chk_arranged(who, mw, lead, rows, k, device):
+    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 5 + len(lead):
+        raise TypeError(f"{who}: the weight must be an MfmaWeight of the {lead + (rows, k)} stack (arrange_mfma16)")
+    _chk_gpu(f"{who} weight", mw.arranged)
+    if tuple(mw.arranged.shape[:len(lead)]) != lead or (mw.rows, mw.k) != (rows, k) or mw.arranged.device != device:
+        raise ValueError(f"{who}: the weight must be {lead + (rows, k)} arranged, on the operands' device, got "
+                         f"{tuple(mw.arranged.shape)}")
+
+
+def crnn_lstm_bf16_train_fwd(xg, mw, images_per_group=0):
+    """`tpspp_crnn_lstm_bf16_train_fwd`: `crnn_lstm_bf16` (the same bits) that keeps what `crnn_lstm_bf16_bwd` reads ->
+    (out (T, N, 512), gates (T, N, 2, 1024) after their activations, cell (T, N, 2, 256)), all fp32."""
+    who = "crnn_lstm_bf16_train_fwd"
+    xg = _lstm_operand(who, "xg", xg, (2, 4 * CRNN_HIDDEN))
+    _chk_arranged(who, mw, (2,), 4 * CRNN_HIDDEN, CRNN_HIDDEN, xg.device)
+    T, N = xg.shape[0], xg.shape[1]
+    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    gates = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    cell = torch.empty((T, N, 2, CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
+    if N > 0:
+        _call("tpspp_crnn_lstm_bf16_train_fwd", xg, xg, mw.arranged, out, gates, cell, T, N, CRNN_HIDDEN, int(images_per_group),
+              int(mw.x3))
+    return out, gates, cell
+
+
+def crnn_lstm_bf16_bwd(d_out, gates, cell, mw_t, images_per_group=0):
+    """`tpspp_crnn_lstm_bf16_bwd`: `crnn_lstm_bwd` with da W_hh on the bf16 matrix cores.  mw_t =
+    `arrange_mfma16(w_hh.transpose(1, 2), x3=...)`, the (2, 256, 1024) per-direction transposes -> d_xg (T, N, 2, 1024), the
+    unrounded fp32 gradient of the pre-activations."""
+    who = "crnn_lstm_bf16_bwd"
+    gates = _lstm_operand(who, "gates", gates, (2, 4 * CRNN_HIDDEN))
+    T, N = gates.shape[0], gates.shape[1]
+    d_out = _lstm_operand(who, "d_out", d_out, (2 * CRNN_HIDDEN,), T, N)
+    cell = _lstm_operand(who, "cell", cell, (2, CRNN_HIDDEN), T, N)
+    _chk_arranged(who, mw_t, (2,), CRNN_HIDDEN, 4 * CRNN_HIDDEN, gates.device)
+    if len({t.device for t in (d_out, gates, cell)}) != 1:
+        raise ValueError(f"{who}: all operands on one device")
+    d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
+    if N > 0:
+        _call("tpspp_crnn_lstm_bf16_bwd", gates, d_out, gates, cell, mw_t.arranged, d_xg, T, N, CRNN_HIDDEN,
+              int(images_per_group), int(mw_t.x3))
+    return d_xg
+
+
+def linear_bwd_weight_bf16_workspace_floats(batch, M, O, K):
+    return _query("tpspp_linear_bwd_weight_bf16_workspace_floats", batch, M, O, K)
+
+
+def linear_bwd_weight_bf16(dy, dy_strides, x, x_strides, batch, M, O, K, x3=True):
+    """`tpspp_linear_bwd_weight_bf16`: dW (O, K) = sum over the batch * M rows of dy[b][r][:]^T x[b][r][:] on the bf16 matrix
+    cores, both fp32 operands read through (batch, row, column) element strides (views are taken as they are) and rounded
+    or (x3) split as they are staged; a fixed split over the rows, bitwise reproducible."""
+    who = "linear_bwd_weight_bf16"
+    for name, t in ((f"{who} dy", dy), (f"{who} x", x)):
+        _chk_gpu(name, t)
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if dy.device != x.device:
+        raise ValueError(f"{who}: operands on different devices")
+    dw = torch.empty((O, K), device=dy.device, dtype=torch.float32)
+    ws, n = _ws_n(linear_bwd_weight_bf16_workspace_floats(batch, M, O, K), dy.device)
+    sd, sx = _i64(*dy_strides), _i64(*x_strides)
+    _call("tpspp_linear_bwd_weight_bf16", dy, batch, M, O, K, dy, _vp(sd), x, _vp(sx), dw, ws, n, int(bool(x3)))
+    return dw
+
+
+def _bilstm_bf16_fwd(x, w_ih, b, w_hh, cfg):
+    """`_BiLstmFunction.forward` in a reduced mode: both products on the bf16 matrix cores."""
+    desc, T, N, group, mode = cfg
+    x3 = mode == "bf16x3"
+    xg = linear_bf16_fwd(x, desc, arrange_mfma16(w_ih, b, x3=x3)).view(T, N, 2, 4 * CRNN_HIDDEN)
+    return crnn_lstm_bf16_train_fwd(xg, arrange_mfma16(w_hh, x3=x3), group)
+
+
+def _bilstm_bf16_bwd(d_out, x, w_ih, w_hh, out, gates, cell, cfg, need):
+    """`_BiLstmFunction.backward` in a reduced mode -> (dx, dw_ih (8 H, K), db (8 H), dw_hh (2, 4 H, H)), None where not
+    needed: the recurrence, d w_ih, d w_hh and dx on the bf16 matrix cores, the bias gradient exact fp32."""
+    desc, T, N, group, mode = cfg
+    x3 = mode == "bf16x3"
+    H, G, K = CRNN_HIDDEN, 4 * CRNN_HIDDEN, w_ih.shape[1]
+    d_xg = crnn_lstm_bf16_bwd(d_out.float().contiguous(), gates, cell, arrange_mfma16(w_hh.transpose(1, 2), x3=x3), group)
+    dy = d_xg.view(T * N, 2 * G)
+    nb, Mi, sb, si, sk = desc
+    dw_ih = linear_bwd_weight_bf16(dy, (Mi * 2 * G, 2 * G, 1), x, (sb, si, sk), nb, Mi, 2 * G, K, x3) if any(need[1:3]) else None
+    db = linear_bwd_weight(dy, x, desc, 2 * G, K, False, True)[1] if any(need[5:9]) else None
+    dx = None
+    if need[0]:
+        dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+        w_t = arrange_mfma16(w_ih.t(), x3=x3)                      # (K rows, 8 H): dx = dy w_ih
+        if x.dim() == 4:                                            # tokens of an NCHW map: (t, n, c) = x[n, c, 0, t]
+            sn, sc, _, sw = dx.stride()
+            mm_bf16(dy, (N * 2 * G, 2 * G, 1), w_t, dx, (sw, sn, sc), T, N)
+        else:
+            mm_bf16(dy, (N * 2 * G, 2 * G, 1), w_t, dx, (N * K, K, 1), T, N)
+    dw_hh = None
+    if any(need[3:5]):
+        if T < 2 or N == 0:
+            dw_hh = torch.zeros((2, G, H), device=x.device, dtype=torch.float32)
+        else:                                                       # the shifted views, read in place
+            sd, sx = (N * 2 * G, 2 * G, 1), (N * 2 * H, 2 * H, 1)
+            dw_hh = torch.stack([
+                linear_bwd_weight_bf16(d_xg[1:, :, 0], sd, out[:-1, :, :H], sx, T - 1, N, G, H, x3),
+                linear_bwd_weight_bf16(d_xg[:-1, :, 1], sd, out[1:, :, H:], sx, T - 1, N, G, H, x3)])
+    return dx, dw_ih, db, dw_hh
+
+
 class _BiLstmFunction(torch.autograd.Function):
     """One bidirectional nn.LSTM layer with zero initial state.  Saves the tokens, the concatenated weights, the output and
-    the recurrence's gates and cell states; the input projection's result is not kept."""
+    the recurrence's gates and cell states; the input projection's result is not kept.  cfg = (desc, T, N, group, mode): mode
+    None runs the exact fp32 kernels, "bf16x3" the bf16 matrix cores (`_bilstm_bf16_fwd` / `_bilstm_bf16_bwd`)."""
 
     @staticmethod
     def forward(ctx, x, w_ih0, w_ih1, w_hh0, w_hh1, b_ih0, b_hh0, b_ih1, b_hh1, cfg):
-        desc, T, N, group = cfg
+        desc, T, N, group, mode = cfg
         w_ih = torch.cat([w_ih0, w_ih1]).float().contiguous()
         b = torch.cat([b_ih0 + b_hh0, b_ih1 + b_hh1]).float().contiguous()
         w_hh = torch.stack([w_hh0, w_hh1]).float().contiguous()
-        xg = linear_fwd(x, desc, w_ih, b).view(T, N, 2, 4 * CRNN_HIDDEN)
-        out, gates, cell = crnn_lstm_train_fwd(xg, w_hh, group)
+        if mode is None:
+            xg = linear_fwd(x, desc, w_ih, b).view(T, N, 2, 4 * CRNN_HIDDEN)
+            out, gates, cell = crnn_lstm_train_fwd(xg, w_hh, group)
+        else:
+            out, gates, cell = _bilstm_bf16_fwd(x, w_ih, b, w_hh, cfg)
         ctx.save_for_backward(x, w_ih, w_hh, out, gates, cell)
         ctx.cfg = cfg
         return out
@@ -3392,9 +3502,15 @@ class _BiLstmFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out):
         x, w_ih, w_hh, out, gates, cell = ctx.saved_tensors
-        desc, T, N, group = ctx.cfg
+        desc, T, N, group, mode = ctx.cfg
         need = ctx.needs_input_grad
         H, K = CRNN_HIDDEN, w_ih.shape[1]
+        if mode is not None:
+            dx, dw_ih, db, dw_hh = _bilstm_bf16_bwd(d_out, x, w_ih, w_hh, out, gates, cell, ctx.cfg, need)
+            gw = (None, None) if dw_ih is None else (dw_ih[:4 * H], dw_ih[4 * H:])
+            gb = (None,) * 4 if db is None else (db[:4 * H], db[:4 * H].clone(), db[4 * H:], db[4 * H:].clone())
+            gh = (None, None) if dw_hh is None else (dw_hh[0], dw_hh[1])
+            return (dx, gw[0], gw[1], gh[0], gh[1], *gb, None)
         w_hh_t = torch.stack([transpose2d(w_hh[0]), transpose2d(w_hh[1])])
         d_xg, d_dir = crnn_lstm_bwd(d_out.float().contiguous(), gates, cell, w_hh_t, group, direction_major=True)
         dy = d_xg.view(T * N, 8 * H)
@@ -3415,13 +3531,22 @@ class _BiLstmFunction(torch.autograd.Function):
         return (dx, gw[0], gw[1], dw_hh[0], dw_hh[1], *gb, None)
 
 
-def crnn_bilstm_autograd(x, desc, T, N, lstm, images_per_group=0):
+def crnn_bilstm_autograd(x, desc, T, N, lstm, images_per_group=0, mode=None):
     """The bidirectional nn.LSTM(K, 256) `lstm` with zero initial state on the token operand x (`desc` = (T, N, batch stride,
     row stride, k stride) as `linear_fwd` takes it: a dense (T, N, K) tensor, or the (N, K, 1, T) feature map read in place)
-    -> (T, N, 512), differentiable in x and in all eight parameters of the layer: input projection and its weight / data
-    gradients on `tpspp_mm_f32` / `tpspp_linear_bwd_weight`, the recurrence on `tpspp_crnn_lstm_train_fwd` / `_bwd`, d w_hh
-    on `tpspp_mm_f32` over shifted views."""
+    -> (T, N, 512), differentiable in x and in all eight parameters of the layer.
+    mode None (exact fp32): the input projection and dx on `tpspp_mm_f32`, d w_ih and the bias gradient on
+    `tpspp_linear_bwd_weight`, the recurrence on `tpspp_crnn_lstm_train_fwd` / `tpspp_crnn_lstm_bwd`, d w_hh on
+    `tpspp_linear_bwd_weight` over the direction-major copy of d_xg and the shifted view of the output.
+    mode "bf16x3" (the three-term split on the bf16 matrix cores, fp32 accumulation): the input projection and dx on
+    `tpspp_mm_bf16` (dx of a feature map written through its strides), the recurrence on
+    `tpspp_crnn_lstm_bf16_train_fwd` / `tpspp_crnn_lstm_bf16_bwd`, d w_ih and d w_hh on `tpspp_linear_bwd_weight_bf16` (d w_hh
+    over the shifted views of d_xg and the output, read in place); the bias gradient stays on `tpspp_linear_bwd_weight`,
+    exact fp32.  The weights are arranged (`arrange_mfma16`, torch code on their device) once per forward and once per
+    backward; nothing synchronises with the host."""
     who = "crnn_bilstm_autograd"
+    if not (mode is None or (isinstance(mode, str) and mode == "bf16x3")):
+        raise ValueError(f'{who}: mode must be None or "bf16x3"')
     _chk_gpu(f"{who} x", x)
     if x.dtype != torch.float32:
         raise TypeError(f"{who}: x must be float32, got {x.dtype}")
@@ -3435,7 +3560,7 @@ def crnn_bilstm_autograd(x, desc, T, N, lstm, images_per_group=0):
         raise ValueError(f"{who}: x must be a dense ({T}, {N}, {K}) tensor or an (N, K, 1, T) feature map, got {tuple(x.shape)}")
     return _BiLstmFunction.apply(x, lstm.weight_ih_l0, lstm.weight_ih_l0_reverse, lstm.weight_hh_l0, lstm.weight_hh_l0_reverse,
                                  lstm.bias_ih_l0, lstm.bias_hh_l0, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse,
-                                 (tuple(int(v) for v in desc), int(T), int(N), int(images_per_group)))
+                                 (tuple(int(v) for v in desc), int(T), int(N), int(images_per_group), mode))
 
 
 class _LinearNwcFunction(torch.autograd.Function):
