@@ -151,6 +151,52 @@ def test_backward_is_reproducible_over_calls_and_streams(cuda, bwd_batch, mode):
     assert torch.equal(bits(first), bits(again)) and torch.equal(bits(first), bits(side))
 
 
+# ---- 2b. one body for every precision --------------------------------------------------------------------------------------------
+# At T = 1 neither recurrence multiplies anything that matters (the forward's h_0 is zero, the backward leaves before its
+# product), so all that runs is the part the fp32 and the bf16 kernels share -- and they must agree to the bit.  N = 5 with
+# g = 4 has a partial block, N = 17 with g = 16 one full block plus one image.
+T1_CASES = [(N, g) for N in (1, 5, 17) for g in (0, 4, 16)]
+
+
+def t1_case(N):
+    gen = torch.Generator().manual_seed(7100 + N)
+    xg = torch.randn((1, N, 2, 4 * H), generator=gen)
+    assert not (xg == 0).any()          # the sign of a zero pre-activation may differ between an fp32 and a bf16 sum of zeros
+    return xg, torch.randn((2, 4 * H, H), generator=gen) / 16, torch.randn((1, N, 2 * H), generator=gen)
+
+
+@pytest.mark.parametrize("N,group", T1_CASES)
+def test_one_step_forward_gives_the_same_bits_in_every_precision(cuda, N, group):
+    xg, w_hh, _ = t1_case(N)
+    with GA.guarded(cuda) as g:
+        x, w = g.input(xg), g.input(w_hh)
+        want, plain = ops.crnn_lstm_train_fwd(x, w, group), ops.crnn_lstm(x, w, group)
+        got = {}
+        for mode in MODES:
+            a = on_device(g, ops.arrange_mfma16(w_hh, x3=mode == "bf16x3"))
+            got[mode] = ops.crnn_lstm_bf16_train_fwd(x, a, group) + (ops.crnn_lstm_bf16(x, a, group),)
+        g.check(list(want) + [plain] + [t for v in got.values() for t in v], require_guarded=True)
+    assert torch.equal(bits(plain), bits(want[0])), "crnn_lstm's out differs from crnn_lstm_train_fwd's"
+    for mode, v in got.items():
+        for name, a, b in zip(("out", "gates", "cell", "out of crnn_lstm_bf16"), want + (plain,), v):
+            assert torch.equal(bits(a), bits(b)), f"{mode}: {name} differs from the fp32 kernel's"
+
+
+@pytest.mark.parametrize("N,group", T1_CASES)
+def test_one_step_backward_gives_the_same_bits_in_every_precision(cuda, N, group):
+    xg, w_hh, d_out = t1_case(N)
+    _, gates, cell = ops.crnn_lstm_train_fwd(xg.to(cuda), w_hh.to(cuda), group)
+    gates, cell = gates.cpu(), cell.cpu()
+    with GA.guarded(cuda) as g:
+        d_xg, d_dir = ops.crnn_lstm_bwd(g.input(d_out), g.input(gates), g.input(cell), g.input(w_hh.transpose(1, 2).contiguous()),
+                                        group, direction_major=True)
+        g.check([d_xg, d_dir], require_guarded=True)
+    assert torch.equal(bits(d_dir), bits(d_xg.permute(2, 0, 1, 3))), "d_xg_dir is not d_xg, direction-major"
+    for mode in MODES:
+        got = run_bwd(cuda, d_out, gates, cell, w_hh, mode, group)
+        assert torch.equal(bits(got), bits(d_xg)), f"{mode}: d_xg differs from the fp32 kernel's"
+
+
 # ---- 3. the weight gradient ---------------------------------------------------------------------------------------------------
 def run_wg(cuda, make, batch, M, O, K, mode, stream=None):
     """`make(put)` -> (dy view, dy strides, x view, x strides) on the device."""

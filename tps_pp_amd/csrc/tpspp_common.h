@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "tpspp.h"
@@ -19,6 +20,8 @@ int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
 
 inline hipStream_t as_stream(tpspp_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // Per-device one-off set-up (hipFuncSetAttribute for > 64 KB of dynamic LDS is a per-device property of a kernel):
 //     static bool done[tpspp::kMaxDevices] = {};  if (tpspp::first_use_on_device(done)) { ... }

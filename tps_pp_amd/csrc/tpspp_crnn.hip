@@ -41,11 +41,11 @@ crnn_maxpool_kernel(const float* __restrict__ in, float* __restrict__ out, long 
 }
 
 // ---- the LSTM recurrence -----------------------------------------------------------------------------------------------------
-// (the constants, the activations and the body: tpspp_crnn_cell.h, shared with the training kernels)
+// (the body, its fp32 product and the entry points' shared checks: tpspp_crnn_cell.h)
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_kernel(const float* __restrict__ xg, const float* __restrict__ whh, float* __restrict__ out, int T, int N, int g)
 {
-    lstm_recurrence<false>(xg, whh, out, nullptr, nullptr, T, N, g);
+    lstm_forward<MulF32, false>(xg, whh, out, nullptr, nullptr, T, N, g);
 }
 
 // ---- CTC greedy decode -----------------------------------------------------------------------------------------------------
@@ -135,15 +135,11 @@ TPSPP_EXPORT int tpspp_crnn_lstm_fwd(const float* xg, const float* w_hh, float* 
 {
     const char* who = "tpspp_crnn_lstm_fwd";
     TPSPP_REQUIRE(xg && w_hh && out, "%s: null pointer", who);
-    TPSPP_REQUIRE(hidden == kHid, "%s: hidden must be %d, got %d", who, kHid, hidden);
-    TPSPP_REQUIRE(T >= 1 && N >= 0, "%s: bad sizes (T >= 1, N >= 0)", who);
-    TPSPP_REQUIRE(images_per_group == 0 || lstm_group_ok(images_per_group), "%s: images_per_group must be 0, 4, 8 or 16, got %d",
-                  who, images_per_group);
-    TPSPP_REQUIRE((long long)T * N <= (1LL << 30), "%s: T * N too large", who);
-    if (N == 0) return TPSPP_OK;
-    const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
+    const int rc = check_lstm(who, T, N, hidden, images_per_group);
+    if (rc != TPSPP_OK || N == 0) return rc;
+    unsigned groups;
+    const int g = lstm_grid(N, images_per_group, groups);
     if (g < 0) return g;
-    const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     hipLaunchKernelGGL(crnn_lstm_kernel, dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg, w_hh, out, T, N, g);
     return tpspp::check_launch(who);
 }

@@ -13,101 +13,16 @@ namespace {
 using namespace tpspp_dev;
 using namespace tpspp_crnn_cell;
 
-constexpr int kLdH = kHid + 8;                      // LDS row stride of h in bf16: 16-byte aligned, rows 4 banks apart
-constexpr int kWhhSlab = (kGates / 16) * (kHid / 32) * kWave;      // 16-byte units of one direction's w_hh slab
-
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+using tpspp::aligned16;
 
 // ---- the recurrence ----------------------------------------------------------------------------------------------------------
-// lstm_recurrence<false> (tpspp_crnn_cell.h) with the product on the bf16 matrix cores: the same work division, the same
-// accumulator map (lane l: unit l & 15 of the tile, images 4 (l >> 4) + r, all four gates), the same cell update.  Lane l
-// holds, as the A operand, h[image l & 15][k = 32 b + 8 (l >> 4) + j] read from the bf16 copy of h in LDS.
-// Save (tpspp_crnn_lstm_bf16_train_fwd): also stores the gates after their activations and the cell state, as
-// lstm_recurrence<true> does; the two instantiations perform the same operations on h, c and out, in the same order.
+// (the body and its bf16 product: tpspp_crnn_cell.h.  Save: tpspp_crnn_lstm_bf16_train_fwd)
 template <bool X3, bool Save>
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_bf16_kernel(const float* __restrict__ xg, const u32x4* __restrict__ whh, float* __restrict__ out,
                       float* __restrict__ gates, float* __restrict__ cell, int T, int N, int g)
 {
-    constexpr int S = X3 ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) unsigned short hbuf[2][S][kRows * kLdH];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    const int d = blockIdx.x & 1;
-    const int n0 = (int)(blockIdx.x >> 1) * g;
-    const int col = lane & 15, quad = lane >> 4;
-    for (int i = tid; i < 2 * S * kRows * kLdH; i += kLstmThreads) (&hbuf[0][0][0])[i] = 0;
-    const u32x4* w = whh + (size_t)d * S * kWhhSlab + lane;
-    float c[2][4];
-    bool valid[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        c[0][r] = c[1][r] = 0.0f;
-        valid[r] = 4 * quad + r < g && n0 + 4 * quad + r < N;
-    }
-    int cur = 0;
-    __syncthreads();
-    for (int s = 0; s < T; ++s) {
-        const int t = d ? T - 1 - s : s;
-        const unsigned short* hrow = &hbuf[cur][0][col * kLdH + 8 * quad];
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int tile = 2 * wave + ut;
-            const int u = tile * 16 + col;
-            f32x4 acc[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float* x = xg + (((size_t)t * N + (valid[r] ? n0 + 4 * quad + r : 0)) * 2 + d) * kGates + u;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q][r] = valid[r] ? x[q * kHid] : 0.0f;
-            }
-            // (unrolled by two only: all eight steps' weight fragments in flight at once spill)
-#pragma unroll 2
-            for (int b = 0; b < kHid / 32; ++b) {
-                const u32x4 ah = *reinterpret_cast<const u32x4*>(hrow + 32 * b);
-                u32x4 al = ah;
-                if (X3) al = *reinterpret_cast<const u32x4*>(hrow + kRows * kLdH + 32 * b);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const u32x4* wt = w + ((q * 16 + tile) * (kHid / 32) + b) * kWave;
-                    const u32x4 bh = wt[0];
-                    acc[q] = mfma_bf16(ah, bh, acc[q]);                     // w_hi h_hi
-                    if (X3) {
-                        acc[q] = mfma_bf16(al, bh, acc[q]);                 // w_hi h_lo
-                        acc[q] = mfma_bf16(ah, wt[kWhhSlab], acc[q]);       // w_lo h_hi
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float gi = sigmoid_safe(acc[0][r]), gf = sigmoid_safe(acc[1][r]);
-                const float gg = tanh_safe(acc[2][r]), go = sigmoid_safe(acc[3][r]);
-                c[ut][r] = gf * c[ut][r] + gi * gg;
-                const float h = go * tanh_safe(c[ut][r]);
-                unsigned hi, lo;
-                split2(h, 0.0f, hi, lo);                                    // rows past the block: xg = 0 keeps c = h = 0
-                unsigned short* hn = &hbuf[cur ^ 1][0][(4 * quad + r) * kLdH + u];
-                hn[0] = (unsigned short)hi;
-                if (X3) hn[kRows * kLdH] = (unsigned short)lo;
-                if (valid[r]) {
-                    const size_t tok = (size_t)t * N + n0 + 4 * quad + r;
-                    out[tok * (2 * kHid) + d * kHid + u] = h;
-                    if (Save) {
-                        float* gt = gates + (tok * 2 + d) * kGates + u;
-                        gt[0] = gi;
-                        gt[kHid] = gf;
-                        gt[2 * kHid] = gg;
-                        gt[3 * kHid] = go;
-                        cell[(tok * 2 + d) * kHid + u] = c[ut][r];
-                    }
-                }
-            }
-        }
-        __syncthreads();            // h of this step is complete before any wavefront reads it; the other copy is free
-        cur ^= 1;
-    }
+    lstm_forward<MulBf16<X3>, Save>(xg, whh, out, gates, cell, T, N, g);
 }
 
 // ---- the projection ------------------------------------------------------------------------------------------------------------
@@ -233,32 +148,17 @@ mm_bf16_kernel(const MmArgs p)
     }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-}  // namespace
-
-namespace {
-
-int check_lstm_bf16(const char* who, const void* w, int T, int N, int hidden, int images_per_group, int split3)
-{
-    TPSPP_REQUIRE(aligned16(w), "%s: the arranged weight must be 16-byte aligned", who);
-    TPSPP_REQUIRE(hidden == kHid, "%s: hidden must be %d, got %d", who, kHid, hidden);
-    TPSPP_REQUIRE(T >= 1 && N >= 0, "%s: bad sizes (T >= 1, N >= 0)", who);
-    TPSPP_REQUIRE(images_per_group == 0 || lstm_group_ok(images_per_group), "%s: images_per_group must be 0, 4, 8 or 16, got %d",
-                  who, images_per_group);
-    TPSPP_REQUIRE(split3 == 0 || split3 == 1, "%s: split3 must be 0 or 1, got %d", who, split3);
-    TPSPP_REQUIRE((long long)T * N <= (1LL << 30), "%s: T * N too large", who);
-    return TPSPP_OK;
-}
-
+// the checks after the null pointers, and the launch
 template <bool Save>
 int launch_lstm_bf16(const char* who, const float* xg, const void* w_hh_arranged, float* out, float* gates, float* cell, int T,
-                     int N, int images_per_group, int split3, tpspp_stream_t stream)
+                     int N, int hidden, int images_per_group, int split3, tpspp_stream_t stream)
 {
-    if (N == 0) return TPSPP_OK;
-    const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
+    TPSPP_REQUIRE(aligned16(w_hh_arranged), "%s: w_hh_arranged must be 16-byte aligned", who);
+    const int rc = check_lstm(who, T, N, hidden, images_per_group, split3);
+    if (rc != TPSPP_OK || N == 0) return rc;
+    unsigned groups;
+    const int g = lstm_grid(N, images_per_group, groups);
     if (g < 0) return g;
-    const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     const u32x4* w = static_cast<const u32x4*>(w_hh_arranged);
     if (split3)
         hipLaunchKernelGGL((crnn_lstm_bf16_kernel<true, Save>), dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg,
@@ -276,10 +176,7 @@ TPSPP_EXPORT int tpspp_crnn_lstm_bf16_fwd(const float* xg, const void* w_hh_arra
 {
     const char* who = "tpspp_crnn_lstm_bf16_fwd";
     TPSPP_REQUIRE(xg && w_hh_arranged && out, "%s: null pointer", who);
-    TPSPP_REQUIRE(aligned16(w_hh_arranged), "%s: w_hh_arranged must be 16-byte aligned", who);
-    const int rc = check_lstm_bf16(who, w_hh_arranged, T, N, hidden, images_per_group, split3);
-    if (rc != TPSPP_OK) return rc;
-    return launch_lstm_bf16<false>(who, xg, w_hh_arranged, out, nullptr, nullptr, T, N, images_per_group, split3, stream);
+    return launch_lstm_bf16<false>(who, xg, w_hh_arranged, out, nullptr, nullptr, T, N, hidden, images_per_group, split3, stream);
 }
 
 TPSPP_EXPORT int tpspp_crnn_lstm_bf16_train_fwd(const float* xg, const void* w_hh_arranged, float* out, float* gates,
@@ -288,9 +185,7 @@ TPSPP_EXPORT int tpspp_crnn_lstm_bf16_train_fwd(const float* xg, const void* w_h
 {
     const char* who = "tpspp_crnn_lstm_bf16_train_fwd";
     TPSPP_REQUIRE(xg && w_hh_arranged && out && gates && cell, "%s: null pointer", who);
-    const int rc = check_lstm_bf16(who, w_hh_arranged, T, N, hidden, images_per_group, split3);
-    if (rc != TPSPP_OK) return rc;
-    return launch_lstm_bf16<true>(who, xg, w_hh_arranged, out, gates, cell, T, N, images_per_group, split3, stream);
+    return launch_lstm_bf16<true>(who, xg, w_hh_arranged, out, gates, cell, T, N, hidden, images_per_group, split3, stream);
 }
 
 TPSPP_EXPORT int tpspp_mm_bf16(int batch, int M, int N, int K, const float* A, const long long* a_strides,

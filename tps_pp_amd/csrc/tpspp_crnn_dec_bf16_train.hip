@@ -12,123 +12,16 @@ namespace {
 using namespace tpspp_dev;
 using namespace tpspp_crnn_cell;
 
-__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using tpspp::aligned16;
 
 // ---- backward through time -----------------------------------------------------------------------------------------------------
-constexpr int kLdDa = kGates + 8;                                   // LDS row stride of da in bf16: 16-byte aligned, rows 4 banks apart
-constexpr int kDaSlab = kRows * kLdDa;                              // bf16 elements of one (hi or lo) copy of da
-constexpr int kWtSlab = (kHid / 16) * (kGates / 32) * kWave;        // 16-byte units of one direction's arranged w_hh^T slab
-
-// crnn_lstm_bwd_kernel (tpspp_crnn_train.hip) with the product on the bf16 matrix cores: the same division, the same lane
-// <-> (image, unit) map, the same recursion.  As the A operand a lane holds da[image l & 15][j = 32 b + 8 (l >> 4) + jj] read
-// from the bf16 copy of da in LDS, as the B operand w_hh[d][j][unit] from the arranged transpose; the accumulators are dh_rec
-// of the lane's own (image, unit) pairs.
+// (the body and its bf16 product: tpspp_crnn_cell.h)
 template <bool X3>
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_bf16_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ gates, const float* __restrict__ cell,
                           const u32x4* __restrict__ wt_all, float* __restrict__ d_xg, int T, int N, int g)
 {
-    constexpr int S = X3 ? 2 : 1;
-    extern __shared__ __attribute__((aligned(16))) unsigned short da[];     // S x kRows x kLdDa
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    const int d = blockIdx.x & 1;
-    const int n0 = (int)(blockIdx.x >> 1) * g;
-    const int col = lane & 15, quad = lane >> 4;
-    const u32x4* wt = wt_all + (size_t)d * S * kWtSlab + lane;
-    float dc[2][4], dhr[2][4], cc[2][4];
-    bool valid[4];
-    const int tfirst = d ? 0 : T - 1;                               // the step the forward visited last
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        valid[r] = 4 * quad + r < g && n0 + 4 * quad + r < N;
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int u = (2 * wave + ut) * 16 + col;
-            dc[ut][r] = dhr[ut][r] = 0.0f;
-            cc[ut][r] = valid[r] ? cell[(((size_t)tfirst * N + n0 + 4 * quad + r) * 2 + d) * kHid + u] : 0.0f;
-        }
-    }
-    for (int s = 0; s < T; ++s) {
-        const int t = d ? s : T - 1 - s;
-        const bool more = s + 1 < T;                                // a step before this one in the forward's order
-        const int tp = d ? t + 1 : t - 1;
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int u = (2 * wave + ut) * 16 + col;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                float cprev = 0.0f;
-                if (valid[r]) {
-                    const size_t n = (size_t)(n0 + 4 * quad + r);
-                    const size_t tok = (size_t)t * N + n;
-                    const float* gt = gates + (tok * 2 + d) * kGates + u;
-                    const float gi = gt[0], gf = gt[kHid], gg = gt[2 * kHid], go = gt[3 * kHid];
-                    if (more) cprev = cell[(((size_t)tp * N + n) * 2 + d) * kHid + u];
-                    const float dh = d_out[tok * (2 * kHid) + d * kHid + u] + dhr[ut][r];
-                    const float tc = tanh_safe(cc[ut][r]);
-                    const float dgo = dh * tc;
-                    const float dcv = dc[ut][r] + dh * go * (1.0f - tc * tc);
-                    a[0] = dcv * gg * gi * (1.0f - gi) + 0.0f;      // + 0.0f: a zero gradient is +0, whatever the signs
-                    a[1] = dcv * cprev * gf * (1.0f - gf) + 0.0f;
-                    a[2] = dcv * gi * (1.0f - gg * gg) + 0.0f;
-                    a[3] = dgo * go * (1.0f - go) + 0.0f;
-                    dc[ut][r] = dcv * gf;
-                    float* dx = d_xg + (tok * 2 + d) * kGates + u;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dx[q * kHid] = a[q];        // the unrounded fp32 da
-                }
-                cc[ut][r] = cprev;
-                if (more) {
-                    unsigned short* dn = &da[(4 * quad + r) * kLdDa + u];   // rows past the block: 0
-#pragma unroll
-                    for (int q = 0; q < 4; q += 2) {
-                        unsigned hi, lo;
-                        split2(a[q], a[q + 1], hi, lo);
-                        dn[q * kHid] = (unsigned short)hi;
-                        dn[(q + 1) * kHid] = (unsigned short)(hi >> 16);
-                        if (X3) {
-                            dn[kDaSlab + q * kHid] = (unsigned short)lo;
-                            dn[kDaSlab + (q + 1) * kHid] = (unsigned short)(lo >> 16);
-                        }
-                    }
-                }
-            }
-        }
-        if (!more) break;                                           // nothing reads dh_rec after the last step
-        __syncthreads();                                            // da of this step is complete
-        f32x4 acc[2];
-        acc[0] = acc[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const unsigned short* arow = da + col * kLdDa + 8 * quad;
-        const u32x4* w0 = wt + (size_t)(2 * wave) * (kGates / 32) * kWave;
-#pragma unroll 4
-        for (int b = 0; b < kGates / 32; ++b) {
-            const u32x4 ah = *reinterpret_cast<const u32x4*>(arow + 32 * b);
-            u32x4 al = ah;
-            if (X3) al = *reinterpret_cast<const u32x4*>(arow + kDaSlab + 32 * b);
-#pragma unroll
-            for (int ut = 0; ut < 2; ++ut) {
-                const u32x4* wf = w0 + ((size_t)ut * (kGates / 32) + b) * kWave;
-                const u32x4 bh = wf[0];
-                acc[ut] = mfma_bf16(ah, bh, acc[ut]);               // w_hi da_hi
-                if (X3) {
-                    acc[ut] = mfma_bf16(al, bh, acc[ut]);           // w_hi da_lo
-                    acc[ut] = mfma_bf16(ah, wf[kWtSlab], acc[ut]);  // w_lo da_hi
-                }
-            }
-        }
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dhr[ut][r] = acc[ut][r];
-        }
-        __syncthreads();                                            // every wavefront has read da: the next step may write it
-    }
+    lstm_backward<MulBf16<X3>>(d_out, gates, cell, wt_all, d_xg, nullptr, T, N, g);
 }
 
 // ---- the weight gradient -------------------------------------------------------------------------------------------------------
@@ -345,23 +238,18 @@ TPSPP_EXPORT int tpspp_crnn_lstm_bf16_bwd(const float* d_out, const float* gates
     const char* who = "tpspp_crnn_lstm_bf16_bwd";
     TPSPP_REQUIRE(d_out && gates && cell && w_hh_t_arranged && d_xg, "%s: null pointer", who);
     TPSPP_REQUIRE(aligned16(w_hh_t_arranged), "%s: w_hh_t_arranged must be 16-byte aligned", who);
-    TPSPP_REQUIRE(hidden == kHid, "%s: hidden must be %d, got %d", who, kHid, hidden);
-    TPSPP_REQUIRE(T >= 1 && N >= 0, "%s: bad sizes (T >= 1, N >= 0)", who);
-    TPSPP_REQUIRE(images_per_group == 0 || lstm_group_ok(images_per_group), "%s: images_per_group must be 0, 4, 8 or 16, got %d",
-                  who, images_per_group);
-    TPSPP_REQUIRE(split3 == 0 || split3 == 1, "%s: split3 must be 0 or 1, got %d", who, split3);
-    TPSPP_REQUIRE((long long)T * N <= (1LL << 30), "%s: T * N too large", who);
-    if (N == 0) return TPSPP_OK;
-    const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
+    const int rc = check_lstm(who, T, N, hidden, images_per_group, split3);
+    if (rc != TPSPP_OK || N == 0) return rc;
+    unsigned groups;
+    const int g = lstm_grid(N, images_per_group, groups);
     if (g < 0) return g;
-    const size_t lds = (size_t)(split3 ? 2 : 1) * kDaSlab * sizeof(unsigned short);    // 66048 bytes with the split
+    const size_t lds = (split3 ? MulBf16<true>::kBwdLds : MulBf16<false>::kBwdLds) * sizeof(unsigned short);
     static bool attr_done[tpspp::kMaxDevices] = {};
     if (tpspp::first_use_on_device(attr_done)) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&crnn_lstm_bf16_bwd_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * kDaSlab * sizeof(unsigned short)));
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MulBf16<true>::kBwdLds * sizeof(unsigned short)));
         (void)hipGetLastError();
     }
-    const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     const u32x4* w = static_cast<const u32x4*>(w_hh_t_arranged);
     hipStream_t st = tpspp::as_stream(stream);
     if (split3)

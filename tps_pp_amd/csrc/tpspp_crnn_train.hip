@@ -13,118 +13,24 @@ namespace {
 using namespace tpspp_dev;
 using namespace tpspp_crnn_cell;
 
-// ---- the LSTM recurrence, saving ---------------------------------------------------------------------------------------------
+// ---- the LSTM recurrence, saving, and its backward through time -------------------------------------------------------------
+// (the two bodies and their fp32 product: tpspp_crnn_cell.h)
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_train_kernel(const float* __restrict__ xg, const float* __restrict__ whh, float* __restrict__ out,
                        float* __restrict__ gates, float* __restrict__ cell, int T, int N, int g)
 {
-    lstm_recurrence<true>(xg, whh, out, gates, cell, T, N, g);
+    lstm_forward<MulF32, true>(xg, whh, out, gates, cell, T, N, g);
 }
 
-// ---- backward through time -----------------------------------------------------------------------------------------------------
-constexpr int kDaLd = kGates + 4;                                   // LDS row stride of da in floats: rows 4 banks apart
-constexpr size_t kBwdLds = (size_t)kRows * kDaLd * sizeof(float);   // 65792 bytes
-
-// The forward's division: blockIdx.x = 2 * block-of-images + direction, wavefront w owns the units 32 w .. 32 w + 31, lane l
-// the images 4 (l >> 4) + r of units (2 w + ut) 16 + (l & 15).  As the A operand of da W_hh a lane holds da[image l & 15][j],
-// as the B operand w_hh_t[unit l & 15][j], j = 16 b + 4 (l >> 4) + m; the accumulators are dh_rec of the lane's own
-// (image, unit) pairs, so neither dc nor dh_rec leaves the registers.
 __global__ void __launch_bounds__(kLstmThreads)
 crnn_lstm_bwd_kernel(const float* __restrict__ d_out, const float* __restrict__ gates, const float* __restrict__ cell,
                      const float* __restrict__ wt_all, float* __restrict__ d_xg, float* __restrict__ d_xg_dir, int T, int N,
                      int g)
 {
-    extern __shared__ __attribute__((aligned(16))) float da[];      // kRows x kDaLd
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
-    const int d = blockIdx.x & 1;
-    const int n0 = (int)(blockIdx.x >> 1) * g;
-    const int col = lane & 15, quad = lane >> 4;
-    const float* wt = wt_all + (size_t)d * kHid * kGates;
-    float dc[2][4], dhr[2][4], cc[2][4];
-    bool valid[4];
-    const int tfirst = d ? 0 : T - 1;                               // the step the forward visited last
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        valid[r] = 4 * quad + r < g && n0 + 4 * quad + r < N;
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int u = (2 * wave + ut) * 16 + col;
-            dc[ut][r] = dhr[ut][r] = 0.0f;
-            cc[ut][r] = valid[r] ? cell[(((size_t)tfirst * N + n0 + 4 * quad + r) * 2 + d) * kHid + u] : 0.0f;
-        }
-    }
-    for (int s = 0; s < T; ++s) {
-        const int t = d ? s : T - 1 - s;
-        const bool more = s + 1 < T;                                // a step before this one in the forward's order
-        const int tp = d ? t + 1 : t - 1;
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-            const int u = (2 * wave + ut) * 16 + col;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                float cprev = 0.0f;
-                if (valid[r]) {
-                    const size_t n = (size_t)(n0 + 4 * quad + r);
-                    const size_t tok = (size_t)t * N + n;
-                    const float* gt = gates + (tok * 2 + d) * kGates + u;
-                    const float gi = gt[0], gf = gt[kHid], gg = gt[2 * kHid], go = gt[3 * kHid];
-                    if (more) cprev = cell[(((size_t)tp * N + n) * 2 + d) * kHid + u];
-                    const float dh = d_out[tok * (2 * kHid) + d * kHid + u] + dhr[ut][r];
-                    const float tc = tanh_safe(cc[ut][r]);
-                    const float dgo = dh * tc;
-                    const float dcv = dc[ut][r] + dh * go * (1.0f - tc * tc);
-                    a[0] = dcv * gg * gi * (1.0f - gi) + 0.0f;      // + 0.0f: a zero gradient is +0, whatever the signs
-                    a[1] = dcv * cprev * gf * (1.0f - gf) + 0.0f;
-                    a[2] = dcv * gi * (1.0f - gg * gg) + 0.0f;
-                    a[3] = dgo * go * (1.0f - go) + 0.0f;
-                    dc[ut][r] = dcv * gf;
-                    float* dx = d_xg + (tok * 2 + d) * kGates + u;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) dx[q * kHid] = a[q];
-                    if (d_xg_dir) {                                 // the direction-major copy: dense rows for d w_hh
-                        float* dd = d_xg_dir + ((size_t)d * T * N + tok) * kGates + u;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) dd[q * kHid] = a[q];
-                    }
-                }
-                cc[ut][r] = cprev;
-                if (more) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) da[(4 * quad + r) * kDaLd + q * kHid + u] = a[q];    // rows past the block: 0
-                }
-            }
-        }
-        if (!more) break;                                           // nothing reads dh_rec after the last step
-        __syncthreads();                                            // da of this step is complete
-        f32x4 acc[2][2];
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) acc[ut][0] = acc[ut][1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const float* arow = da + col * kDaLd + 4 * quad;
-        const float* w0 = wt + (size_t)((2 * wave) * 16 + col) * kGates + 4 * quad;
-        const float* w1 = w0 + (size_t)16 * kGates;
-#pragma unroll 2
-        for (int b = 0; b < kGates / 16; b += 2) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {                           // two accumulation chains per tile: even b, odd b
-                const f32x4 av = *reinterpret_cast<const f32x4*>(arow + 16 * (b + h));
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(w0 + 16 * (b + h));
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(w1 + 16 * (b + h));
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    acc[0][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], b0[m], acc[0][h], 0, 0, 0);
-                    acc[1][h] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], b1[m], acc[1][h], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int ut = 0; ut < 2; ++ut) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dhr[ut][r] = acc[ut][0][r] + acc[ut][1][r];
-        }
-        __syncthreads();                                            // every wavefront has read da: the next step may write it
-    }
+    lstm_backward<MulF32>(d_out, gates, cell, wt_all, d_xg, d_xg_dir, T, N, g);
 }
+
+constexpr size_t kBwdLds = MulF32::kBwdLds * sizeof(float);
 
 // ---- CTC loss ------------------------------------------------------------------------------------------------------------------
 constexpr int kCtcThreads = 64;             // one wavefront per image
@@ -318,16 +224,6 @@ ctc_loss_bwd_kernel(const CtcParams P, const float* __restrict__ g, const float*
     }
 }
 
-int check_lstm(const char* who, int T, int N, int hidden, int images_per_group)
-{
-    TPSPP_REQUIRE(hidden == kHid, "%s: hidden must be %d, got %d", who, kHid, hidden);
-    TPSPP_REQUIRE(T >= 1 && N >= 0, "%s: bad sizes (T >= 1, N >= 0)", who);
-    TPSPP_REQUIRE(images_per_group == 0 || lstm_group_ok(images_per_group), "%s: images_per_group must be 0, 4, 8 or 16, got %d",
-                  who, images_per_group);
-    TPSPP_REQUIRE((long long)T * N <= (1LL << 30), "%s: T * N too large", who);
-    return TPSPP_OK;
-}
-
 int check_ctc(const char* who, int N, int T, int C, int Lmax, int blank, int reduction)
 {
     TPSPP_REQUIRE(N >= 0 && T >= 1, "%s: bad sizes (N >= 0, T >= 1)", who);
@@ -356,12 +252,11 @@ TPSPP_EXPORT int tpspp_crnn_lstm_train_fwd(const float* xg, const float* w_hh, f
 {
     const char* who = "tpspp_crnn_lstm_train_fwd";
     TPSPP_REQUIRE(xg && w_hh && out && gates && cell, "%s: null pointer", who);
-    int rc = check_lstm(who, T, N, hidden, images_per_group);
-    if (rc != TPSPP_OK) return rc;
-    if (N == 0) return TPSPP_OK;
-    const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
+    const int rc = check_lstm(who, T, N, hidden, images_per_group);
+    if (rc != TPSPP_OK || N == 0) return rc;
+    unsigned groups;
+    const int g = lstm_grid(N, images_per_group, groups);
     if (g < 0) return g;
-    const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     hipLaunchKernelGGL(crnn_lstm_train_kernel, dim3(groups), dim3(kLstmThreads), 0, tpspp::as_stream(stream), xg, w_hh, out,
                        gates, cell, T, N, g);
     return tpspp::check_launch(who);
@@ -373,10 +268,10 @@ TPSPP_EXPORT int tpspp_crnn_lstm_bwd(const float* d_out, const float* gates, con
 {
     const char* who = "tpspp_crnn_lstm_bwd";
     TPSPP_REQUIRE(d_out && gates && cell && w_hh_t && d_xg, "%s: null pointer", who);
-    int rc = check_lstm(who, T, N, hidden, images_per_group);
-    if (rc != TPSPP_OK) return rc;
-    if (N == 0) return TPSPP_OK;
-    const int g = tpspp_crnn_lstm_plan(N, images_per_group, 0);
+    const int rc = check_lstm(who, T, N, hidden, images_per_group);
+    if (rc != TPSPP_OK || N == 0) return rc;
+    unsigned groups;
+    const int g = lstm_grid(N, images_per_group, groups);
     if (g < 0) return g;
     static bool attr_done[tpspp::kMaxDevices] = {};
     if (tpspp::first_use_on_device(attr_done)) {
@@ -384,7 +279,6 @@ TPSPP_EXPORT int tpspp_crnn_lstm_bwd(const float* d_out, const float* gates, con
                                   (int)kBwdLds);
         (void)hipGetLastError();
     }
-    const unsigned groups = 2u * (unsigned)((N + g - 1) / g);
     hipLaunchKernelGGL(crnn_lstm_bwd_kernel, dim3(groups), dim3(kLstmThreads), kBwdLds, tpspp::as_stream(stream), d_out, gates,
                        cell, w_hh_t, d_xg, d_xg_dir, T, N, g);
     return tpspp::check_launch(who);

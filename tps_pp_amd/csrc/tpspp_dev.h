@@ -10,6 +10,7 @@ namespace tpspp_dev {
 constexpr int kWave = 64;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -43,6 +44,12 @@ __device__ __forceinline__ void split2(float v0, float v1, unsigned& hi, unsigne
     hi = pack_bf16(v0, v1);
     const float h0 = __builtin_bit_cast(float, hi << 16), h1 = __builtin_bit_cast(float, hi & 0xffff0000u);
     lo = pack_bf16(v0 - h0, v1 - h1);
+}
+
+// v_mfma_f32_16x16x32_bf16 on operands held as four 32-bit words of packed bf16
+__device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
 // ds_read_b64_tr_b16: lane (l & 15) of a 16-lane group gets column l & 15 of a [4 rows][16 columns] block of 16-bit

@@ -3181,20 +3181,67 @@ def crnn_lstm_plan(N, images_per_group=0, compute_units=0):
     return g
 
 
+def _lstm_operand(who, name, t, shape_tail, T=None, N=None):
+    t = _chk(f"{who} {name}", t, 2 + len(shape_tail))
+    if tuple(t.shape[2:]) != tuple(shape_tail) or (T is not None and tuple(t.shape[:2]) != (T, N)):
+        raise ValueError(f"{who}: {name} must be (T, N, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}")
+    return t
+
+
+def _chk_arranged(who, mw, lead, rows, k, device):
+    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 5 + len(lead):
+        raise TypeError(f"{who}: the weight must be an MfmaWeight of the {lead + (rows, k)} stack (arrange_mfma16)")
+    _chk_gpu(f"{who} weight", mw.arranged)
+    if tuple(mw.arranged.shape[:len(lead)]) != lead or (mw.rows, mw.k) != (rows, k) or mw.arranged.device != device:
+        raise ValueError(f"{who}: the weight must be {lead + (rows, k)} arranged, on the operands' device, got "
+                         f"{tuple(mw.arranged.shape)}")
+
+
+def _lstm_weight(who, name, w, rows, k, device, bf16):
+    """The recurrent weight of both directions, a dense fp32 (2, rows, k) tensor or (bf16) its `MfmaWeight` -> (what the
+    entry point reads, the split3 argument that only a bf16 entry point takes)."""
+    if bf16:
+        _chk_arranged(who, w, (2,), rows, k, device)
+        return w.arranged, (int(w.x3),)
+    w = _chk(f"{who} {name}", w, 3)
+    if tuple(w.shape) != (2, rows, k) or w.device != device:
+        raise ValueError(f"{who}: {name} must be (2, {rows}, {k}) on the operands' device, got {tuple(w.shape)}")
+    return w, ()
+
+
+def _lstm_fwd(who, entry, xg, w_hh, images_per_group, bf16, save):
+    """The four forward recurrences on their entry points -> out, or (save: a `_train_fwd`) -> (out, gates, cell)."""
+    xg = _lstm_operand(who, "xg", xg, (2, 4 * CRNN_HIDDEN))
+    w, split3 = _lstm_weight(who, "w_hh", w_hh, 4 * CRNN_HIDDEN, CRNN_HIDDEN, xg.device, bf16)
+    T, N = xg.shape[0], xg.shape[1]
+    tails = ((2 * CRNN_HIDDEN,), (2, 4 * CRNN_HIDDEN), (2, CRNN_HIDDEN))[:3 if save else 1]
+    outs = [torch.empty((T, N) + tail, device=xg.device, dtype=torch.float32) for tail in tails]
+    if N > 0:
+        _call(entry, xg, xg, w, *outs, T, N, CRNN_HIDDEN, int(images_per_group), *split3)
+    return tuple(outs) if save else outs[0]
+
+
+def _lstm_bwd(who, entry, d_out, gates, cell, w_hh_t, images_per_group, bf16, direction_major=False):
+    """The two backwards through time on their entry points -> (d_xg, its direction-major copy | None)."""
+    gates = _lstm_operand(who, "gates", gates, (2, 4 * CRNN_HIDDEN))
+    T, N = gates.shape[0], gates.shape[1]
+    d_out = _lstm_operand(who, "d_out", d_out, (2 * CRNN_HIDDEN,), T, N)
+    cell = _lstm_operand(who, "cell", cell, (2, CRNN_HIDDEN), T, N)
+    w, split3 = _lstm_weight(who, "w_hh_t", w_hh_t, CRNN_HIDDEN, 4 * CRNN_HIDDEN, gates.device, bf16)
+    if len({t.device for t in (d_out, gates, cell)}) != 1:
+        raise ValueError(f"{who}: all operands on one device")
+    d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
+    d_dir = torch.empty((2, T, N, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32) if direction_major else None
+    if N > 0:
+        _call(entry, gates, d_out, gates, cell, w, d_xg, *(() if bf16 else (d_dir,)), T, N, CRNN_HIDDEN, int(images_per_group),
+              *split3)
+    return d_xg, d_dir
+
+
 def crnn_lstm(xg, w_hh, images_per_group=0):
     """The recurrence of one bidirectional nn.LSTM(., 256) layer with zero initial state (`tpspp_crnn_lstm_fwd`;
     lstm_layer.py:14): xg (T, N, 2, 1024) input pre-activations of both directions, w_hh (2, 1024, 256) -> (T, N, 512)."""
-    xg, w_hh = _chk("crnn_lstm xg", xg, 4), _chk("crnn_lstm w_hh", w_hh, 3)
-    T, N = xg.shape[0], xg.shape[1]
-    if tuple(xg.shape[2:]) != (2, 4 * CRNN_HIDDEN) or tuple(w_hh.shape) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) \
-            or w_hh.device != xg.device:
-        raise ValueError(f"crnn_lstm: xg (T, N, 2, 1024) and w_hh (2, 1024, 256) on one device, got {tuple(xg.shape)}, "
-                         f"{tuple(w_hh.shape)}")
-    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    if N == 0:
-        return out
-    _call("tpspp_crnn_lstm_fwd", xg, xg, w_hh, out, T, N, CRNN_HIDDEN, int(images_per_group))
-    return out
+    return _lstm_fwd("crnn_lstm", "tpspp_crnn_lstm_fwd", xg, w_hh, images_per_group, False, False)
 
 
 class MfmaWeight:
@@ -3260,20 +3307,7 @@ def linear_bf16_fwd(x, desc, mw):
 def crnn_lstm_bf16(xg, mw, images_per_group=0):
     """`crnn_lstm` with the recurrent product on the bf16 matrix cores (`tpspp_crnn_lstm_bf16_fwd`): xg (T, N, 2, 1024)
     fp32, mw = `arrange_mfma16(w_hh (2, 1024, 256), x3=...)` -> (T, N, 512) fp32; h is rounded (x3: split) per step."""
-    xg = _chk("crnn_lstm_bf16 xg", xg, 4)
-    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 6:
-        raise TypeError("crnn_lstm_bf16: the weight must be an MfmaWeight of the (2, 1024, 256) stack (arrange_mfma16)")
-    _chk_gpu("crnn_lstm_bf16 w_hh", mw.arranged)
-    T, N = xg.shape[0], xg.shape[1]
-    if tuple(xg.shape[2:]) != (2, 4 * CRNN_HIDDEN) or (mw.arranged.shape[0], mw.rows, mw.k) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) \
-            or mw.arranged.device != xg.device:
-        raise ValueError(f"crnn_lstm_bf16: xg (T, N, 2, 1024) and w_hh (2, 1024, 256) arranged, on one device, got "
-                         f"{tuple(xg.shape)}, {tuple(mw.arranged.shape)}")
-    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    if N == 0:
-        return out
-    _call("tpspp_crnn_lstm_bf16_fwd", xg, xg, mw.arranged, out, T, N, CRNN_HIDDEN, int(images_per_group), int(mw.x3))
-    return out
+    return _lstm_fwd("crnn_lstm_bf16", "tpspp_crnn_lstm_bf16_fwd", xg, mw, images_per_group, True, False)
 
 
 def crnn_ctc_decode_device(logits, decode_len, blank=0):
@@ -3312,48 +3346,18 @@ def crnn_ctc_decode(logits, decode_len, blank=0):
 
 
 # ---- training of the CRNN decoder and the CTC loss (include/tpspp_crnn_train.h, tpspp_crnn_train.hip) --------------
-def _lstm_operand(who, name, t, shape_tail, T=None, N=None):
-    t = _chk(f"{who} {name}", t, 2 + len(shape_tail))
-    if tuple(t.shape[2:]) != tuple(shape_tail) or (T is not None and tuple(t.shape[:2]) != (T, N)):
-        raise ValueError(f"{who}: {name} must be (T, N, {', '.join(map(str, shape_tail))}), got {tuple(t.shape)}")
-    return t
-
-
 def crnn_lstm_train_fwd(xg, w_hh, images_per_group=0):
     """`tpspp_crnn_lstm_train_fwd`: `crnn_lstm` (the same bits) that keeps what `crnn_lstm_bwd` reads ->
     (out (T, N, 512), gates (T, N, 2, 1024) after their activations, cell (T, N, 2, 256))."""
-    who = "crnn_lstm_train_fwd"
-    xg = _lstm_operand(who, "xg", xg, (2, 4 * CRNN_HIDDEN))
-    w_hh = _chk(f"{who} w_hh", w_hh, 3)
-    if tuple(w_hh.shape) != (2, 4 * CRNN_HIDDEN, CRNN_HIDDEN) or w_hh.device != xg.device:
-        raise ValueError(f"{who}: w_hh must be (2, 1024, 256) on xg's device, got {tuple(w_hh.shape)}")
-    T, N = xg.shape[0], xg.shape[1]
-    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    gates = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    cell = torch.empty((T, N, 2, CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    if N == 0:
-        return out, gates, cell
-    _call("tpspp_crnn_lstm_train_fwd", xg, xg, w_hh, out, gates, cell, T, N, CRNN_HIDDEN, int(images_per_group))
-    return out, gates, cell
+    return _lstm_fwd("crnn_lstm_train_fwd", "tpspp_crnn_lstm_train_fwd", xg, w_hh, images_per_group, False, True)
 
 
 def crnn_lstm_bwd(d_out, gates, cell, w_hh_t, images_per_group=0, direction_major=False):
     """`tpspp_crnn_lstm_bwd`: the backward through time.  d_out (T, N, 512), gates and cell of `crnn_lstm_train_fwd`, w_hh_t
     (2, 256, 1024) the per-direction transpose of w_hh -> d_xg (T, N, 2, 1024), the gradient of the pre-activations; with
     `direction_major` -> (d_xg, its copy as (2, T, N, 1024): what `crnn_lstm_bwd_w_hh` reads)."""
-    who = "crnn_lstm_bwd"
-    gates = _lstm_operand(who, "gates", gates, (2, 4 * CRNN_HIDDEN))
-    T, N = gates.shape[0], gates.shape[1]
-    d_out = _lstm_operand(who, "d_out", d_out, (2 * CRNN_HIDDEN,), T, N)
-    cell = _lstm_operand(who, "cell", cell, (2, CRNN_HIDDEN), T, N)
-    w_hh_t = _chk(f"{who} w_hh_t", w_hh_t, 3)
-    if tuple(w_hh_t.shape) != (2, CRNN_HIDDEN, 4 * CRNN_HIDDEN) or len({t.device for t in (d_out, gates, cell, w_hh_t)}) != 1:
-        raise ValueError(f"{who}: w_hh_t must be (2, 256, 1024), all operands on one device, got {tuple(w_hh_t.shape)}")
-    d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
-    d_dir = torch.empty((2, T, N, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32) if direction_major else None
-    if N > 0:
-        _call("tpspp_crnn_lstm_bwd", gates, d_out, gates, cell, w_hh_t, d_xg, d_dir, T, N, CRNN_HIDDEN,
-              int(images_per_group))
+    d_xg, d_dir = _lstm_bwd("crnn_lstm_bwd", "tpspp_crnn_lstm_bwd", d_out, gates, cell, w_hh_t, images_per_group, False,
+                            direction_major)
     return (d_xg, d_dir) if direction_major else d_xg
 
 
@@ -3372,48 +3376,17 @@ def crnn_lstm_bwd_w_hh(d_xg_dir, out):
     return torch.stack([linear_bwd_weight(dy.reshape(M, G), x, (1, M, 0, 2 * H, 1), G, H, True, False)[0] for dy, x in pairs])
 
 
-def _chk_arranged(who, mw, lead, rows, k, device):
-    if not isinstance(mw, MfmaWeight) or mw.arranged.dim() != 5 + len(lead):
-        raise TypeError(f"{who}: the weight must be an MfmaWeight of the {lead + (rows, k)} stack (arrange_mfma16)")
-    _chk_gpu(f"{who} weight", mw.arranged)
-    if tuple(mw.arranged.shape[:len(lead)]) != lead or (mw.rows, mw.k) != (rows, k) or mw.arranged.device != device:
-        raise ValueError(f"{who}: the weight must be {lead + (rows, k)} arranged, on the operands' device, got "
-                         f"{tuple(mw.arranged.shape)}")
-
-
 def crnn_lstm_bf16_train_fwd(xg, mw, images_per_group=0):
     """`tpspp_crnn_lstm_bf16_train_fwd`: `crnn_lstm_bf16` (the same bits) that keeps what `crnn_lstm_bf16_bwd` reads ->
     (out (T, N, 512), gates (T, N, 2, 1024) after their activations, cell (T, N, 2, 256)), all fp32."""
-    who = "crnn_lstm_bf16_train_fwd"
-    xg = _lstm_operand(who, "xg", xg, (2, 4 * CRNN_HIDDEN))
-    _chk_arranged(who, mw, (2,), 4 * CRNN_HIDDEN, CRNN_HIDDEN, xg.device)
-    T, N = xg.shape[0], xg.shape[1]
-    out = torch.empty((T, N, 2 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    gates = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    cell = torch.empty((T, N, 2, CRNN_HIDDEN), device=xg.device, dtype=torch.float32)
-    if N > 0:
-        _call("tpspp_crnn_lstm_bf16_train_fwd", xg, xg, mw.arranged, out, gates, cell, T, N, CRNN_HIDDEN, int(images_per_group),
-              int(mw.x3))
-    return out, gates, cell
+    return _lstm_fwd("crnn_lstm_bf16_train_fwd", "tpspp_crnn_lstm_bf16_train_fwd", xg, mw, images_per_group, True, True)
 
 
 def crnn_lstm_bf16_bwd(d_out, gates, cell, mw_t, images_per_group=0):
     """`tpspp_crnn_lstm_bf16_bwd`: `crnn_lstm_bwd` with da W_hh on the bf16 matrix cores.  mw_t =
     `arrange_mfma16(w_hh.transpose(1, 2), x3=...)`, the (2, 256, 1024) per-direction transposes -> d_xg (T, N, 2, 1024), the
     unrounded fp32 gradient of the pre-activations."""
-    who = "crnn_lstm_bf16_bwd"
-    gates = _lstm_operand(who, "gates", gates, (2, 4 * CRNN_HIDDEN))
-    T, N = gates.shape[0], gates.shape[1]
-    d_out = _lstm_operand(who, "d_out", d_out, (2 * CRNN_HIDDEN,), T, N)
-    cell = _lstm_operand(who, "cell", cell, (2, CRNN_HIDDEN), T, N)
-    _chk_arranged(who, mw_t, (2,), CRNN_HIDDEN, 4 * CRNN_HIDDEN, gates.device)
-    if len({t.device for t in (d_out, gates, cell)}) != 1:
-        raise ValueError(f"{who}: all operands on one device")
-    d_xg = torch.empty((T, N, 2, 4 * CRNN_HIDDEN), device=gates.device, dtype=torch.float32)
-    if N > 0:
-        _call("tpspp_crnn_lstm_bf16_bwd", gates, d_out, gates, cell, mw_t.arranged, d_xg, T, N, CRNN_HIDDEN,
-              int(images_per_group), int(mw_t.x3))
-    return d_xg
+    return _lstm_bwd("crnn_lstm_bf16_bwd", "tpspp_crnn_lstm_bf16_bwd", d_out, gates, cell, mw_t, images_per_group, True)[0]
 
 
 def linear_bwd_weight_bf16_workspace_floats(batch, M, O, K):
@@ -3507,28 +3480,26 @@ class _BiLstmFunction(torch.autograd.Function):
         H, K = CRNN_HIDDEN, w_ih.shape[1]
         if mode is not None:
             dx, dw_ih, db, dw_hh = _bilstm_bf16_bwd(d_out, x, w_ih, w_hh, out, gates, cell, ctx.cfg, need)
-            gw = (None, None) if dw_ih is None else (dw_ih[:4 * H], dw_ih[4 * H:])
-            gb = (None,) * 4 if db is None else (db[:4 * H], db[:4 * H].clone(), db[4 * H:], db[4 * H:].clone())
-            gh = (None, None) if dw_hh is None else (dw_hh[0], dw_hh[1])
-            return (dx, gw[0], gw[1], gh[0], gh[1], *gb, None)
-        w_hh_t = torch.stack([transpose2d(w_hh[0]), transpose2d(w_hh[1])])
-        d_xg, d_dir = crnn_lstm_bwd(d_out.float().contiguous(), gates, cell, w_hh_t, group, direction_major=True)
-        dy = d_xg.view(T * N, 8 * H)
-        dw_ih, db = linear_bwd_weight(dy, x, desc, 8 * H, K, any(need[1:3]), any(need[5:9]))
-        dx = None
-        if need[0]:
-            dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
-            if x.dim() == 4:                                         # tokens of an NCHW map: (t, n, c) = x[n, c, 0, t]
-                sn, sc, _, sw = dx.stride()
-                linear_bwd_data(dy, w_ih, dx, (T, N, sw, sn, sc))
-            else:
-                linear_bwd_data(dy, w_ih, dx, (T, N, N * K, K, 1))
-        dw_hh = crnn_lstm_bwd_w_hh(d_dir, out) if any(need[3:5]) else (None, None)
+        else:
+            w_hh_t = torch.stack([transpose2d(w_hh[0]), transpose2d(w_hh[1])])
+            d_xg, d_dir = crnn_lstm_bwd(d_out.float().contiguous(), gates, cell, w_hh_t, group, direction_major=True)
+            dy = d_xg.view(T * N, 8 * H)
+            dw_ih, db = linear_bwd_weight(dy, x, desc, 8 * H, K, any(need[1:3]), any(need[5:9]))
+            dx = None
+            if need[0]:
+                dx = torch.empty(x.shape, device=x.device, dtype=torch.float32)
+                if x.dim() == 4:                                     # tokens of an NCHW map: (t, n, c) = x[n, c, 0, t]
+                    sn, sc, _, sw = dx.stride()
+                    linear_bwd_data(dy, w_ih, dx, (T, N, sw, sn, sc))
+                else:
+                    linear_bwd_data(dy, w_ih, dx, (T, N, N * K, K, 1))
+            dw_hh = crnn_lstm_bwd_w_hh(d_dir, out) if any(need[3:5]) else None
         gw = (None, None) if dw_ih is None else (dw_ih[:4 * H], dw_ih[4 * H:])
         # (b_ih and b_hh of a direction receive the same values in tensors of their own: autograd may keep a gradient it is
         # handed as the parameter's .grad, and two parameters must not share one)
         gb = (None,) * 4 if db is None else (db[:4 * H], db[:4 * H].clone(), db[4 * H:], db[4 * H:].clone())
-        return (dx, gw[0], gw[1], dw_hh[0], dw_hh[1], *gb, None)
+        gh = (None, None) if dw_hh is None else (dw_hh[0], dw_hh[1])
+        return (dx, gw[0], gw[1], gh[0], gh[1], *gb, None)
 
 
 def crnn_bilstm_autograd(x, desc, T, N, lstm, images_per_group=0, mode=None):
