@@ -968,6 +968,45 @@ int tpspp_conv2d_bf16_fwd(const void* const* src_ptrs, const int* src_dims, int 
                           int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
                           void* out, int out_f32, int Ho, int Wo, int split3, tpspp_stream_t stream);
 
+/*
+ * The kernel tpspp_conv2d_bf16_fwd launches for these arguments (a host-side query: touches no device, works without one).
+ * Takes what the forward takes, minus the stream; the pointers only for being NULL or not and for their alignment (the
+ * choice depends on the 16-byte alignment of sources, output and weight) -- none is dereferenced.  Honours bits 1 and 2 of
+ * tpspp_conv_set_tuning.  What the forward refuses is refused with the same negative code and the same tpspp_last_error
+ * text.  Otherwise a non-negative packed code:
+ *   bits 0-2   family: 0 tiled (plain bf16), 1 tiled-x3 (three-term split), 2 wide3 (3x3, 128 x 64 wavefront tiles),
+ *              3 wide1 (the same kernel's 1x1 form), 4 stem, 5 persist (persistent blocked 3x3), 6 blk1 (blocked 1x1)
+ *   bit 3      kernel size: 0 1x1, 1 3x3
+ *   bits 4-5   stride h, bits 6-7 stride w
+ *   every family but blk1:
+ *     bits 8-12  output tile rows TH, bits 13-21 tile columns TW, bits 22-24 images per tile (1, 2 or 4),
+ *     bits 25-26 32-pixel fragments per wavefront NF - 1 (tiled: NF 1 = 128-pixel workgroup tiles, 2 = 256; persist: 1 | 2;
+ *                wide3, wide1 and stem: 4)
+ *   tiled, tiled-x3: bit 27 wide staging (16-byte pieces of bf16 NCHW rows brought into patch order in LDS; needs a 3x3
+ *              stride-1 layer, a tile of a multiple of 16 columns and every source bf16 NCHW at full resolution with W a
+ *              multiple of 8 and a 16-byte aligned pointer; never with split3), bit 28 accumulators per fragment - 1 (one
+ *              32-channel accumulator for split3 with Cout <= 32, two otherwise)
+ *   persist:   bit 27 WRES (the whole weight resident in LDS: Cin <= 64), bits 28-29 EPI (0 blocked output, 1 blocked output
+ *              + blocked residual, 2 fp32 NCHW output), bit 30 CPB - 1 (two 16-channel chunks per ring slot: WRES, an even
+ *              chunk count and room for a ring of three such slots)
+ *   wide3, wide1: bits 27-28 epilogue (0 blocked output, 1 blocked + blocked residual, 2 fp32 NCHW, 3 fp32 NCHW + blocked
+ *              residual)
+ *   stem:      bit 27 output form (0 bf16 NCHW, 1 blocked)
+ *   blk1:      bits 8-11 NT (32-channel output tiles per launch), bits 12-16 NKS (16-channel k steps = Cin / 16),
+ *              bits 17-18 slices (launches, each owning NT x 32 output channels: 2 for 256 -> 512), bits 19-22 NW
+ *              (wavefronts per workgroup, 4 | 8)
+ * Some routes depend on N: blk1 wants N * Ho * Wo to be a multiple of 32 NW pixels, and every grid has its limit.  N = 0
+ * launches nothing; the code is then the one a batch of N = 8 would be judged by (a whole number of tiles of every kernel).
+ * A route, once named, is launched or the forward fails: a refused LDS opt-in or a failed CU-count query (which sizes the
+ * persistent kernels' grids, never the route) is an error that names the route, not a silent change of kernel.
+ */
+int tpspp_conv2d_bf16_route(const void* const* src_ptrs, const int* src_dims, int nsrc,
+                            const void* weight_arranged, const float* bias,
+                            const void* residual, int residual_f32,
+                            const float* post_scale, const float* post_shift,
+                            int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
+                            void* out, int out_f32, int Ho, int Wo, int split3);
+
 /* Channels per K-chunk of the bf16 conv kernel for a 1x1 / 3x3 kernel (layout of weight_arranged). */
 int tpspp_conv_bf16_chunk_channels(int kernel_size);
 

@@ -186,9 +186,11 @@ def test_conv_bf16_persistent_kernel_is_the_tiled_kernel_bit_for_bit(cuda, name,
     raw = lambda o: o.view(torch.int32) if f32_out else o.t.view(torch.int16)
     try:
         _lib.lib().tpspp_conv_set_tuning(2)
+        assert ops.conv2d_bf16_route(xs, cw, stride, **kw).startswith("tiled 3x3 ")
         want = raw(ops.conv2d_bf16(xs, cw, stride, **kw)).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route(xs, cw, stride, **kw).startswith("persist 3x3 ")
     for _ in range(2):                                      # twice: no state survives a launch
         got = raw(ops.conv2d_bf16(xs, cw, stride, **kw))
         assert torch.equal(got, want)
@@ -229,9 +231,11 @@ def test_conv3_wide_kernel_is_the_tiled_kernel_bit_for_bit(cuda, name, C, H, W, 
     raw = (lambda o: o.view(torch.int32)) if f32_out else (lambda o: o.t.view(torch.int16))
     try:
         _lib.lib().tpspp_conv_set_tuning(4)
+        assert ops.conv2d_bf16_route(xs, cw, (1, 1), **kw).startswith("tiled 3x3 ")
         want = raw(ops.conv2d_bf16(xs, cw, (1, 1), **kw)).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route(xs, cw, (1, 1), **kw).startswith("wide3 3x3 ")
     for _ in range(2):
         got = ops.conv2d_bf16(xs, cw, (1, 1), **kw)
         assert torch.equal(raw(got), want), name
@@ -256,9 +260,11 @@ def test_stem_kernel_is_the_tiled_kernel_bit_for_bit(cuda, C, H, N, relu):
     xd = x.to(cuda)
     try:
         _lib.lib().tpspp_conv_set_tuning(4)
+        assert ops.conv2d_bf16_route([xd], cw, 1, relu=relu).startswith("tiled 3x3 ")
         want = ops.conv2d_bf16([xd], cw, 1, relu=relu).view(torch.int16).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route([xd], cw, 1, relu=relu).startswith("stem 3x3 ")
     for _ in range(2):
         got = ops.conv2d_bf16([xd], cw, 1, relu=relu)
         assert got.dtype == torch.bfloat16 and torch.equal(got.view(torch.int16), want)
@@ -290,9 +296,11 @@ def test_conv_bf16_persistent_kernel_with_32_output_channels(cuda, name, H, W, s
     raw = lambda o: o.view(torch.int32) if f32_out else o.t.view(torch.int16)
     try:
         _lib.lib().tpspp_conv_set_tuning(2)
+        assert ops.conv2d_bf16_route(xs, cw, stride, **kw).startswith("tiled 3x3 ")
         want = raw(ops.conv2d_bf16(xs, cw, stride, **kw)).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route(xs, cw, stride, **kw).startswith("persist 3x3 ")
     for _ in range(2):
         got = ops.conv2d_bf16(xs, cw, stride, **kw)
         assert tuple((got if f32_out else got.t).shape[:2]) == ((N, 32) if f32_out else (N, 4))
@@ -612,7 +620,14 @@ C1X1_CASES = [
     # spans several images)
     ("layer5 first 256->512 @8x32, two slices", 256, 512, 8, 32, True, 261),
     ("128->256 @4x16: a tile spans several images", 128, 256, 4, 16, False, 36),
+    # 256 input channels on a map that is neither 8x32 nor 4x16 (128-pixel tiles; 256 -> 512 as two slices): see C1X1_WIDE_FIRST
+    ("256->256 @8x16, 2-3 trips", 256, 256, 8, 16, True, 530),
+    ("256->512 @8x16, two slices", 256, 512, 8, 16, True, 261),
 ]
+# The layers with 256 input channels go, on the backbone's own 8x32 maps, to the wide-tile kernel's 1x1 form first, with or without
+# tuning bit 1: on these two cases this test used to compare that kernel with itself.  They now name the kernel they reach and
+# compare it with the tiled kernel (bits 1 and 2); the two 8x16 cases above are where the blocked 1x1 kernel runs such layers.
+C1X1_WIDE_FIRST = {"layer4 256->256 @8x32, 2-3 trips", "layer5 first 256->512 @8x32, two slices"}
 
 
 @pytest.mark.parametrize("name,cin,cout,H,W,relu,N", C1X1_CASES, ids=[c[0] for c in C1X1_CASES])
@@ -627,11 +642,14 @@ def test_conv1x1_blocked_kernel_is_the_tiled_kernel_bit_for_bit(cuda, name, cin,
     b = torch.randn((cout,), generator=g) * 0.2
     xb = ops.Blocked.from_nchw(x.to(cuda))
     cw = ops.prep_conv_weight_bf16(w.to(cuda), conv_bias=b.to(cuda))
+    family, bits = ("wide1", 6) if name in C1X1_WIDE_FIRST else ("blk1", 2)
     try:
-        _lib.lib().tpspp_conv_set_tuning(2)
+        _lib.lib().tpspp_conv_set_tuning(bits)
+        assert ops.conv2d_bf16_route([xb], cw, 1, relu=relu, out_blocked=True).startswith("tiled 1x1 ")
         want = ops.conv2d_bf16([xb], cw, 1, relu=relu, out_blocked=True).t.view(torch.int16).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route([xb], cw, 1, relu=relu, out_blocked=True).startswith(family + " 1x1 ")
     for _ in range(2):
         got = ops.conv2d_bf16([xb], cw, 1, relu=relu, out_blocked=True)
         assert torch.equal(got.t.view(torch.int16), want)
@@ -734,9 +752,11 @@ def test_conv1x1_wide_kernel_is_the_tiled_kernel_bit_for_bit(cuda, name, cin, co
     raw = (lambda o: o.view(torch.int32)) if f32_out else (lambda o: o.t.view(torch.int16))
     try:
         _lib.lib().tpspp_conv_set_tuning(6)
+        assert ops.conv2d_bf16_route([xb], cw, 1, relu=relu, **kw).startswith("tiled 1x1 ")
         want = raw(ops.conv2d_bf16([xb], cw, 1, relu=relu, **kw)).clone()
     finally:
         _lib.lib().tpspp_conv_set_tuning(0)
+    assert ops.conv2d_bf16_route([xb], cw, 1, relu=relu, **kw).startswith("wide1 1x1 ")
     for _ in range(2):
         got = ops.conv2d_bf16([xb], cw, 1, relu=relu, **kw)
         assert torch.equal(raw(got), want)

@@ -21,7 +21,7 @@ EXCLUDED = {
     "tpspp_plane_ln_bwd_workspace_floats": _QUERY, "tpspp_cbam_bwd_workspace_floats": _QUERY,
     "tpspp_bn_stats_workspace_floats": _QUERY, "tpspp_bn_bwd_reduce_workspace_floats": _QUERY,
     "tpspp_warp_bwd_workspace_floats": _QUERY, "tpspp_nrtr_encoder_workspace": _QUERY, "tpspp_nrtr_decoder_workspace": _QUERY,
-    "tpspp_nrtr_decoder_route": _QUERY, "tpspp_warp_bwd_route": _QUERY,
+    "tpspp_nrtr_decoder_route": _QUERY, "tpspp_warp_bwd_route": _QUERY, "tpspp_conv2d_bf16_route": _QUERY,
     "tpspp_conv_set_tuning": _KNOB, "tpspp_warp_set_tuning": _KNOB, "tpspp_warp_set_trace": _KNOB,
     "tpspp_head_set_trace": _KNOB, "tpspp_warp_bwd_set_accumulator": _KNOB,
     "tpspp_table_mirror_symmetry": _HOST,

@@ -19,6 +19,7 @@ ALLOWED = {
         "WarpPlan.__init__": "tpspp_warp_plan_create ends in the handle's address, not in a stream; keeps the run functions",
         "WarpPlan.run": "the headline's hot path: one foreign call on a stored handle, the status read only when non-zero",
         "conv2d_route": "host-side query of a host array whose negative result is an error code for _lib.check",
+        "conv2d_bf16_route": "host-side query of pointers (alignment only) whose negative result is an error code for _lib.check",
         "nrtr_decoder_route": "host-side query of a host pointer table whose negative result is an error code",
         "warp_backward_route": "host-side query of pointers (alignment only) whose non-zero status is an error for _lib.check",
         "crnn_lstm_plan": "host-side query (through _query) whose negative result is an error code for _lib.check",

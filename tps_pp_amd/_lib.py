@@ -36,6 +36,7 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_conv2d_fwd": ([_f, _f, _i, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
     "tpspp_conv2d_route": ([_f] + [_i] * 11, _i),
     "tpspp_conv2d_bf16_fwd": ([_f, _f, _i, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i, _f], _i),
+    "tpspp_conv2d_bf16_route": ([_f, _f, _i, _f, _f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _i], _i),
     "tpspp_conv2d_bwd_data": ([_f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f], _i),
     "tpspp_conv2d_bwd_weight_workspace_floats": ([_f, _i, _i, _i, _i, _i, _i, _i], ctypes.c_size_t),
     "tpspp_conv2d_bwd_weight": ([_f, _f, _i, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, ctypes.c_size_t,

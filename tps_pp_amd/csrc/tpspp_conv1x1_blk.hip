@@ -123,30 +123,27 @@ conv1x1_blk_kernel(const BParams P, int ntiles, int cg_total, int cg0)
     }
 }
 
+// wavefronts per workgroup of an (NT, NKS) instantiation: accumulators + operands per lane
+constexpr int blk_nw(int NT, int NKS) { return (NT * 16 + NKS * 4 > 160) ? 4 : 8; }
+constexpr size_t blk_lds(int NT, int NKS) { return (size_t)((NT + 1) / 2) * 64 * NKS * 2 * 16 + (size_t)NT * 32 * 4; }
+
 // SL: launches per layer, each owning NT x 32 of the SL x NT x 32 output channels
 template <int NT, int NKS, int SL = 1>
-bool launch(const BParams& P0, hipStream_t st)
+int launch(const BParams& P0, hipStream_t st)
 {
-    constexpr int NW = (NT * 16 + NKS * 4 > 160) ? 4 : 8;      // accumulators + operands per lane
-    const size_t lds = (size_t)((NT + 1) / 2) * 64 * NKS * 2 * 16 + (size_t)NT * 32 * 4;
-    if (lds > (size_t)kMaxLds) return false;
-    const int HW = P0.Ho * P0.Wo;
-    const long total = (long)P0.N * HW;
-    if (HW % 32 || total % (NW * 32)) return false;
-    const long nt = total / (NW * 32);
-    if (nt <= 0 || nt > 0x3fffffffL) return false;
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-        (void)hipGetLastError();
-        return false;
-    }
+    constexpr int NW = blk_nw(NT, NKS);
+    constexpr size_t lds = blk_lds(NT, NKS);
+    static_assert(lds <= (size_t)kMaxLds, "the weight does not fit");
+    const long nt = (long)P0.N * P0.Ho * P0.Wo / (NW * 32);
+    int ncu = 0;
+    if (int rc = tpspp::cu_count("blk1", ncu)) return rc;
     static bool attr[tpspp::kMaxDevices] = {};
     if (tpspp::first_use_on_device(attr)) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_blk_kernel<NT, NKS, NW>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds) != hipSuccess) {
             (void)hipGetLastError();
-            return false;
+            return tpspp::fail(TPSPP_EIO, "tpspp_conv2d_bf16_fwd(blk1 nt%d nks%d): the device refused %d bytes of dynamic LDS", NT, NKS,
+                               kMaxLds);
         }
     }
     for (int sl = 0; sl < SL; ++sl) {
@@ -157,30 +154,48 @@ bool launch(const BParams& P0, hipStream_t st)
         hipLaunchKernelGGL((conv1x1_blk_kernel<NT, NKS, NW>), dim3((unsigned)(nt < ncu ? nt : ncu)), dim3(NW * 64), lds, st, P, (int)nt,
                            SL * NT * 4, sl * NT * 4);
     }
-    return true;
+    return TPSPP_OK;
 }
+
+// the instantiations: (Cin, Cout, slices).  256 -> 512 is the first layer of the last stage: the weight of an output-channel slice
+// in LDS, one launch per slice (132 -> 82 us at batch 512).  Not 512 -> 512 on the 4x16 maps: four slices of 131 KB for ONE
+// 128-pixel tile per workgroup measured 74 us against the tiled kernel's 55.  (32 -> 32 / 64, round 6: the backbone's first
+// stage, when its maps are blocked)
+#define TPSPP_BLK1(X) X(64, 64, 1) X(64, 128, 1) X(128, 128, 1) X(128, 256, 1) X(256, 256, 1) X(32, 32, 1) X(32, 64, 1) X(256, 512, 2)
 
 }  // namespace
 
 namespace tpspp {
 
-// true when the kernel took the layer: 1x1, stride 1, one blocked bf16 source at its own resolution, blocked bf16 output,
-// bias / ReLU only, Cin and Cout in {64, 128, 256} (+ 256 -> 512 as output-channel slices), whole 32 NW-pixel tiles
-// of the flat (image, pixel) index
-bool conv1x1_blk_launch(const BParams& P, hipStream_t st)
+// true when the kernel takes the layer: 1x1, stride 1, one blocked bf16 source at its own resolution, blocked bf16 output,
+// bias / ReLU only, 16-byte aligned source, output and weight, a (Cin, Cout) of TPSPP_BLK1, whole 32 NW-pixel tiles of the flat
+// (image, pixel) index
+bool conv1x1_blk_route(const BParams& P, BRoute& R)
 {
     if (P.nsrc != 1 || P.src[0].f32 != 2 || P.out_f32 != 2 || P.res || P.res_mode || P.post_scale || P.relu > 1) return false;
     if (P.src[0].lh || P.src[0].lw || P.src[0].H != P.Ho || P.src[0].W != P.Wo || P.src[0].C != P.Cin) return false;
     if ((reinterpret_cast<size_t>(P.src[0].p) | reinterpret_cast<size_t>(P.out) | reinterpret_cast<size_t>(P.wt)) & 15) return false;
-#define TPSPP_C1(CI, CO) if (P.Cin == CI && P.Cout == CO) return launch<CO / 32, CI / 16>(P, st);
-    TPSPP_C1(64, 64) TPSPP_C1(64, 128) TPSPP_C1(128, 128) TPSPP_C1(128, 256) TPSPP_C1(256, 256)
-    TPSPP_C1(32, 32) TPSPP_C1(32, 64)             // (round 6: the backbone's first stage, when its maps are blocked)
+    R = BRoute{};
+    R.family = kBfBlk1; R.kh = 1; R.sh = R.sw = 1;
+#define TPSPP_C1(CI, CO, SL) if (P.Cin == CI && P.Cout == CO) { R.nt = CO / 32 / SL; R.nks = CI / 16; R.sl = SL; }
+    TPSPP_BLK1(TPSPP_C1)
 #undef TPSPP_C1
-    // the first layer of the last stage: the weight of an output-channel slice in LDS, one launch per slice (132 -> 82 us at batch
-    // 512).  Not 512 -> 512 on the 4x16 maps: four slices of 131 KB for ONE 128-pixel tile per workgroup measured 74 us against the
-    // tiled kernel's 55.
-    if (P.Cin == 256 && P.Cout == 512) return launch<8, 16, 2>(P, st);
-    return false;
+    if (!R.nt) return false;
+    R.nw = blk_nw(R.nt, R.nks);
+    if (blk_lds(R.nt, R.nks) > (size_t)kMaxLds) return false;
+    const int HW = P.Ho * P.Wo;
+    const long total = (long)P.N * HW;
+    if (HW % 32 || total % (R.nw * 32)) return false;
+    const long nt = total / (R.nw * 32);
+    return nt > 0 && nt <= 0x3fffffffL;
+}
+
+int conv1x1_blk_launch(const BParams& P, const BRoute& R, hipStream_t st)
+{
+#define TPSPP_C1(CI, CO, SL) if (R.nt == CO / 32 / SL && R.nks == CI / 16 && R.sl == SL) return launch<CO / 32 / SL, CI / 16, SL>(P, st);
+    TPSPP_BLK1(TPSPP_C1)
+#undef TPSPP_C1
+    return fail(TPSPP_EINVAL, "tpspp_conv2d_bf16_fwd(blk1): the route names no kernel");
 }
 
 }  // namespace tpspp

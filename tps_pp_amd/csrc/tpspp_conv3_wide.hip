@@ -304,20 +304,38 @@ conv3_wide_kernel(const BParams P)
 }
 
 template <int TH, int TW, int NI, int KS = 3>
-bool launch_w(const BParams& P, hipStream_t st)
+bool launch_w(const BParams& P, const tpspp::BRoute& R, hipStream_t st)
 {
+    if (R.th != TH || R.tw != TW || R.ni != NI) return false;
     const long groups = (P.N + NI - 1) / NI;
     const long blocks = ((groups + 7) / 8) * 8 * (P.Cout / 128);     // (see the kernel: block -> (image group, channel tile))
-    if (blocks > 0x7fffffffL) return false;
     const dim3 grid((unsigned)blocks);
     constexpr int PD = WK<KS>::PD;
-    if (P.out_f32 == 1) {
-        if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 3, PD, KS>), grid, dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 2, PD, KS>), grid, dim3(256), 0, st, P);
-        return true;
+    switch (R.epi) {
+    case 0: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 0, PD, KS>), grid, dim3(256), 0, st, P); return true;
+    case 1: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, PD, KS>), grid, dim3(256), 0, st, P); return true;
+    case 2: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 2, PD, KS>), grid, dim3(256), 0, st, P); return true;
+    case 3: hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 3, PD, KS>), grid, dim3(256), 0, st, P); return true;
     }
-    if (P.res_mode) hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 1, PD, KS>), grid, dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((conv3_wide_kernel<TH, TW, NI, 0, PD, KS>), grid, dim3(256), 0, st, P);
+    return false;
+}
+
+// what the 3x3 and the 1x1 form share: ONE blocked source at full resolution, Cout a multiple of 128, blocked bf16 or fp32 NCHW
+// output (+ blocked bf16 residual), bias / ReLU only, 8x32 or 4x16 maps, a grid that fits
+bool wide_route(const BParams& P, int family, tpspp::BRoute& R)
+{
+    if (P.nsrc != 1 || P.src[0].f32 != 2 || P.src[0].lh || P.src[0].lw || (P.out_f32 != 2 && P.out_f32 != 1) || P.post_scale || P.relu > 1) return false;
+    if ((P.Cout % 128) || P.src[0].C != P.Cin) return false;
+    if (P.res_mode && P.res_f32 != 2) return false;
+    if (P.Ho != P.Hi || P.Wo != P.Wi) return false;
+    R = tpspp::BRoute{};
+    R.family = family; R.kh = family == tpspp::kBfWide3 ? 3 : 1; R.sh = R.sw = 1; R.nf = 4;
+    if (P.Ho == 8 && P.Wo == 32) { R.th = 8; R.tw = 32; R.ni = 1; }
+    else if (P.Ho == 4 && P.Wo == 16) { R.th = 4; R.tw = 16; R.ni = 4; }
+    else return false;
+    const long groups = ((long)P.N + R.ni - 1) / R.ni;
+    if (((groups + 7) / 8) * 8 * (P.Cout / 128) > 0x7fffffffL) return false;
+    R.epi = (P.out_f32 == 1 ? 2 : 0) + (P.res_mode ? 1 : 0);   // 0 blocked, 1 blocked + residual, 2 fp32 NCHW, 3 fp32 NCHW + residual
     return true;
 }
 
@@ -325,17 +343,12 @@ bool launch_w(const BParams& P, hipStream_t st)
 
 namespace tpspp {
 
-// true when the wide-tile kernel took the layer: 3x3 stride 1, plain bf16, ONE blocked source at full resolution, Cin a multiple
+// true when the wide-tile kernel takes the layer: 3x3 stride 1, plain bf16, ONE blocked source at full resolution, Cin a multiple
 // of 32, Cout a multiple of 128, blocked bf16 or fp32 NCHW output (+ blocked bf16 residual), bias / ReLU only, 8x32 or 4x16 maps
-bool conv3_wide_launch(const BParams& P, hipStream_t st)
+bool conv3_wide_route(const BParams& P, BRoute& R)
 {
-    if (P.nsrc != 1 || P.src[0].f32 != 2 || P.src[0].lh || P.src[0].lw || (P.out_f32 != 2 && P.out_f32 != 1) || P.post_scale || P.relu > 1) return false;
-    if ((P.Cin % 32) || (P.Cout % 128) || P.Cin < 64 || P.src[0].C != P.Cin) return false;
-    if (P.res_mode && P.res_f32 != 2) return false;
-    if (P.Ho != P.Hi || P.Wo != P.Wi) return false;
-    if (P.Ho == 8 && P.Wo == 32) return launch_w<8, 32, 1>(P, st);
-    if (P.Ho == 4 && P.Wo == 16) return launch_w<4, 16, 4>(P, st);
-    return false;
+    if ((P.Cin % 32) || P.Cin < 64) return false;
+    return wide_route(P, kBfWide3, R);
 }
 
 // the same kernel for 1x1 layers (KS = 1: 32-channel chunks, no halo), where it measures faster than the blocked 1x1 kernel
@@ -343,15 +356,19 @@ bool conv3_wide_launch(const BParams& P, hipStream_t st)
 // 256 -> 512 133 (tiled) / 82 (sliced) -> 53 us on 8x32 maps, 512 -> 512 on 4x16 maps 55 (tiled) -> 25 us at batch 512; the
 // 128-channel layers measure the same on both and stay where they were.  Stride 1, one blocked source, Cin a multiple of 64,
 // Cout a multiple of 128, blocked bf16 or fp32 NCHW output
-bool conv1x1_wide_launch(const BParams& P, hipStream_t st)
+bool conv1x1_wide_route(const BParams& P, BRoute& R)
 {
-    if (P.nsrc != 1 || P.src[0].f32 != 2 || P.src[0].lh || P.src[0].lw || (P.out_f32 != 2 && P.out_f32 != 1) || P.post_scale || P.relu > 1) return false;
-    if ((P.Cin % 64) || (P.Cout % 128) || P.src[0].C != P.Cin || P.Cin < 256) return false;
-    if (P.res_mode && P.res_f32 != 2) return false;
-    if (P.Ho != P.Hi || P.Wo != P.Wi) return false;
-    if (P.Ho == 8 && P.Wo == 32) return launch_w<8, 32, 1, 1>(P, st);
-    if (P.Ho == 4 && P.Wo == 16) return launch_w<4, 16, 4, 1>(P, st);
-    return false;
+    if ((P.Cin % 64) || P.Cin < 256) return false;
+    return wide_route(P, kBfWide1, R);
+}
+
+int conv_wide_launch(const BParams& P, const BRoute& R, hipStream_t st)
+{
+    bool ok;
+    if (R.family == kBfWide3) ok = launch_w<8, 32, 1>(P, R, st) || launch_w<4, 16, 4>(P, R, st);
+    else ok = launch_w<8, 32, 1, 1>(P, R, st) || launch_w<4, 16, 4, 1>(P, R, st);
+    TPSPP_REQUIRE(ok, "tpspp_conv2d_bf16_fwd(%s): the route names no kernel", R.family == kBfWide3 ? "wide3" : "wide1");
+    return TPSPP_OK;
 }
 
 }  // namespace tpspp

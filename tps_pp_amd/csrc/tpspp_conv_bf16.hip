@@ -34,12 +34,15 @@ TPSPP_EXPORT int tpspp_conv_bf16_chunk_channels(int kernel_size)
     return kernel_size == 1 ? kKC1 : kKC3;
 }
 
-TPSPP_EXPORT int tpspp_conv2d_bf16_fwd(const void* const* src_ptrs, const int* src_dims, int nsrc,
-                                       const void* weight_arranged, const float* bias,
-                                       const void* residual, int residual_f32,
-                                       const float* post_scale, const float* post_shift,
-                                       int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
-                                       void* out, int out_f32, int Ho, int Wo, int split3, tpspp_stream_t stream)
+namespace {
+
+// ---- the route: which kernel a call takes, as a value (as tpspp_conv.hip does it for the fp32 kernels) --------------------------
+// bf16_shape() holds every argument check and fills the kernels' parameter block, bf16_route() every dispatch condition (shapes,
+// alignments, N and the tuning bits: no device), launch_route() one launch per family.  tpspp_conv2d_bf16_fwd and
+// tpspp_conv2d_bf16_route go through the same two functions; the forward then launches what the route names.
+int bf16_shape(const void* const* src_ptrs, const int* src_dims, int nsrc, const void* weight_arranged, const float* bias,
+               const void* residual, int residual_f32, const float* post_scale, const float* post_shift, int res_mode, int relu,
+               int N, int Cout, int KH, int KW, int sh, int sw, void* out, int out_f32, int Ho, int Wo, int split3, BParams& P)
 {
     TPSPP_REQUIRE(src_ptrs && src_dims && weight_arranged && out, "tpspp_conv2d_bf16_fwd: null pointer");
     TPSPP_REQUIRE(nsrc >= 1 && nsrc <= 3, "tpspp_conv2d_bf16_fwd: 1..3 sources");
@@ -50,7 +53,6 @@ TPSPP_EXPORT int tpspp_conv2d_bf16_fwd(const void* const* src_ptrs, const int* s
     TPSPP_REQUIRE(relu >= 0 && relu <= 2, "tpspp_conv2d_bf16_fwd: activation code must be 0 (none), 1 (ReLU) or 2 (GELU)");
     TPSPP_REQUIRE((post_scale == nullptr) == (post_shift == nullptr),
                   "tpspp_conv2d_bf16_fwd: post_scale/post_shift come together");
-    BParams P;
     P.nsrc = nsrc;
     const int KC = (KH == 1) ? kKC1 : kKC3;
     int cin = 0, Hi = -1, Wi = -1;
@@ -88,36 +90,96 @@ TPSPP_EXPORT int tpspp_conv2d_bf16_fwd(const void* const* src_ptrs, const int* s
     P.post_scale = post_scale; P.post_shift = post_shift;
     P.relu = relu; P.res_mode = res_mode;
     P.nchunks = (cin + KC - 1) / KC;
-    if (N == 0) return TPSPP_OK;
     TPSPP_REQUIRE((long)N * ((Cout + BN - 1) / BN) <= 65535, "tpspp_conv2d_bf16_fwd: grid too large");
-    hipStream_t st = tpspp::as_stream(stream);
-    bool ok = false;
+    return TPSPP_OK;
+}
+
+// The order is the dispatcher's preference; every specialised kernel gives the tiled kernel's bits.
+int bf16_route(const BParams& P, int KH, int KW, int sh, int sw, bool split3, BRoute& R)
+{
+    const bool s11 = sh == 1 && sw == 1;
+    const bool wide = !split3 && s11 && !tpspp::g_conv_bf16_no_wide, persist = !split3 && !tpspp::g_conv_bf16_no_persist;
     // the wide blocked 3x3 layers of the backbone (>= 128 output channels on 8x32 / 4x16 maps): 128 x 64 wavefront tiles, weights
-    // streamed into registers (tpspp_conv3_wide.hip); bit-identical results
-    if (!split3 && KH == 3 && sh == 1 && sw == 1 && !tpspp::g_conv_bf16_no_wide && tpspp::conv3_wide_launch(P, st))
-        return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
-    // the backbone's stem (3 fp32 channels -> 32 bf16 NCHW): tpspp_conv_stem.hip; bit-identical results
-    if (!split3 && KH == 3 && sh == 1 && sw == 1 && !tpspp::g_conv_bf16_no_wide && tpspp::conv_stem_launch(P, st))
-        return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
-    // the big blocked 3x3 layers: persistent, LDS-DMA-fed kernel (tpspp_conv_bf16_persist.hip); bit-identical results
-    if (!split3 && KH == 3 && !tpspp::g_conv_bf16_no_persist && tpspp::conv_bf16_persist_launch(P, sh, sw, st))
-        return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
+    // streamed into registers (tpspp_conv3_wide.hip)
+    if (wide && KH == 3 && tpspp::conv3_wide_route(P, R)) return TPSPP_OK;
+    // the backbone's stem (3 fp32 channels -> 32 bf16 NCHW): tpspp_conv_stem.hip
+    if (wide && KH == 3 && tpspp::conv_stem_route(P, R)) return TPSPP_OK;
+    // the big blocked 3x3 layers: persistent, LDS-DMA-fed kernel (tpspp_conv_bf16_persist.hip)
+    if (persist && KH == 3 && tpspp::conv_bf16_persist_route(P, sh, sw, R)) return TPSPP_OK;
     // 1x1 layers with >= 256 input channels between blocked maps: the wide-tile kernel's 1x1 form (tpspp_conv3_wide.hip)
-    if (!split3 && KH == 1 && sh == 1 && sw == 1 && !tpspp::g_conv_bf16_no_wide && tpspp::conv1x1_wide_launch(P, st))
-        return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
+    if (wide && KH == 1 && tpspp::conv1x1_wide_route(P, R)) return TPSPP_OK;
     // 1x1 layers between blocked maps (the backbone's BasicBlocks): every activation read once, the weight in LDS
-    // (tpspp_conv1x1_blk.hip); bit-identical results
-    if (!split3 && KH == 1 && sh == 1 && sw == 1 && !tpspp::g_conv_bf16_no_persist && tpspp::conv1x1_blk_launch(P, st))
-        return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
-    if (split3) {
-        ok = tpspp::conv_bf16x3_launch(P, KH, sh, sw, st);
-    } else {
-        if (KH == 1 && sh == 1 && sw == 1)      ok = launch_by_shape<1, 1, 1, kKC1, false>(P, st);
-        else if (KH == 1 && sh == 2 && sw == 2) ok = launch_by_shape<1, 2, 2, kKC1, false>(P, st);
-        else if (KH == 3 && sh == 1 && sw == 1) ok = launch_by_shape<3, 1, 1, kKC3, false>(P, st);
-        else if (KH == 3 && sh == 2 && sw == 2) ok = launch_by_shape<3, 2, 2, kKC3, false>(P, st);
-        else if (KH == 3 && sh == 2 && sw == 1) ok = launch_by_shape<3, 2, 1, kKC3, false>(P, st);
+    // (tpspp_conv1x1_blk.hip)
+    if (persist && KH == 1 && s11 && tpspp::conv1x1_blk_route(P, R)) return TPSPP_OK;
+    TPSPP_REQUIRE(tiled_route(P, KH, sh, sw, split3, R),
+                  "tpspp_conv2d_bf16_fwd: no kernel for a %dx%d kernel with stride (%d,%d)", KH, KW, sh, sw);
+    return TPSPP_OK;
+}
+
+int launch_route(const BParams& P, const BRoute& R, hipStream_t st)
+{
+    switch (R.family) {
+    case tpspp::kBfWide3: case tpspp::kBfWide1: return tpspp::conv_wide_launch(P, R, st);
+    case tpspp::kBfStem: return tpspp::conv_stem_launch(P, R, st);
+    case tpspp::kBfPersist: return tpspp::conv_bf16_persist_launch(P, R, st);
+    case tpspp::kBfBlk1: return tpspp::conv1x1_blk_launch(P, R, st);
+    case tpspp::kBfTiledX3: return tpspp::conv_bf16x3_launch(P, R, st);
     }
-    TPSPP_REQUIRE(ok, "tpspp_conv2d_bf16_fwd: no kernel for a %dx%d kernel with stride (%d,%d)", KH, KW, sh, sw);
-    return tpspp::check_launch("tpspp_conv2d_bf16_fwd");
+    bool ok = false;
+    if (R.kh == 1 && R.sh == 1 && R.sw == 1)      ok = launch_by_shape<1, 1, 1, kKC1, false>(P, R, st);
+    else if (R.kh == 1 && R.sh == 2 && R.sw == 2) ok = launch_by_shape<1, 2, 2, kKC1, false>(P, R, st);
+    else if (R.kh == 3 && R.sh == 1 && R.sw == 1) ok = launch_by_shape<3, 1, 1, kKC3, false>(P, R, st);
+    else if (R.kh == 3 && R.sh == 2 && R.sw == 2) ok = launch_by_shape<3, 2, 2, kKC3, false>(P, R, st);
+    else if (R.kh == 3 && R.sh == 2 && R.sw == 1) ok = launch_by_shape<3, 2, 1, kKC3, false>(P, R, st);
+    TPSPP_REQUIRE(ok, "tpspp_conv2d_bf16_fwd(tiled): the route names no kernel");
+    return TPSPP_OK;
+}
+
+constexpr int kRouteN0 = 8;   // the batch an empty one is judged as: a whole number of every kernel's tiles (include/tpspp.h)
+
+}  // namespace
+
+TPSPP_EXPORT int tpspp_conv2d_bf16_route(const void* const* src_ptrs, const int* src_dims, int nsrc,
+                                         const void* weight_arranged, const float* bias,
+                                         const void* residual, int residual_f32,
+                                         const float* post_scale, const float* post_shift,
+                                         int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
+                                         void* out, int out_f32, int Ho, int Wo, int split3)
+{
+    BParams P;
+    BRoute R;
+    if (int rc = bf16_shape(src_ptrs, src_dims, nsrc, weight_arranged, bias, residual, residual_f32, post_scale, post_shift, res_mode,
+                            relu, N, Cout, KH, KW, sh, sw, out, out_f32, Ho, Wo, split3, P)) return rc;
+    if (N == 0) P.N = kRouteN0;
+    if (int rc = bf16_route(P, KH, KW, sh, sw, split3 != 0, R)) return rc;
+    int code = R.family | ((R.kh == 3) << 3) | (R.sh << 4) | (R.sw << 6);
+    if (R.family == tpspp::kBfBlk1) return code | (R.nt << 8) | (R.nks << 12) | (R.sl << 17) | (R.nw << 19);
+    code |= (R.th << 8) | (R.tw << 13) | (R.ni << 22) | ((R.nf - 1) << 25);
+    switch (R.family) {
+    case tpspp::kBfTiled: case tpspp::kBfTiledX3: code |= (R.wide << 27) | ((R.nb - 1) << 28); break;
+    case tpspp::kBfPersist: code |= (R.wres << 27) | (R.epi << 28) | ((R.cpb - 1) << 30); break;
+    case tpspp::kBfWide3: case tpspp::kBfWide1: code |= R.epi << 27; break;
+    case tpspp::kBfStem: code |= R.blocked << 27; break;
+    }
+    return code;
+}
+
+TPSPP_EXPORT int tpspp_conv2d_bf16_fwd(const void* const* src_ptrs, const int* src_dims, int nsrc,
+                                       const void* weight_arranged, const float* bias,
+                                       const void* residual, int residual_f32,
+                                       const float* post_scale, const float* post_shift,
+                                       int res_mode, int relu, int N, int Cout, int KH, int KW, int sh, int sw,
+                                       void* out, int out_f32, int Ho, int Wo, int split3, tpspp_stream_t stream)
+{
+    BParams P;
+    BRoute R;
+    if (int rc = bf16_shape(src_ptrs, src_dims, nsrc, weight_arranged, bias, residual, residual_f32, post_scale, post_shift, res_mode,
+                            relu, N, Cout, KH, KW, sh, sw, out, out_f32, Ho, Wo, split3, P)) return rc;
+    if (N == 0) return TPSPP_OK;
+    if (int rc = bf16_route(P, KH, KW, sh, sw, split3 != 0, R)) return rc;
+    if (int rc = launch_route(P, R, tpspp::as_stream(stream))) return rc;
+    static const char* const what[] = {"tpspp_conv2d_bf16_fwd(tiled)", "tpspp_conv2d_bf16_fwd(tiled-x3)", "tpspp_conv2d_bf16_fwd(wide3)",
+                                       "tpspp_conv2d_bf16_fwd(wide1)", "tpspp_conv2d_bf16_fwd(stem)", "tpspp_conv2d_bf16_fwd(persist)",
+                                       "tpspp_conv2d_bf16_fwd(blk1)"};
+    return tpspp::check_launch(what[R.family]);
 }

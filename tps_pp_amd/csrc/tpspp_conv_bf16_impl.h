@@ -33,12 +33,43 @@ struct BParams {
     int nchunks;
 };
 
+// ---- the route: which kernel a call takes, as a value ------------------------------------------------------------------
+// Every family has a pure `*_route` (shapes, alignments and N in, BRoute out; false = "not mine"; no device is touched) and
+// a `*_launch` that launches exactly what the BRoute names.  tpspp_conv2d_bf16_fwd and tpspp_conv2d_bf16_route go through
+// the same bf16_route(), so a test can name the kernel it is about to run.
+enum { kBfTiled = 0, kBfTiledX3 = 1, kBfWide3 = 2, kBfWide1 = 3, kBfStem = 4, kBfPersist = 5, kBfBlk1 = 6 };
+
+struct BRoute {
+    int family;               // kBf*
+    int kh, sh, sw;           // kernel size (1 | 3) and strides of the instantiation
+    int th, tw, ni, nf;       // output tile, images per tile, 32-pixel fragments per wavefront (not blk1)
+    int wide, nb;             // tiled: wide staging (0 | 1), 32-channel accumulators per fragment (1 | 2)
+    int wres, cpb;            // persist: resident weight (0 | 1), chunks per ring slot (1 | 2)
+    int epi;                  // persist: 0 blocked, 1 blocked + blocked residual, 2 fp32 NCHW; wide3 / wide1: 0..3
+    int blocked;              // stem: blocked output (0 | 1)
+    int nt, nks, sl, nw;      // blk1: 32-channel output tiles, 16-channel k steps, slices (launches), wavefronts
+};
+
+// the CU count of the current device, which sizes the grids of the persistent kernels (never a route decision)
+inline int cu_count(const char* route, int& ncu)
+{
+    int dev = 0;
+    ncu = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        ncu <= 0) {
+        (void)hipGetLastError();
+        return fail(TPSPP_EIO, "tpspp_conv2d_bf16_fwd(%s): cannot query the device's CU count", route);
+    }
+    return TPSPP_OK;
+}
+
 }  // namespace tpspp
 
 namespace {
 
 using tpspp::BSrc;
 using tpspp::BParams;
+using tpspp::BRoute;
 
 constexpr int kThreads = 256;
 constexpr int BM = 256;       // output pixels per workgroup (NF = 2 fragments per wavefront; 128 with NF = 1)
@@ -536,87 +567,121 @@ inline bool wide_staging_applies(const BParams& P)
     return true;
 }
 
-template <int KH, int SH, int SW, int TH, int TW, int NI, int KC, bool X3, int NF = 2>
-void launch_b(const BParams& P, hipStream_t st)
+// the tile a (kernel, stride, split) form takes for an output map: the one table the route and the launch share.
+// A: 128-pixel tiles -- stride 2 (the patch holds 4x the output positions: half the LDS and registers, twice the workgroups)
+// and the three-term split's 3x3 (two 256-pixel workgroups would need 2 x 62 KB of LDS); B: everything else
+inline void tiled_tile(int KH, int SH, bool X3, int Ho, int Wo, tpspp::BRoute& R)
 {
+    auto tile = [&](int th, int tw, int ni, int nf) { R.th = th; R.tw = tw; R.ni = ni; R.nf = nf; };
+    if (KH == 3 && (SH == 2 || X3)) {
+        if (Wo > 64)      tile(1, 128, 1, 1);
+        else if (Wo > 32) tile(2, 64, 1, 1);
+        else if (Wo > 16) tile(4, 32, 1, 1);
+        else if (Ho > 4)  tile(8, 16, 1, 1);
+        else if (Ho > 2)  tile(4, 16, 2, 1);
+        else              tile(2, 16, 4, 1);
+        return;
+    }
+    if (Ho == 1 && Wo > 128) tile(1, 256, 1, 2);          // a row of tokens
+    else if (Wo > 64) tile(2, 128, 1, 2);
+    else if (Wo > 32) tile(4, 64, 1, 2);
+    else if (Wo > 16) {
+        // 3x3 on 32-wide maps (backbone layer 3-4): 128-pixel tiles measured 3 % faster (64-wide maps: neutral)
+        if (KH == 3) tile(4, 32, 1, 1);
+        else tile(8, 32, 1, 2);
+    }
+    else if (Ho > 8)  tile(16, 16, 1, 2);
+    else if (Ho > 4)  tile(8, 16, 2, 2);
+    else if (Ho > 2)  tile(4, 16, 2, 1);                   // 128-pixel tiles: 2 images
+    else              tile(2, 16, 4, 1);                   //                  4 images
+}
+
+// the tiled route of a call: plain bf16 or the three-term split; false when no instantiation has these strides
+inline bool tiled_route(const BParams& P, int KH, int sh, int sw, bool X3, tpspp::BRoute& R)
+{
+    if (!((KH == 1 && ((sh == 1 && sw == 1) || (sh == 2 && sw == 2))) || (KH == 3 && (sh == 1 || sh == 2) && (sw == 1 || sw == 2) && sh >= sw)))
+        return false;
+    R = tpspp::BRoute{};
+    R.family = X3 ? tpspp::kBfTiledX3 : tpspp::kBfTiled;
+    R.kh = KH; R.sh = sh; R.sw = sw;
+    tiled_tile(KH, sh, X3, P.Ho, P.Wo, R);
+    // (stride 2: the dense patch is 4x the output, the raw tile and its transposition cost more than the gather saves:
+    //  127 -> 154 us on the 32x128 -> 16x64 layers)
+    R.wide = KH == 3 && sh == 1 && sw == 1 && !X3 && (R.tw % 16) == 0 && wide_staging_applies(P);
+    R.nb = (X3 && P.Cout <= 32) ? 1 : 2;                      // one accumulator per fragment (see the kernel, NB)
+    return true;
+}
+
+template <int KH, int SH, int SW, int TH, int TW, int NI, int KC, bool X3, int NF = 2>
+bool launch_b(const BParams& P, const tpspp::BRoute& R, hipStream_t st)
+{
+    if (R.th != TH || R.tw != TW || R.ni != NI || R.nf != NF) return false;
     const int ctiles = (P.Cout + BN - 1) / BN;
     const dim3 grid((unsigned)((P.Wo + TW - 1) / TW), (unsigned)((P.Ho + TH - 1) / TH),
                     (unsigned)(((P.N + NI - 1) / NI) * ctiles));
-    // (stride 2: the dense patch is 4x the output, the raw tile and its transposition cost more than the gather saves:
-    //  127 -> 154 us on the 32x128 -> 16x64 layers)
     if constexpr (KH == 3 && SH == 1 && SW == 1 && !X3 && (TW % 16) == 0) {
-        if (wide_staging_applies(P)) {
+        if (R.wide) {
             hipLaunchKernelGGL((conv_tiled_bf16_kernel<KH, SH, SW, TH, TW, NI, KC, X3, NF, true>), grid, dim3(kThreads), 0, st, P);
-            return;
+            return true;
         }
     }
+    if (R.wide) return false;
     if constexpr (X3) {
-        if (P.Cout <= 32) {                                   // one accumulator per fragment (see the kernel, NB)
+        if (R.nb == 1) {
             hipLaunchKernelGGL((conv_tiled_bf16_kernel<KH, SH, SW, TH, TW, NI, KC, X3, NF, false, 1>), grid, dim3(kThreads), 0, st, P);
-            return;
+            return true;
         }
     }
+    if (R.nb != 2) return false;
     hipLaunchKernelGGL((conv_tiled_bf16_kernel<KH, SH, SW, TH, TW, NI, KC, X3, NF>), grid, dim3(kThreads), 0, st, P);
+    return true;
 }
 
 constexpr int kKC3 = 16;      // channels per chunk, 3x3 kernels
 constexpr int kKC1 = 32;      // channels per chunk, 1x1 kernels
 
-// picks the tile by output width / height; false when no instantiation fits
+// launches the tile the route names (`tiled_tile` is the table); false when this form has no such instantiation
 template <int KH, int SH, int SW, int KC, bool X3>
-bool launch_by_shape(const BParams& P, hipStream_t st)
+bool launch_by_shape(const BParams& P, const tpspp::BRoute& R, hipStream_t st)
 {
-    if constexpr (KH == 3 && SH == 2) {
-        // stride 2: the patch holds 4x the output positions -- 128-pixel tiles (half the LDS and registers, twice the
-        // workgroups); the same for the maps of at most 8 rows of 16, where 256-pixel tiles start too few workgroups
-        if (P.Wo > 64)      launch_b<KH, SH, SW, 1, 128, 1, KC, X3, 1>(P, st);
-        else if (P.Wo > 32) launch_b<KH, SH, SW, 2, 64, 1, KC, X3, 1>(P, st);
-        else if (P.Wo > 16) launch_b<KH, SH, SW, 4, 32, 1, KC, X3, 1>(P, st);
-        else if (P.Ho > 4)  launch_b<KH, SH, SW, 8, 16, 1, KC, X3, 1>(P, st);
-        else if (P.Ho > 2)  launch_b<KH, SH, SW, 4, 16, 2, KC, X3, 1>(P, st);
-        else                launch_b<KH, SH, SW, 2, 16, 4, KC, X3, 1>(P, st);
-        return true;
-    } else if constexpr (KH == 3 && X3) {
-        // three-term split, stride 1: 128-pixel tiles as well (two 256-pixel workgroups would need 2 x 62 KB of LDS)
-        if (P.Wo > 64)      launch_b<KH, SH, SW, 1, 128, 1, KC, X3, 1>(P, st);
-        else if (P.Wo > 32) launch_b<KH, SH, SW, 2, 64, 1, KC, X3, 1>(P, st);
-        else if (P.Wo > 16) launch_b<KH, SH, SW, 4, 32, 1, KC, X3, 1>(P, st);
-        else if (P.Ho > 4)  launch_b<KH, SH, SW, 8, 16, 1, KC, X3, 1>(P, st);
-        else if (P.Ho > 2)  launch_b<KH, SH, SW, 4, 16, 2, KC, X3, 1>(P, st);
-        else                launch_b<KH, SH, SW, 2, 16, 4, KC, X3, 1>(P, st);
-        return true;
+    if constexpr (KH == 3 && (SH == 2 || X3)) {
+        return launch_b<KH, SH, SW, 1, 128, 1, KC, X3, 1>(P, R, st) || launch_b<KH, SH, SW, 2, 64, 1, KC, X3, 1>(P, R, st) ||
+               launch_b<KH, SH, SW, 4, 32, 1, KC, X3, 1>(P, R, st) || launch_b<KH, SH, SW, 8, 16, 1, KC, X3, 1>(P, R, st) ||
+               launch_b<KH, SH, SW, 4, 16, 2, KC, X3, 1>(P, R, st) || launch_b<KH, SH, SW, 2, 16, 4, KC, X3, 1>(P, R, st);
     } else {
-        if (P.Ho == 1 && P.Wo > 128) launch_b<KH, SH, SW, 1, 256, 1, KC, X3>(P, st);   // a row of tokens
-        else if (P.Wo > 64) launch_b<KH, SH, SW, 2, 128, 1, KC, X3>(P, st);
-        else if (P.Wo > 32) launch_b<KH, SH, SW, 4, 64, 1, KC, X3>(P, st);
-        else if (P.Wo > 16) {
-            // 3x3 on 32-wide maps (backbone layer 3-4): 128-pixel tiles measured 3 % faster (64-wide maps: neutral)
-            if constexpr (KH == 3) launch_b<KH, SH, SW, 4, 32, 1, KC, X3, 1>(P, st);
-            else launch_b<KH, SH, SW, 8, 32, 1, KC, X3>(P, st);
+        if constexpr (KH == 3) {
+            if (launch_b<KH, SH, SW, 4, 32, 1, KC, X3, 1>(P, R, st)) return true;
+        } else {
+            if (launch_b<KH, SH, SW, 8, 32, 1, KC, X3>(P, R, st)) return true;
         }
-        else if (P.Ho > 8)  launch_b<KH, SH, SW, 16, 16, 1, KC, X3>(P, st);
-        else if (P.Ho > 4)  launch_b<KH, SH, SW, 8, 16, 2, KC, X3>(P, st);
-        else if (P.Ho > 2)  launch_b<KH, SH, SW, 4, 16, 2, KC, X3, 1>(P, st);          // 128-pixel tiles: 2 images
-        else                launch_b<KH, SH, SW, 2, 16, 4, KC, X3, 1>(P, st);          //                  4 images
-        return true;
+        return launch_b<KH, SH, SW, 1, 256, 1, KC, X3>(P, R, st) || launch_b<KH, SH, SW, 2, 128, 1, KC, X3>(P, R, st) ||
+               launch_b<KH, SH, SW, 4, 64, 1, KC, X3>(P, R, st) || launch_b<KH, SH, SW, 16, 16, 1, KC, X3>(P, R, st) ||
+               launch_b<KH, SH, SW, 8, 16, 2, KC, X3>(P, R, st) || launch_b<KH, SH, SW, 4, 16, 2, KC, X3, 1>(P, R, st) ||
+               launch_b<KH, SH, SW, 2, 16, 4, KC, X3, 1>(P, R, st);
     }
 }
 
 }  // namespace
 
 namespace tpspp {
-// defined in tpspp_conv_bf16x3.hip: dispatches the split3 instantiations; false when no kernel fits
-bool conv_bf16x3_launch(const BParams& P, int KH, int sh, int sw, hipStream_t st);
-// defined in tpspp_conv_bf16_persist.hip: the persistent kernel for blocked 3x3 layers; false when it does not apply
-bool conv_bf16_persist_launch(const BParams& P, int sh, int sw, hipStream_t st);
-// defined in tpspp_conv1x1_blk.hip: 1x1 layers between blocked maps; false when it does not apply
-bool conv1x1_blk_launch(const BParams& P, hipStream_t st);
-// defined in tpspp_conv3_wide.hip: 3x3 stride-1 layers with >= 128 output channels between blocked maps (128 x 64 wavefront
-// tiles, weights streamed from L2 into registers); false when it does not apply
-bool conv3_wide_launch(const BParams& P, hipStream_t st);
-bool conv1x1_wide_launch(const BParams& P, hipStream_t st);   // the same kernel for the 1x1 layers with >= 256 input channels
-// defined in tpspp_conv_stem.hip: the backbone's stem (3x3, <= 3 fp32 input channels -> 32 bf16 NCHW); false when it does not apply
-bool conv_stem_launch(const BParams& P, hipStream_t st);
+// Each `*_route` is pure (no device; false = the family does not take the layer), each `*_launch` launches what the route names:
+// TPSPP_OK, or an error that names the route (a refused LDS opt-in, a failed CU-count query, a route value with no kernel).
+// tpspp_conv_bf16x3.hip: the split3 instantiations of the tiled kernel
+int conv_bf16x3_launch(const BParams& P, const BRoute& R, hipStream_t st);
+// tpspp_conv_bf16_persist.hip: the persistent kernel for blocked 3x3 layers
+bool conv_bf16_persist_route(const BParams& P, int sh, int sw, BRoute& R);
+int conv_bf16_persist_launch(const BParams& P, const BRoute& R, hipStream_t st);
+// tpspp_conv1x1_blk.hip: 1x1 layers between blocked maps
+bool conv1x1_blk_route(const BParams& P, BRoute& R);
+int conv1x1_blk_launch(const BParams& P, const BRoute& R, hipStream_t st);
+// tpspp_conv3_wide.hip: 3x3 stride-1 layers with >= 128 output channels between blocked maps (128 x 64 wavefront tiles, weights
+// streamed from L2 into registers), and the same kernel for the 1x1 layers with >= 256 input channels
+bool conv3_wide_route(const BParams& P, BRoute& R);
+bool conv1x1_wide_route(const BParams& P, BRoute& R);
+int conv_wide_launch(const BParams& P, const BRoute& R, hipStream_t st);
+// tpspp_conv_stem.hip: the backbone's stem (3x3, <= 3 fp32 input channels -> 32 bf16 NCHW or blocked)
+bool conv_stem_route(const BParams& P, BRoute& R);
+int conv_stem_launch(const BParams& P, const BRoute& R, hipStream_t st);
 extern int g_conv_bf16_no_persist;           // tpspp_conv_set_tuning bit 1
 extern int g_conv_bf16_no_wide;              // tpspp_conv_set_tuning bit 2
 }  // namespace tpspp

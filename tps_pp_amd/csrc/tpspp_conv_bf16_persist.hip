@@ -421,63 +421,63 @@ conv3_blk_persist_kernel(const BParams P, int ntx, int nty, int ntiles)
     }
 }
 
+constexpr const char* kNoKernel = "tpspp_conv2d_bf16_fwd(persist): the route names no kernel";
+
 template <typename K>
-bool launch_k(K kfn, bool (&attr_done)[tpspp::kMaxDevices], int grid, int threads, size_t lds, hipStream_t st, const BParams& P,
-              int ntx, int nty, int nt)
+int launch_k(K kfn, bool (&attr_done)[tpspp::kMaxDevices], int grid, int threads, size_t lds, hipStream_t st, const BParams& P,
+             int ntx, int nty, int nt)
 {
     if (tpspp::first_use_on_device(attr_done)) {             // per device: the opt-in is a property of the loaded code object
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, kPLdsMax) != hipSuccess) {
             (void)hipGetLastError();
-            return false;
+            return tpspp::fail(TPSPP_EIO, "tpspp_conv2d_bf16_fwd(persist): the device refused %d bytes of dynamic LDS", kPLdsMax);
         }
     }
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(threads), lds, st, P, ntx, nty, nt);
-    return true;
+    return TPSPP_OK;
 }
 
 template <int SH, int SW, int TH, int TW, int NF, bool WRES, int EPI, int CPB>
-bool launch_pc(const BParams& P, hipStream_t st)
+int launch_pc(const BParams& P, hipStream_t st)
 {
     using Cfg = PCfg<SH, SW, TH, TW, WRES, CPB>;
+    // a resident weight is at most 4 chunks (Cin <= 64), which NBFIT leaves room for: the ring always fits
+    static_assert((kFlagUnits + Cfg::NB * Cfg::BUF + (WRES ? 4 * kPSlab : 0)) * 16 <= kPLdsMax, "the ring does not fit");
     const int ntx = P.Wo / TW, nty = P.Ho / TH;
     const long nt = (long)P.N * ntx * nty;
-    if (nt > 0x3fffffffL) return false;
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-        (void)hipGetLastError();
-        return false;
-    }
+    int ncu = 0;
+    if (int rc = tpspp::cu_count("persist", ncu)) return rc;
     const long pairs = (nt + 1) / 2;                         // a workgroup works on two tiles at a time
     const int grid = (int)(pairs < ncu ? pairs : ncu);
     const size_t lds = (size_t)(kFlagUnits + Cfg::NB * Cfg::BUF + (WRES ? P.nchunks * kPSlab : 0)) * 16;   // (BUF: see PCfg)
-    if (lds > (size_t)kPLdsMax) return false;
+    TPSPP_REQUIRE(lds <= (size_t)kPLdsMax, "tpspp_conv2d_bf16_fwd(persist): %zu bytes of LDS", lds);
     static bool attr[tpspp::kMaxDevices] = {};
     return launch_k(conv3_blk_persist_kernel<SH, SW, TH, TW, NF, WRES, EPI, CPB>, attr, grid,
                     (2 * PTeam<TH, TW, NF>::W + PLoaders<NF, PTeam<TH, TW, NF>::W>::N) * kWave, lds, st, P, ntx, nty, (int)nt);
 }
 
 // resident weight and an even chunk count: two chunks (32 channels) per ring slot -- half the flag hand-offs, 72 matrix
-// instructions per wait
+// instructions per wait -- where a ring of three such slots fits
+template <int SH, int SW, int TH, int TW>
+constexpr bool kCpb2Fits = PCfg<SH, SW, TH, TW, true, 2>::NBFIT >= 3;
+
 template <int SH, int SW, int TH, int TW, int NF, bool WRES, int EPI>
-bool launch_pe(const BParams& P, hipStream_t st)
+int launch_pe(const BParams& P, const tpspp::BRoute& R, hipStream_t st)
 {
-    if constexpr (WRES && PCfg<SH, SW, TH, TW, true, 2>::NBFIT >= 3) {
-        if (P.nchunks % 2 == 0) return launch_pc<SH, SW, TH, TW, NF, WRES, EPI, 2>(P, st);
+    if constexpr (WRES && kCpb2Fits<SH, SW, TH, TW>) {
+        if (R.cpb == 2) return launch_pc<SH, SW, TH, TW, NF, WRES, EPI, 2>(P, st);
     }
+    if (R.cpb != 1) return tpspp::fail(TPSPP_EINVAL, "%s", kNoKernel);
     return launch_pc<SH, SW, TH, TW, NF, WRES, EPI, 1>(P, st);
 }
 
 template <int SH, int SW, int TH, int TW, int NF>
-bool launch_p(const BParams& P, hipStream_t st)
+int launch_p(const BParams& P, const tpspp::BRoute& R, hipStream_t st)
 {
-    if (P.Ho % TH || P.Wo % TW) return false;
-    const int epi = P.out_f32 == 1 ? (P.res_mode ? -1 : 2) : (P.res_mode ? (P.res_f32 == 2 ? 1 : -1) : 0);
-    const bool wres = P.Cin <= 64;
-    if (epi == 0) return wres ? launch_pe<SH, SW, TH, TW, NF, true, 0>(P, st) : launch_pe<SH, SW, TH, TW, NF, false, 0>(P, st);
-    if (epi == 1) return wres ? launch_pe<SH, SW, TH, TW, NF, true, 1>(P, st) : launch_pe<SH, SW, TH, TW, NF, false, 1>(P, st);
-    if (epi == 2) return wres ? launch_pe<SH, SW, TH, TW, NF, true, 2>(P, st) : launch_pe<SH, SW, TH, TW, NF, false, 2>(P, st);
-    return false;
+    if (R.epi == 0) return R.wres ? launch_pe<SH, SW, TH, TW, NF, true, 0>(P, R, st) : launch_pe<SH, SW, TH, TW, NF, false, 0>(P, R, st);
+    if (R.epi == 1) return R.wres ? launch_pe<SH, SW, TH, TW, NF, true, 1>(P, R, st) : launch_pe<SH, SW, TH, TW, NF, false, 1>(P, R, st);
+    if (R.epi == 2) return R.wres ? launch_pe<SH, SW, TH, TW, NF, true, 2>(P, R, st) : launch_pe<SH, SW, TH, TW, NF, false, 2>(P, R, st);
+    return tpspp::fail(TPSPP_EINVAL, "%s", kNoKernel);
 }
 
 }  // namespace
@@ -491,18 +491,43 @@ extern "C" __attribute__((visibility("default"))) int tpspp_debug_conv_trace(lon
 
 namespace tpspp {
 
-// true when the persistent kernel took the layer: 3x3, plain bf16, every source blocked, 64 (or 32) output channels, blocked
+// true when the persistent kernel takes the layer: 3x3, plain bf16, every source blocked, 64 (or 32) output channels, blocked
 // output (+ blocked residual) or fp32-NCHW output, bias / ReLU only, whole tiles
-bool conv_bf16_persist_launch(const BParams& P, int sh, int sw, hipStream_t st)
+bool conv_bf16_persist_route(const BParams& P, int sh, int sw, BRoute& R)
 {
     if ((P.Cout != 64 && P.Cout != 32) || (P.Cin % kPKC) || P.post_scale || P.relu > 1) return false;
     if (P.out_f32 != 2 && P.out_f32 != 1) return false;
     for (int i = 0; i < P.nsrc; ++i)
         if (P.src[i].f32 != 2 || (P.src[i].C % kPKC)) return false;
+    R = BRoute{};
+    R.family = kBfPersist; R.kh = 3; R.sh = sh; R.sw = sw; R.ni = 1;
+    bool cpb2;
     // 64-wide maps: 4 x 64 (stride 2: 2 x 64) tiles; 32-wide maps (the 8x32 level of the MSFA): 8 x 32 (4 x 32)
-    if (sh == 1 && sw == 1) return P.Wo % 64 == 0 ? launch_p<1, 1, 4, 64, 2>(P, st) : launch_p<1, 1, 8, 32, 2>(P, st);
-    if (sh == 2 && sw == 2) return P.Wo % 64 == 0 ? launch_p<2, 2, 2, 64, 1>(P, st) : launch_p<2, 2, 4, 32, 1>(P, st);
-    return false;
+    if (sh == 1 && sw == 1) {
+        R.nf = 2;
+        if (P.Wo % 64 == 0) { R.th = 4; R.tw = 64; cpb2 = kCpb2Fits<1, 1, 4, 64>; }
+        else { R.th = 8; R.tw = 32; cpb2 = kCpb2Fits<1, 1, 8, 32>; }
+    } else if (sh == 2 && sw == 2) {
+        R.nf = 1;
+        if (P.Wo % 64 == 0) { R.th = 2; R.tw = 64; cpb2 = kCpb2Fits<2, 2, 2, 64>; }
+        else { R.th = 4; R.tw = 32; cpb2 = kCpb2Fits<2, 2, 4, 32>; }
+    } else return false;
+    if (P.Ho % R.th || P.Wo % R.tw) return false;
+    R.epi = P.out_f32 == 1 ? (P.res_mode ? -1 : 2) : (P.res_mode ? (P.res_f32 == 2 ? 1 : -1) : 0);
+    if (R.epi < 0) return false;
+    R.wres = P.Cin <= 64;
+    R.cpb = (R.wres && cpb2 && P.nchunks % 2 == 0) ? 2 : 1;
+    if ((long)P.N * (P.Wo / R.tw) * (P.Ho / R.th) > 0x3fffffffL) return false;
+    return true;
+}
+
+int conv_bf16_persist_launch(const BParams& P, const BRoute& R, hipStream_t st)
+{
+    if (R.sh == 1 && R.th == 4 && R.tw == 64) return launch_p<1, 1, 4, 64, 2>(P, R, st);
+    if (R.sh == 1 && R.th == 8 && R.tw == 32) return launch_p<1, 1, 8, 32, 2>(P, R, st);
+    if (R.sh == 2 && R.th == 2 && R.tw == 64) return launch_p<2, 2, 2, 64, 1>(P, R, st);
+    if (R.sh == 2 && R.th == 4 && R.tw == 32) return launch_p<2, 2, 4, 32, 1>(P, R, st);
+    return tpspp::fail(TPSPP_EINVAL, "%s", kNoKernel);
 }
 
 }  // namespace tpspp

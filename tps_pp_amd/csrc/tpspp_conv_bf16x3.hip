@@ -3,14 +3,16 @@
 
 namespace tpspp {
 
-bool conv_bf16x3_launch(const BParams& P, int KH, int sh, int sw, hipStream_t st)
+int conv_bf16x3_launch(const BParams& P, const BRoute& R, hipStream_t st)
 {
-    if (KH == 1 && sh == 1 && sw == 1) return launch_by_shape<1, 1, 1, kKC1, true>(P, st);
-    if (KH == 1 && sh == 2 && sw == 2) return launch_by_shape<1, 2, 2, kKC1, true>(P, st);
-    if (KH == 3 && sh == 1 && sw == 1) return launch_by_shape<3, 1, 1, kKC3, true>(P, st);
-    if (KH == 3 && sh == 2 && sw == 2) return launch_by_shape<3, 2, 2, kKC3, true>(P, st);
-    if (KH == 3 && sh == 2 && sw == 1) return launch_by_shape<3, 2, 1, kKC3, true>(P, st);
-    return false;
+    bool ok = false;
+    if (R.kh == 1 && R.sh == 1 && R.sw == 1)      ok = launch_by_shape<1, 1, 1, kKC1, true>(P, R, st);
+    else if (R.kh == 1 && R.sh == 2 && R.sw == 2) ok = launch_by_shape<1, 2, 2, kKC1, true>(P, R, st);
+    else if (R.kh == 3 && R.sh == 1 && R.sw == 1) ok = launch_by_shape<3, 1, 1, kKC3, true>(P, R, st);
+    else if (R.kh == 3 && R.sh == 2 && R.sw == 2) ok = launch_by_shape<3, 2, 2, kKC3, true>(P, R, st);
+    else if (R.kh == 3 && R.sh == 2 && R.sw == 1) ok = launch_by_shape<3, 2, 1, kKC3, true>(P, R, st);
+    TPSPP_REQUIRE(ok, "tpspp_conv2d_bf16_fwd(tiled-x3): the route names no kernel");
+    return TPSPP_OK;
 }
 
 }  // namespace tpspp

@@ -181,9 +181,9 @@ conv_stem_bf16_kernel(const StemP P)
 
 namespace tpspp {
 
-// true when the stem kernel took the layer: 3x3 stride 1, ONE fp32 NCHW source of <= 3 channels at its own resolution, 32 output
-// channels, bf16 NCHW or blocked bf16 output, bias / ReLU only, 128 columns, rows a multiple of 4
-bool conv_stem_launch(const BParams& P, hipStream_t st)
+// true when the stem kernel takes the layer: 3x3 stride 1, ONE fp32 NCHW source of <= 3 channels at its own resolution, 32 output
+// channels, bf16 NCHW or blocked bf16 output, bias / ReLU only, 128 columns, rows a multiple of 4, 16-byte aligned output and weight
+bool conv_stem_route(const BParams& P, BRoute& R)
 {
     if (P.nsrc != 1 || P.src[0].f32 != 1 || P.src[0].lh || P.src[0].lw || (P.out_f32 != 0 && P.out_f32 != 2) || P.res_mode || P.post_scale ||
         P.relu > 1) return false;
@@ -191,18 +191,24 @@ bool conv_stem_launch(const BParams& P, hipStream_t st)
     if ((reinterpret_cast<size_t>(P.out) | reinterpret_cast<size_t>(P.wt)) & 15) return false;
     const long nt = (long)P.N * (P.Ho / kSTH);
     if (nt <= 0 || nt > 0x3fffffffL) return false;
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-        (void)hipGetLastError();
-        return false;
-    }
+    R = BRoute{};
+    R.family = kBfStem; R.kh = 3; R.sh = R.sw = 1; R.th = kSTH; R.tw = kSW; R.ni = 1; R.nf = 4;
+    R.blocked = P.out_f32 == 2;
+    return true;
+}
+
+int conv_stem_launch(const BParams& P, const BRoute& R, hipStream_t st)
+{
+    int ncu = 0;
+    if (int rc = cu_count("stem", ncu)) return rc;
+    const long nt = (long)P.N * (P.Ho / kSTH);
     StemP S;
     S.in = reinterpret_cast<const float*>(P.src[0].p); S.wt = P.wt; S.bias = P.bias; S.out = reinterpret_cast<unsigned short*>(P.out);
     S.N = P.N; S.C = P.Cin; S.H = P.Ho; S.ntiles = (int)nt; S.relu = P.relu;
     const long slots = (long)ncu * 3;
-    if (P.out_f32 == 2) hipLaunchKernelGGL(conv_stem_bf16_kernel<true>, dim3((unsigned)(nt < slots ? nt : slots)), dim3(256), 0, st, S);
+    if (R.blocked) hipLaunchKernelGGL(conv_stem_bf16_kernel<true>, dim3((unsigned)(nt < slots ? nt : slots)), dim3(256), 0, st, S);
     else hipLaunchKernelGGL(conv_stem_bf16_kernel<false>, dim3((unsigned)(nt < slots ? nt : slots)), dim3(256), 0, st, S);
-    return true;
+    return TPSPP_OK;
 }
 
 }  // namespace tpspp

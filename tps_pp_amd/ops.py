@@ -816,6 +816,69 @@ def conv2d_bf16(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, o
     return out
 
 
+_ROUTE_BASE = 1 << 20         # stands for the (512-byte aligned) start of an allocation where a tensor has no memory
+
+
+def _route_ptr(t):
+    """The address `conv2d_bf16_route` judges a tensor by: its own, or, for a tensor without memory ("meta"), its offset
+    from an aligned allocation.  None stays NULL."""
+    if t is None:
+        return None
+    t = t.t if isinstance(t, Blocked) else t
+    return t.data_ptr() or _ROUTE_BASE + t.storage_offset() * t.element_size()
+
+
+_BF16_FAMILIES = ("tiled", "tiled-x3", "wide3", "wide1", "stem", "persist", "blk1")
+
+
+def conv2d_bf16_route_name(code):
+    """The packed code of `tpspp_conv2d_bf16_route` (include/tpspp.h) as a string: `tiled 3x3 s1x1 4x64 ni1 nf2 wide1 nb2`,
+    `tiled-x3 1x1 s2x2 4x16 ni2 nf1 wide0 nb1`, `persist 3x3 s2x2 2x64 ni1 nf1 wres1 epi0 cpb2`, `wide3 3x3 s1x1 8x32 ni1 nf4
+    epi1`, `wide1 1x1 s1x1 4x16 ni4 nf4 epi3`, `stem 3x3 s1x1 4x128 ni1 nf4 blocked0`, `blk1 1x1 s1x1 nt2 nks4 sl1 nw8`."""
+    fam = _BF16_FAMILIES[code & 7]
+    k = 3 if (code >> 3) & 1 else 1
+    head = f"{fam} {k}x{k} s{(code >> 4) & 3}x{(code >> 6) & 3}"
+    if fam == "blk1":
+        return f"{head} nt{(code >> 8) & 15} nks{(code >> 12) & 31} sl{(code >> 17) & 3} nw{(code >> 19) & 15}"
+    head += f" {(code >> 8) & 31}x{(code >> 13) & 511} ni{(code >> 22) & 7} nf{((code >> 25) & 3) + 1}"
+    if fam in ("tiled", "tiled-x3"):
+        return f"{head} wide{(code >> 27) & 1} nb{((code >> 28) & 1) + 1}"
+    if fam == "persist":
+        return f"{head} wres{(code >> 27) & 1} epi{(code >> 28) & 3} cpb{((code >> 30) & 1) + 1}"
+    if fam == "stem":
+        return f"{head} blocked{(code >> 27) & 1}"
+    return f"{head} epi{(code >> 27) & 3}"
+
+
+def conv2d_bf16_route(srcs, cw, stride=(1, 1), relu=True, residual=None, res_mode=0, out_dtype=torch.bfloat16, out_blocked=False):
+    """The kernel `conv2d_bf16` launches for the same arguments (`tpspp_conv2d_bf16_route`), as a string
+    (`conv2d_bf16_route_name`).  A host-side query: shapes, layouts and the 16-byte alignment of sources and weight are all
+    it reads, so the tensors may live on any device, "meta" included (judged as their offset into an aligned allocation);
+    the output is judged as `conv2d_bf16` allocates it, aligned.  What `conv2d_bf16` refuses raises the same error."""
+    ents = _split_sources(srcs)
+    if not 1 <= len(ents) <= 3:
+        raise ValueError("conv2d_bf16_route: 1..3 sources")
+    dims = []
+    for t, uh, uw in ents:
+        dims += [t.shape[1], t.shape[2], t.shape[3], int(uh), int(uw), _layout_code(t)]
+    N = ents[0][0].shape[0]
+    if sum(dims[0::6]) != cw.cin:
+        raise ValueError("conv2d_bf16_route: source channels != Cin of the weight")
+    sh, sw, Ho, Wo = _conv_out_size(dims[1] * dims[3], dims[2] * dims[4], cw.kernel, stride)
+    if (residual is None) != (res_mode == 0):
+        raise ValueError("conv2d_bf16_route: residual / res_mode")
+    res_code = 0 if residual is None else _layout_code(residual)
+    out_code = (3 if cw.x3 else 2) if out_blocked else int(out_dtype == torch.float32)
+    ptrs = (ctypes.c_void_p * len(ents))(*[_route_ptr(t) for t, _, _ in ents])
+    code = _lib.lib().tpspp_conv2d_bf16_route(
+        _vp(ptrs), _vp(_int_array(dims)), len(ents), _route_ptr(cw.arranged), _route_ptr(cw.bias), _route_ptr(residual), res_code,
+        _route_ptr(cw.post_scale), _route_ptr(cw.post_shift), int(res_mode), int(relu), N, cw.cout, cw.kernel, cw.kernel, sh, sw,
+        _ROUTE_BASE, out_code, Ho, Wo, int(cw.x3))
+    if code < 0:
+        _lib.check(code, "tpspp_conv2d_bf16_route")
+    return conv2d_bf16_route_name(code)
+
+
 class _BlkView:
     """What the shared source checks look at (logical shape, device, is_cuda, dtype, data_ptr) for a `Blocked` map."""
 
