@@ -58,7 +58,8 @@ extern "C" {
                                (still 12): the CRNN decoder's reduced-precision kernels tpspp_crnn_lstm_bf16_fwd and tpspp_mm_bf16,
                                   bound by name;
                                (still 12): their training counterparts tpspp_crnn_lstm_bf16_train_fwd, tpspp_crnn_lstm_bf16_bwd and
-                                  tpspp_linear_bwd_weight_bf16 (+ _workspace_floats), bound by name */
+                                  tpspp_linear_bwd_weight_bf16 (+ _workspace_floats), bound by name;
+                               (still 12): the VGG's training kernel tpspp_crnn_maxpool_bwd, bound by name */
 
 #define TPSPP_OK        0
 #define TPSPP_EINVAL  (-22)  /* bad argument (null pointer, non-positive size, unsupported shape) */
@@ -660,6 +661,30 @@ int tpspp_bn_pool2x2_bwd_data(const float* dp, const float* z, const float* mean
  * replaces: the autograd of nn.AdaptiveAvgPool2d(1)   preprocessor/tps_preprocessor.py:101-128
  */
 int tpspp_global_avgpool_bwd(const float* g, int N, int C, int H, int W, float* dx, tpspp_stream_t stream);
+
+/*
+ * VeryDeepVgg's training graph (VeryDeepVgg.set_vgg_train_backend("hip"); tpspp_crnn_pool_train.hip): the backward of
+ * tpspp_crnn_maxpool_fwd (tpspp_crnn.h), with the backward of the in-place ReLU in front of the pool folded in.
+ *   y  (N, C, H, W):   the pool's input (the convolution's ReLU output);
+ *   dp (N, C, Ho, Wo): the gradient of the pool's output;
+ *   dy (N, C, H, W):   the gradient of y, every element written.
+ * Geometry and argument rules are tpspp_crnn_maxpool_fwd's (kh, kw, sh, sw >= 1; 0 <= ph <= kh / 2, 0 <= pw <= kw / 2; Ho, Wo
+ * must equal the formula; -22 otherwise), and N C H W <= 2^31 - 1.  No index map is read: each window of y is scanned again
+ * with the forward's rule, row by row from -inf, `v > m || v != v` replaces m, and the window SELECTS the last element
+ * that did: the first of equal maxima, the last of several NaNs, never padding; a window in which nothing replaced m (all
+ * of it -inf) selects its first element inside the map.  This is the routing of ATen's max_pool2d backward.
+ *   dy[h][w] = sum of dp[oh][ow] over the windows (oh, ow) that contain (h, w) and selected it,
+ * gathered by the element's own lane in ascending (oh, ow), starting from +0: no atomics, no workspace, bitwise
+ * reproducible.  relu_mask = 1: an element with !(y > 0) -- zero, negative or NaN -- receives +0 (the ReLU's backward;
+ * the convolution backward then runs with relu = 0 and does not read y); relu_mask = 0: the pool's backward alone.  An
+ * element that no window covers (an odd last row or column at 2x2 / stride 2) receives +0.
+ * Two forms: kernel 2x2, stride 2, no padding, W % 4 == 0, y and dy 16-byte and dp 8-byte aligned: a lane owns two windows
+ * side by side (16-byte loads and stores); anything else: one lane per element of y.  Both give the same bits.
+ * N == 0 returns 0 and launches nothing.
+ * replaces: the autograd of nn.MaxPool2d and of the nn.ReLU(True) in front of it   backbones/very_deep_vgg.py:39-60
+ */
+int tpspp_crnn_maxpool_bwd(const float* dp, const float* y, int relu_mask, int N, int C, int H, int W, int kh, int kw, int sh,
+                           int sw, int ph, int pw, float* dy, int Ho, int Wo, tpspp_stream_t stream);
 
 
 

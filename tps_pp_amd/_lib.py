@@ -70,6 +70,7 @@ _SIGNATURES = {"tpspp.h": {
     "tpspp_bn_pool2x2_bwd_reduce": ([_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _f, _f, _f, ctypes.c_size_t, _f], _i),
     "tpspp_bn_pool2x2_bwd_data": ([_f, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _f, _f], _i),
     "tpspp_global_avgpool_bwd": ([_f, _i, _i, _i, _i, _f, _f], _i),
+    "tpspp_crnn_maxpool_bwd": ([_f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i, _f], _i),
     "tpspp_conv_bf16_chunk_channels": ([_i], _i),
     "tpspp_dgab_fwd": ([_f] * 16 + [_i, _i, _f], _i),
     "tpspp_dgab_bf16_fwd": ([_f] * 16 + [_i, _i, _i, _f], _i),

@@ -12,8 +12,11 @@ that requires grad, runs the PyTorch composition of the same layers (`nn.LSTM`, 
 trains through PyTorch plus the HIP warp forward and backward of the preprocessor.  `CRNNDecoder.set_train_backend("hip")`
 (and `CTCLoss.set_train_backend("hip")`, tps_pp_amd/losses.py) moves the recurrent half of that training graph onto the
 kernels of include/tpspp_crnn_train.h, and `TPSPreprocessor.set_train_backend("hip")` the preprocessor's localisation network
-onto HIP kernels (`CRNNNet.set_train_backend("torch", preprocessor="hip", decoder="hip", loss="hip")` sets all three); the VGG,
-with its pools, keeps training on PyTorch.  `CRNNDecoder.set_train_compute_dtype("bf16x3")` (opt-in) runs that HIP training
+onto HIP kernels (`CRNNNet.set_train_backend("torch", preprocessor="hip", decoder="hip", loss="hip")` sets all three).
+`VeryDeepVgg.set_vgg_train_backend("hip")` (`CRNNNet.set_vgg_train_backend`; opt-in, default "torch") moves the VGG with its
+pools: the convolutions on the fp32 forward / backward kernels, the max-pools' backward with the ReLU mask on
+`tpspp_crnn_maxpool_bwd` (include/tpspp.h), the BatchNorms on the backbone's training kernels.
+`CRNNDecoder.set_train_compute_dtype("bf16x3")` (opt-in) runs that HIP training
 graph's LSTM layers on the bf16 matrix cores, forward and backward, as three-term splits (include/tpspp.h).
 
 Precision: `set_compute_dtype` of the recogniser (None | "bf16x3" | torch.bfloat16) means for the VGG what it means for
@@ -142,8 +145,49 @@ class VeryDeepVgg(nn.Module):
                              f"{x.shape[2]} rows")
         return ops.conv2d([x], cw, (2, 1), True)[:, :, :, :x.shape[3] - 1]
 
+    VGG_TRAIN_BACKENDS = ("torch", "hip")
+    vgg_train_backend = "torch"                     # `set_vgg_train_backend`; a plain attribute, never in the state_dict
+
+    def set_vgg_train_backend(self, mode):
+        """Which kernels the graph-building forward (`.train()`, or an input that carries gradients) runs on: "torch"
+        (default) -- the PyTorch composition `self.cnn`; "hip" -- `_forward_train_hip`, HIP forward and backward for every
+        layer, taken for a GPU tensor (a host tensor keeps the PyTorch composition).  `leaky_relu=True` refuses "hip": the
+        kernels' activation is ReLU.  Touches neither the parameters, the buffers, the state_dict nor the eval path.
+        (Its own name, not `set_train_backend`: the recogniser's `set_train_backend(..., backbone=)` tells a backbone with
+        a HIP training path by that attribute, and goes on refusing this one.)"""
+        if mode not in self.VGG_TRAIN_BACKENDS:
+            raise ValueError(f'set_vgg_train_backend: "torch" or "hip", got {mode!r}')
+        if mode == "hip" and self.leaky_relu:
+            raise ValueError('set_vgg_train_backend: "hip" needs leaky_relu=False (the HIP kernels\' activation is ReLU)')
+        self.vgg_train_backend = mode
+        return self
+
+    def _train_weights(self):
+        """The forward's weight layouts for `_forward_train_hip` (no BatchNorm folded; conv6 with its zero-extended 3x3
+        kernel: `ops.conv6_extend`), cached and rebuilt on the device when a parameter changes (`_prepared`)."""
+        convs = [getattr(self.cnn, f"conv{i}") for i in range(7)]
+        return prepared(self, "vgg_train", convs, lambda: [
+            ops.conv6_extend(c) if i == 6 else ops.prep_conv_weight_device(c.weight, c.bias) for i, c in enumerate(convs)])
+
+    def _forward_train_hip(self, x):
+        """`self.cnn` on the HIP kernels inside an autograd graph (`set_vgg_train_backend("hip")`): conv0, conv1, conv3 and
+        conv5 with the pool behind them each one `ops.conv_relu_pool_autograd` (the pool's backward carries the ReLU mask:
+        `tpspp_crnn_maxpool_bwd`), conv2 and conv4 `ops.bn_stem_autograd`, conv6 `ops.conv6_bn_autograd`.  Exact fp32
+        whatever `compute_dtype` says; every BatchNorm follows its own mode."""
+        c, cw = self.cnn, self._train_weights()
+        x = x.float().contiguous()
+        x = ops.conv_relu_pool_autograd(x, c.conv0, 2, 2, 0, cw[0], name="conv0")
+        x = ops.conv_relu_pool_autograd(x, c.conv1, 2, 2, 0, cw[1], name="conv1")
+        x = ops.bn_stem_autograd(x, c.conv2, c.batchnorm2, cw[2], name="conv2")
+        x = ops.conv_relu_pool_autograd(x, c.conv3, (2, 2), (2, 1), (0, 1), cw[3], name="conv3")
+        x = ops.bn_stem_autograd(x, c.conv4, c.batchnorm4, cw[4], name="conv4")
+        x = ops.conv_relu_pool_autograd(x, c.conv5, (2, 2), (2, 1), (0, 1), cw[5], name="conv5")
+        return ops.conv6_bn_autograd(x, c.conv6, c.batchnorm6, cw[6], name="conv6")
+
     def forward(self, x):
         if self.leaky_relu or not _hip_path(self, x):
+            if self.vgg_train_backend == "hip" and not self.leaky_relu and x.is_cuda:
+                return self._forward_train_hip(x)
             return self.cnn(x)
         ops.require_gpu(x, "VeryDeepVgg")
         ops.warn_detached_once(self, "VeryDeepVgg")
@@ -469,3 +513,12 @@ class CTCConvertor(BaseConvertor):
 @DETECTORS.register_module()
 class CRNNNet(EncodeDecodeRecognizer):
     """`recognizer/crnn.py`: the CTC-loss based recogniser."""
+
+    def set_vgg_train_backend(self, mode):
+        """`VeryDeepVgg.set_vgg_train_backend(mode)` of the backbone ("torch" | "hip"): the VGG's training graph on HIP
+        kernels, next to `set_train_backend("torch", preprocessor="hip", decoder="hip", loss="hip")` for the other stages.
+        A backbone of another type raises.  A call that fails changes nothing."""
+        if not isinstance(self.backbone, VeryDeepVgg):
+            raise ValueError(f"set_vgg_train_backend: {type(self.backbone).__name__} is not a VeryDeepVgg")
+        self.backbone.set_vgg_train_backend(mode)
+        return self

@@ -3215,6 +3215,141 @@ def crnn_maxpool(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
     return out
 
 
+# ---- VeryDeepVgg's training graph (tpspp_crnn_pool_train.hip; VeryDeepVgg.set_vgg_train_backend("hip")) ------------------
+def crnn_maxpool_bwd(dp, y, kernel=(2, 2), stride=(2, 2), padding=(0, 0), relu_mask=True):
+    """Backward of `crnn_maxpool(y, kernel, stride, padding)` (`tpspp_crnn_maxpool_bwd`): dp (N, C, Ho, Wo) -> dy like y.
+    No index map: every window of y is scanned again with the forward's rule, and an element gathers dp over the windows
+    that selected it (no atomics, bitwise reproducible).  relu_mask: the backward of the in-place ReLU that produced y in
+    the same pass -- an element with not (y > 0) receives +0."""
+    who = "crnn_maxpool_bwd"
+    y = _chk(f"{who} y", y, 4)
+    (kh, kw), (sh, sw), (ph, pw) = _pair(kernel), _pair(stride), _pair(padding)
+    N, C, H, W = y.shape
+    if min(kh, kw, sh, sw) < 1 or H + 2 * ph < kh or W + 2 * pw < kw:
+        raise ValueError(f"{who}: kernel {(kh, kw)} / stride {(sh, sw)} / padding {(ph, pw)} on a {H} x {W} map")
+    Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    dp = _chk(f"{who} dp", dp, 4)
+    if tuple(dp.shape) != (N, C, Ho, Wo) or dp.device != y.device:
+        raise ValueError(f"{who}: dp must be {(N, C, Ho, Wo)} on {y.device}, got {tuple(dp.shape)} on {dp.device}")
+    dy = torch.empty_like(y)
+    if N == 0:          # an empty batch has no device pointer to hand over
+        return dy
+    _call("tpspp_crnn_maxpool_bwd", y, dp, y, int(bool(relu_mask)), N, C, H, W, kh, kw, sh, sw, ph, pw, dy, Ho, Wo)
+    return dy
+
+
+class _ConvReluPoolFunction(torch.autograd.Function):
+    """p = maxpool(relu(conv(x) + bias)): HIP forward (`conv2d`, `crnn_maxpool`) and backward (`crnn_maxpool_bwd` with the
+    ReLU mask, then `conv2d_bwd_weight` / `conv2d_bwd_data` with relu=False, which do not read y).  Saves x, the weight and
+    y; no index map (the backward rescans y)."""
+
+    @staticmethod
+    def forward(ctx, x, w, cb, cfg):
+        cw, (k, st), pool = cfg
+        x = x.float().contiguous()
+        y = conv2d([x], cw, st, relu=True)
+        p = crnn_maxpool(y, *pool)
+        ctx.cfg = (k, st, pool, cb is not None)
+        ctx.save_for_backward(x, w, y)
+        return p
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gp):
+        k, st, pool, has_bias = ctx.cfg
+        x, w, y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_w, want_b = need[1], has_bias and need[2]
+        dx = dw = dcb = None
+        if need[0] or want_w or want_b:
+            dy = crnn_maxpool_bwd(gp.float().contiguous(), y, *pool, relu_mask=True)
+            if want_w or want_b:
+                dw, dcb = conv2d_bwd_weight([x], dy, k, st, relu=False, want_weight=want_w, want_bias=want_b)
+            if need[0]:
+                dx = conv2d_bwd_data(dy, w, [x], st, relu=False)[0]
+        return dx, dw, dcb, None
+
+
+def conv_relu_pool_autograd(x, conv, kernel=(2, 2), stride=(2, 2), padding=(0, 0), cw=None, name="pooled layer"):
+    """maxpool(relu(conv(x))) -- conv0, conv1, conv3 and conv5 of VeryDeepVgg with the nn.MaxPool2d(kernel, stride, padding)
+    behind them -- inside an autograd graph on the HIP kernels.  conv: nn.Conv2d (3x3 'same', bias allowed); cw: the
+    forward's ConvWeight (a cache the caller keys on the parameters' versions), built on the device here if None.  The
+    backward honours `needs_input_grad`: nothing is launched for a frozen layer whose input needs no gradient."""
+    _chk_gpu(name, x)
+    kst = _conv_spec(conv, f"{name} conv", bias_ok=True)
+    pool = (_pair(kernel), _pair(stride), _pair(padding))
+    if cw is None:
+        cw = prep_conv_weight_device(conv.weight, conv.bias)
+    return _ConvReluPoolFunction.apply(x, conv.weight, conv.bias, (cw, kst, pool))
+
+
+def conv6_extend(conv):
+    """(ConvWeight, w3) of VeryDeepVgg's conv6 for the HIP kernels: the 2x2 valid convolution as the 3x3 kernel w3 whose
+    first row and first column are zero (`VeryDeepVgg._hip_weights`), prepared on the device without BatchNorm folded."""
+    w3 = Fn.pad(conv.weight.detach().float(), (1, 0, 1, 0)).contiguous()
+    return prep_conv_weight_device(w3, conv.bias), w3
+
+
+class _Conv6BnFunction(torch.autograd.Function):
+    """y = relu(bn(conv6(x) + bias)) of a (N, C, 2, W) map -> (N, Cout, 1, W - 1).  The zero-extended 3x3 kernel at stride
+    (2, 1) gives a W-wide map whose last column reads the right padding: it is dropped BEFORE the batch statistics (a
+    contiguous copy of the small map), and receives a zero gradient on the way back.  Otherwise `_BnStemFunction`."""
+
+    @staticmethod
+    def forward(ctx, x, w, cb, g, b, cfg):
+        (cw, w3), spec = cfg
+        x = x.float().contiguous()
+        z = conv2d([x], cw, (2, 1), relu=False)[:, :, :, :x.shape[3] - 1].contiguous()
+        mean, rstd = _bn_stats_of(z, spec)
+        y = bn_apply(z, (mean, rstd), g, b, relu=True)
+        ctx.cfg = (spec[0], cb is not None)
+        ctx.save_for_backward(x, w3, g, z, y, mean, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        train, has_bias = ctx.cfg
+        x, w3, g, z, y, mean, rstd = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy = gy.float().contiguous()
+        need_z = need[0] or need[1] or (has_bias and need[2])
+        dx = dw = dcb = dg = db = None
+        sums = (None, None, None)
+        if train or need[3] or need[4]:
+            sums = bn_bwd_reduce(gy, y, z, (mean, rstd), relu=True)
+            dg = sums[1] if need[3] else None
+            db = sums[0] if need[4] else None
+        if need_z:
+            dz, _ = bn_bwd_data(gy, y, z, (mean, rstd), g, sums, train, relu=True)
+            dz = Fn.pad(dz, (0, 1))                                # the dropped column: a zero gradient
+            if need[1] or (has_bias and need[2]):
+                dw, dcb = conv2d_bwd_weight([x], dz, 3, (2, 1), relu=False, want_weight=need[1], want_bias=has_bias and need[2])
+                if dw is not None:
+                    dw = dw[:, :, 1:, 1:].contiguous()             # the four real taps
+            if need[0]:
+                dx = conv2d_bwd_data(dz, w3, [x], (2, 1), relu=False)[0]
+        return dx, dw, dcb, dg, db, None
+
+
+def conv6_bn_autograd(x, conv, bn, prepared6=None, name="conv6"):
+    """relu(bn(conv(x))) for VeryDeepVgg's conv6 -- nn.Conv2d(C, Cout, 2, 1, 0) on a two-row map -- inside an autograd
+    graph on the HIP kernels; (N, C, 2, W) -> (N, Cout, 1, W - 1).  bn follows its own mode as in `bn_stem_autograd`
+    (.training: batch statistics over the (N, Cout, 1, W - 1) map, running statistics and num_batches_tracked updated on
+    the device).  prepared6: `conv6_extend(conv)` (a cache the caller keys on the parameters' versions)."""
+    _chk_gpu(name, x)
+    if not isinstance(conv, torch.nn.Conv2d) or (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding),
+                                                   tuple(conv.dilation), conv.groups) != ((2, 2), (1, 1), (0, 0), (1, 1), 1):
+        raise ValueError(f"{name}: expected nn.Conv2d(C, Cout, 2, 1, 0) without dilation or groups")
+    if x.dim() != 4 or x.shape[2] != 2 or x.shape[3] < 2:
+        raise ValueError(f"{name}: the HIP path needs an image height of 32 (a two-row map before conv6) and at least two "
+                         f"columns, got {tuple(x.shape)}")
+    spec = _bn_spec(bn, f"{name} bn")
+    if prepared6 is None:
+        prepared6 = conv6_extend(conv)
+    return _Conv6BnFunction.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, (prepared6, spec))
+
+
 def crnn_maxpool_blocked(x, kernel=(2, 2), stride=(2, 2), padding=(0, 0)):
     """`crnn_maxpool` on a `Blocked` (bf16) or `Blocked32` (fp32) map -> the same class (`tpspp_crnn_maxpool_blk_fwd`,
     include/tpspp_crnn_bf16.h): the bits `F.max_pool2d` gives on the NCHW view."""
